@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the IQ hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step = one pass of the north-star chain (u8 -> c64 -> Shift(-fs/8) -> 1024-tap
 FIR -> decimate-by-8: one hzsdr_chain_run, no full-rate c64 intermediate in HBM)
@@ -12,8 +12,14 @@ over the ranks with its RCCL exchange (the other half of the metric).
 
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel against HBM
 peak with its algorithmic bytes (3 B per input sample) and the
-HIP-event duration measured inside the timed region; `cpu_baseline` times the
-oracle (a scalar port of the reference algorithms) on a bounded sample.
+HIP-event duration measured inside the timed region.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed
+steps, the outputs of the last step (--dump-outputs) and the line.  --full adds
+everything else, each in runs of its own: the unpipelined launch times, the side
+measurements (`extra`), the Beamform section, the oracle parity check
+(`parity`) and `cpu_baseline`, which times the oracle (a scalar port of the
+reference algorithms) on a bounded sample.
 """
 import argparse
 import importlib
@@ -32,13 +38,20 @@ FP32_PEAK_TFLOPS = 157.3    # vector f32
 I8_PEAK_TOPS = 5000.0       # MI355X_MICROARCH.md: dense int8 MFMA, 2x the ~2.5 PF of bf16
 
 
-def splitmix64(seed, n):
-    idx = np.arange(1, n + 1, dtype=np.uint64)
+def splitmix64(seed, n, chunk=1 << 18):
+    # (in chunks that stay in the host's cache: the set-up of a plain run is mostly this, twice as fast as whole arrays)
+    z = np.empty(n, np.uint64)
     with np.errstate(over="ignore"):
-        z = np.uint64(seed) + idx * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
+        for a in range(0, n, chunk):
+            c = np.arange(a + 1, min(n, a + chunk) + 1, dtype=np.uint64)
+            c *= np.uint64(0x9E3779B97F4A7C15)
+            c += np.uint64(seed)
+            c ^= c >> np.uint64(30)
+            c *= np.uint64(0xBF58476D1CE4E5B9)
+            c ^= c >> np.uint64(27)
+            c *= np.uint64(0x94D049BB133111EB)
+            c ^= c >> np.uint64(31)
+            z[a:a + len(c)] = c
     return z
 
 
@@ -104,6 +117,18 @@ def stream_rot(torch, fn_i, steps, warmup):
     return a.elapsed_time(b) / steps
 
 
+def dump_outputs(d, out, clock):
+    """--dump-outputs: the output of the last timed step (complex64 samples as float32 (re, im) pairs; beyond 2^21
+    of them, the same seeded sample every run) and the chain's clock after it."""
+    os.makedirs(d, exist_ok=True)
+    y = out.cpu().numpy().view(np.float32).reshape(-1, 2)
+    cap = 1 << 21
+    if len(y) > cap:
+        y = y[np.sort(np.random.default_rng(0).choice(len(y), cap, replace=False))]
+    np.save(os.path.join(d, "output.npy"), y)
+    np.save(os.path.join(d, "clock.npy"), np.array([clock], np.float64))
+
+
 def self_launch(args):
     """Parent of a multi-rank run: spawn torch.distributed.run as a child, relay stdout
     (the ONE JSON line rank 0 prints) and stderr, return the child's exit code."""
@@ -135,10 +160,17 @@ def main():
                          "have settled whatever W is (with W = 5 the timed loop still ran through the ramp: 41.2 ... 45.1 us per "
                          "step from run to run on one box, 40.0 ... 40.3 behind 150 steps); reported as clock_ramp_ms")
     ap.add_argument("--log2n", type=int, default=24, help="samples per buffer = 2^log2n")
-    ap.add_argument("--no-extra", action="store_true", help="skip the per-config side measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle TIMING (the parity check still runs)")
-    ap.add_argument("--no-oracle", action="store_true", help="skip everything that needs oracle/ (profiling runs)")
-    ap.add_argument("--no-full-parity", action="store_true", help="skip the full-size check of the timed form (2 x batch x 2^log2n samples through the oracle)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: the unpipelined launch times, the per-config side measurements, "
+                         "the Beamform section, the oracle parity check and the CPU baseline (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed: DIR/output.npy, its output samples as float32 (re, im) "
+                         "pairs (a fixed sample of 2^21 of them when there are more), and DIR/clock.npy, the chain's clock "
+                         "after it (float64)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the per-config side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle TIMING (the parity check still runs)")
+    ap.add_argument("--no-oracle", action="store_true", help="--full: skip everything that needs oracle/ (profiling runs)")
+    ap.add_argument("--no-full-parity", action="store_true", help="--full: skip the full-size check of the timed form (2 x batch x 2^log2n samples through the oracle)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="the headline chain WITHOUT hzsdr_chain_pipeline: one launch behind the other, as rounds 1-3 measured")
     ap.add_argument("--batch", type=int, default=4,
@@ -218,6 +250,7 @@ def main():
     if piped:
         chain.pipeline(True)
     it = [0]
+    last_out = [None]  # the output buffer of the last step submitted
 
     def submit(ch, k, after):
         # one stream: the NCO clock and the FIR history carry on from buffer to buffer; k buffers per call
@@ -227,6 +260,7 @@ def main():
             (ch.run_after if after else ch.run)(xs[i % nbuf], ys[i % len(ys)])
         else:
             ch.run_batch([xs[(i + j) % nbuf] for j in range(k)], [ys[(i + j) % len(ys)] for j in range(k)], after=after)
+        last_out[0] = ys[(i + k - 1) % len(ys)]
 
     def run_steps(ch, steps, batch, after):
         full, rem = divmod(steps, batch)
@@ -242,6 +276,12 @@ def main():
             run_steps(chain, 48, B, piped)
             torch.cuda.synchronize()
             ramp_steps += 48
+    # (the ramp's length is the wall clock's: the stream the warm-up and the timed steps carry on starts afresh behind
+    # it -- clock 0, no FIR history, the rotation at its first buffer -- so that what the steps compute depends on the
+    # arguments alone)
+    chain.reset()
+    it[0] = 0
+    torch.cuda.synchronize()
     run_steps(chain, args.warmup, B, piped)
     torch.cuda.synchronize()
     if world > 1:
@@ -264,10 +304,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # device time per step, launch gaps included
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out[0], chain.time())
     # the same chain one launch behind the other, in the same run: what ONE launch takes (and what rocprofv3 lists
     # per launch, `--no-pipeline`), beside the time per step of overlapping launches
     kernel_ms_plain = kernel_ms_batch_plain = None
-    if (piped or B > 1) and world == 1:
+    if (piped or B > 1) and world == 1 and args.full:
         plain = ctx.chain(hz.FMT_U8, fs).shift(shift).fir_decimate(taps, D)
 
         def time_plain(batch):
@@ -441,7 +483,7 @@ def main():
     # ---- side measurements: the other BASELINE configs (rank 0, N = 1 semantics) ----
     # (the side measurements are one-GPU figures: in a multi-rank job they would only keep the other ranks waiting at
     # the Beamform section's first collective)
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         extra = {}
         k, w = 20, 3  # median of 20 runs after 3 warm-ups, per-call HIP events
 
@@ -659,15 +701,16 @@ def main():
         result["extra"] = extra
 
     # ---- Beamform, 4 channels, on sub-groups of 1 / 2 / 4 ranks (the other half of the metric) ----
-    from importlib import import_module
-    mg = import_module("go-sdr_amd.multigpu")
-    xs, ys = xs[:1], ys[:1]  # the rotation's other buffers are no longer needed
-    torch.cuda.empty_cache()
-    try:
-        result["beamform"] = mg.bench_beamform(hz, ctx, torch, dist, rank, world, n,
-                                               steps=max(5, args.steps // 2), warmup=2, synth=synth_c64)
-    except Exception as e:  # noqa: BLE001  (the multi-GPU exchange has never met real hardware: the headline survives it)
-        result["beamform"] = {"error": f"{type(e).__name__}: {e}"}
+    if args.full:
+        from importlib import import_module
+        mg = import_module("go-sdr_amd.multigpu")
+        xs, ys = xs[:1], ys[:1]  # the rotation's other buffers are no longer needed
+        torch.cuda.empty_cache()
+        try:
+            result["beamform"] = mg.bench_beamform(hz, ctx, torch, dist, rank, world, n,
+                                                   steps=max(5, args.steps // 2), warmup=2, synth=synth_c64)
+        except Exception as e:  # noqa: BLE001  (the multi-GPU exchange has never met real hardware: the headline survives it)
+            result["beamform"] = {"error": f"{type(e).__name__}: {e}"}
     # evidence that the collective library really spanned N ranks: an all-reduce of (rank + 1)
     rccl = {"backend": backend if world > 1 else None, "world_size": world}
     if world > 1:
@@ -687,7 +730,7 @@ def main():
 
     # ---- the oracle section (the cpu_baseline leg): the checker first, then its timing -------
     parity_ok = True
-    if rank == 0 and not args.no_oracle:
+    if rank == 0 and args.full and not args.no_oracle:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as orc
         ns = min(n, 1 << 22)

@@ -122,7 +122,7 @@ def test_two_rank_bench_on_one_gpu_runs_every_multi_rank_code_path():
     from conftest import ROOT
     env = dict(os.environ, HZ_BENCH_SAME_DEVICE="1", HZ_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "4", "--ramp-ms", "0",
-                        "--log2n", "20", "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+                        "--log2n", "20", "--full", "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

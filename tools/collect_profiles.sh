@@ -8,13 +8,13 @@ tag=${1:-r06}
 out=gpurun_out/prof_$tag
 export TMPDIR=/tmp
 mkdir -p $out
-python3 bench.py > $out/bench.json 2> $out/bench.err
-python3 bench.py --no-extra --no-cpu-baseline --steps 20 --warmup 5 > $out/bench_driver_style.json 2> /dev/null
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --no-extra --no-cpu-baseline --steps 20 --warmup 5 > $out/bench_driver_style.json 2> /dev/null
 # per-launch kernel times: ONE buffer per launch, one launch behind the other (what rounds 1-4 listed), then the benchmarked
 # form (four buffers per launch, overlapped)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace -- python3 bench.py --no-oracle --no-extra --no-pipeline --batch 1 > $out/bench_profiled.json 2> /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace_batch -- python3 bench.py --no-oracle --no-extra --no-pipeline > $out/bench_profiled_batch.json 2> /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace_pipelined -- python3 bench.py --no-oracle --no-extra > $out/bench_profiled_pipelined.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace -- python3 bench.py --full --no-oracle --no-extra --no-pipeline --batch 1 > $out/bench_profiled.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace_batch -- python3 bench.py --full --no-oracle --no-extra --no-pipeline > $out/bench_profiled_batch.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace_pipelined -- python3 bench.py --full --no-oracle --no-extra > $out/bench_profiled_pipelined.json 2> /dev/null
 K="chain_batch4 chain_fft convert shift_gain conv chain_c64 beamform downsample scale fftbig16 fftbig18"
 REPS=6 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 tools/prof_kernels.py $K > /dev/null 2>&1
 REPS=6 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 tools/prof_kernels.py $K > /dev/null 2>&1
