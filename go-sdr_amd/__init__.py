@@ -402,6 +402,14 @@ class Context:
     def chain(self, src_fmt, sample_rate=0):
         return Chain(self, src_fmt, sample_rate)
 
+    def spectrum(self, src_fmt, n, hop=None, avg=1, window=None, scale=1.0, order=None, db=False, sample_rate=None):
+        """The fused power spectrum (include/hzsdr_spectrum.h, spectrum.Spectrum): frames of n samples `hop` apart
+        (default n), windowed, |X|^2 averaged over `avg` frames per row; scale a number or "power" / "density"
+        (spectrum.spectrum_scale; "density" needs sample_rate); order NEGATIVE_FIRST (default) or ZERO_FIRST."""
+        from .spectrum import NegativeFirst, Spectrum
+        return Spectrum(self, src_fmt, n, hop, avg, window, scale, NegativeFirst if order is None else order, db,
+                        sample_rate)
+
 
 class LookupTable:
     """sdr.LookupTable (iq_lookup_table.go:36-50)."""
@@ -796,3 +804,10 @@ class Ring:
             self.iq = None
             lib.hzsdr_ring_free(self._h)
             self._h = C.c_void_p()
+
+
+from ._capi import (ORDER_NEGATIVE_FIRST, ORDER_ZERO_FIRST, SPECTRUM_FORM_AUTO,  # noqa: E402
+                    SPECTRUM_FORM_FRAME_PARALLEL, SPECTRUM_FORM_ROW_WALK)
+from .spectrum import Spectrum  # noqa: E402
+
+ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

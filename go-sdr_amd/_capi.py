@@ -178,7 +178,22 @@ SIGNATURES = {
     "hzsdr_ring_free": (i32, [vp]),
 }
 
-for _name, (_res, _args) in SIGNATURES.items():
+# name -> (restype, argtypes); every symbol include/hzsdr_spectrum.h declares
+SPECTRUM_SIGNATURES = {
+    "hzsdr_spectrum_create": (i32, [vp, i32, sz, sz, sz, C.POINTER(f32), f32, i32, i32, pvp]),
+    "hzsdr_spectrum_push": (i32, [vp, vp, sz, vp, sz, psz]),
+    "hzsdr_spectrum_rows_for": (i32, [vp, sz, psz]),
+    "hzsdr_spectrum_pending": (i32, [vp, psz, psz]),
+    "hzsdr_spectrum_options": (i32, [vp, i32]),
+    "hzsdr_spectrum_last_form": (i32, [vp, C.POINTER(i32)]),
+    "hzsdr_spectrum_reset": (i32, [vp]),
+    "hzsdr_spectrum_free": (i32, [vp]),
+}
+ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST = 0, 1  # fft.ZeroFirst = false, fft.NegativeFirst = true (fft/result.go:34-47)
+SPECTRUM_POWER, SPECTRUM_DB = 0, 1
+SPECTRUM_FORM_AUTO, SPECTRUM_FORM_ROW_WALK, SPECTRUM_FORM_FRAME_PARALLEL = 0, 1, 2
+
+for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/hzsdr.h"
+#include "../../include/hzsdr_spectrum.h"
 
 namespace hzsdr {
 
@@ -872,4 +873,53 @@ struct Fused {
 };
 
 }  // namespace stream
+
+namespace fft {
+// The fused power spectrum (include/hzsdr_spectrum.h): Push consumes every sample it is given and returns the rows
+// that complete, rows x n float32, row-major, in the spectrum's fft.Order (fft/result.go:34-47).
+class Spectrum {
+public:
+    Spectrum(const Context &x, int src_format, size_t n, size_t hop, size_t avg, const std::vector<float> &window, float scale,
+             int order = HZSDR_ORDER_NEGATIVE_FIRST, bool db = false)
+        : x_(x), n_(n) {
+        check(x_.raw(), hzsdr_spectrum_create(x_.raw(), src_format, n, hop, avg, window.empty() ? nullptr : window.data(), scale,
+                                              order, db ? HZSDR_SPECTRUM_DB : HZSDR_SPECTRUM_POWER, &s_));
+    }
+    ~Spectrum() { if (s_) hzsdr_spectrum_free(s_); }
+    Spectrum(const Spectrum &) = delete;
+    Spectrum &operator=(const Spectrum &) = delete;
+    size_t RowsFor(size_t n_in) const {
+        size_t r = 0;
+        check(x_.raw(), hzsdr_spectrum_rows_for(s_, n_in, &r));
+        return r;
+    }
+    // (a HOST context's buffers: the rows come back in a vector)
+    std::vector<float> Push(Samples in) {
+        std::vector<float> out(RowsFor(in.length) * n_);
+        size_t rows = 0;
+        check(x_.raw(), hzsdr_spectrum_push(s_, in.data, in.length, out.empty() ? nullptr : out.data(), out.size() / n_, &rows));
+        out.resize(rows * n_);
+        return out;
+    }
+    // -> (frames summed into the open row, samples held for the next frame)
+    std::pair<size_t, size_t> Pending() const {
+        size_t f = 0, h = 0;
+        check(x_.raw(), hzsdr_spectrum_pending(s_, &f, &h));
+        return {f, h};
+    }
+    Spectrum &Options(int form) { check(x_.raw(), hzsdr_spectrum_options(s_, form)); return *this; }
+    int LastForm() const {
+        int f = 0;
+        check(x_.raw(), hzsdr_spectrum_last_form(s_, &f));
+        return f;
+    }
+    void Reset() { check(x_.raw(), hzsdr_spectrum_reset(s_)); }
+    size_t Bins() const { return n_; }
+
+private:
+    const Context &x_;
+    size_t n_;
+    hzsdr_spectrum *s_ = nullptr;
+};
+}  // namespace fft
 }  // namespace hzsdr

@@ -818,3 +818,22 @@ class Beamform(Reader):
 __all__ = ["Reader", "BufferReader", "ReadTransformer", "Stream", "Beamform", "ChainReader", "read_full",
            "read_at_least", "EOF", "ErrShortBuffer", "ErrUnexpectedEOF", "READER_BLOCK",
            "beamform_angles", "beamform_angles_2d"]
+
+
+# ---- spectra of a Reader (include/hzsdr_spectrum.h) -------------------------------------------
+
+def spectrum_rows(r, spectrum, block=READER_BLOCK):
+    """Read `r` to its end in blocks of `block` samples, push them through `spectrum` (a spectrum.Spectrum of the
+    reader's format on a HOST context) and yield (rows, sample_rate, order) for every block that completes rows.
+    (rows, r.sample_rate(), spectrum.order) are what the FrequencySlice helpers of `spectrum` take, row by row."""
+    if spectrum.src_fmt != r.sample_format():
+        raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+    buf = make_samples(r.sample_format(), block)
+    while True:
+        try:
+            k = r.read(buf)
+        except EOF:
+            return
+        rows = spectrum.push(buf[:k])
+        if len(rows):
+            yield rows, r.sample_rate(), spectrum.order
