@@ -189,7 +189,9 @@ static void mm_geometry(hzsdr_chain *c) {
     // q = round(h' 2^S) with |q| <= 2^30 (hz_firmm_plan.h: digit_shift)
     const int S = mm::digit_shift(c->taps_host.data(), c->ntaps, mm_scale(c));
     if (c->mm_ver == 2) {
-        const mm2::Geom g2 = mm2::make_geom((int)c->ntaps, D, c->off, S);
+        mm2::Geom g2 = mm2::make_geom((int)c->ntaps, D, c->off, S);
+        mm2::plane0_window(g2, D, c->taps_host.data(), mm_scale(c));
+        c->mm_p0[0] = g2.p0_lo, c->mm_p0[1] = g2.p0_hi;
         mm::Geom &g = c->mmg;
         g.ntaps = g2.ntaps, g.w0 = g2.w0, g.ks = g2.ks, g.ne = g2.ne, g.e0 = g2.e0, g.shift = g2.shift, g.off = g2.off;
     } else {
@@ -560,7 +562,7 @@ static int mm2_launch(hzsdr_chain *c, const void *in, void *out, size_t n, const
                       const mm2::Fix &F, const CallBatch *cbp) {
     mm2::Geom g2{};
     g2.ntaps = c->mmg.ntaps, g2.w0 = c->mmg.w0, g2.ks = c->mmg.ks, g2.ne = c->mmg.ne, g2.e0 = c->mmg.e0, g2.shift = c->mmg.shift,
-    g2.off = c->mmg.off;
+    g2.off = c->mmg.off, g2.p0_lo = c->mm_p0[0], g2.p0_hi = c->mm_p0[1];
     const void *in1[1] = {in};
     void *out1[1] = {out};
     const CallBatch one{in1, out1, 1, n, n / c->factor};

@@ -53,6 +53,7 @@ struct hzsdr_chain {
     bool mm_ok = false;
     int mm_ver = 1;  // 1: hz_firmm.h (one round of chunk workgroups), 2: hz_firmm2.h (persistent passes; D = 8)
     hz::mm::Geom mmg{};
+    int mm_p0[2] = {0, 0};  // mm_ver 2: the step pairs on which plane 0 is multiplied (hz_firmm2_plan.h, plane0_window)
     void *taps_dev = nullptr;
     std::map<uint64_t, void *> mm_cache;
     // the last `off` RAW samples of the previous call (two buffers, flipped with hist[]): valid

@@ -193,6 +193,10 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     constexpr bool STRAIGHT = NG > 0 && UG == 0;
     constexpr int KU = NG > 0 ? ((pass_tiles(D) - 1 + NG) * PPT + 63) / 64 : kU;
     constexpr bool kWhole = NG > 0 && ((pass_tiles(D) - 1 + NG) * PPT) % 64 == 0;  // every lane has KU pieces
+    // (1 << 29: the straight-line form at D = 8 with ONE digit plane per A fragment -- v_mfma_i32_16x16x64_i8 over PAIRS
+    // of steps, plane 0 only on the pairs [G.p0_lo, G.p0_hi) where some tap can have a nonzero top digit; see the loop)
+    constexpr bool kPlane = STRAIGHT && D == 8 && (EXP & (1 << 29)) != 0;
+    static_assert(!kPlane || (EXP & (256 | 524288 | (1 << 23) | (1 << 27) | (1 << 28))) == 0, "not with the pair loop's experiments");
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
     const int wb = blockIdx.x;
     const int n = l & 31, h = l >> 5;
@@ -545,6 +549,95 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     const int f_stride = G.ne * 64;
     const int groups = NG > 0 ? NG : G.ks / GS;  // (NG > 0: the host launches this instantiation for ks = NG GS only)
 
+    // The per-plane matrix loop (kPlane).  The pair loop's A fragment holds TWO digit planes (rows: 8 outputs x (re, im)
+    // x planes 2 f, 2 f + 1), and for most taps of a decimating low-pass the top plane is zero: |q| <= 127 (2^16 + 2^8 + 1)
+    // (hz_firmm2_plan.h, plane0_window) -- the tails of a windowed sinc, 70 % of the taps of the benchmarked filter.  The
+    // MFMA still runs, half of its rows zero, at ~0.8 of a full one's energy, and at the chip's power cap energy is time
+    // (DESIGN section 4).  Here a fragment is ONE plane: v_mfma_i32_16x16x64_i8, rows = 8 outputs x (re, im), K = 64
+    // bytes = two of the pair loop's steps, columns = 16 tiles; four column blocks = the pass's 64 tiles, sixteen
+    // accumulators of four registers (the same 64).  Plane 0's MFMAs run on the pairs [G.p0_lo, G.p0_hi) only, one
+    // uniform branch per pair.  Lane l: A row l & 15 (output (l & 15) >> 1, part l & 1), B column l & 15, K piece
+    // kq = l >> 4 of the pair -- piece kq of the tile's window at 64 t bytes, and the table's entry E = (D / 8) i - kq -
+    // 4 t + e0, whose part and plane rows are the pair loop's own (T[f][E][part][pl]): no other table.  Operands one
+    // pair ahead, one LDS read behind each of the first eight MFMAs; plane 0's operand is read on every pair (a read is
+    // cheap, a branch in the middle of the reads is not).  tools/mfma_plane_skip.hip prices the two loops bare.
+    [[maybe_unused]] auto plane_loop = [&](v4i(&pa)[4][4], int tab_off) {
+        constexpr int KP = NG * GS / 2;                             // step pairs
+        constexpr int FS = 64 * (2 * (2 * KP + 4) + (D / 8) * (kT - 1) + 1);  // bytes of a fragment's entries (64 G.ne)
+        const int r16 = l & 15, kq = l >> 4;
+        // (the lane's entry of the LAST pair, kept from folding back: DS offsets are unsigned)
+        int a_off = 64 * ((D / 8) * (r16 >> 1) - kq + G.e0) + 32 * (r16 & 1) - 256 * (KP - 1) + tab_off;
+        asm volatile("" : "+v"(a_off));
+        const uint8_t *ap = tabp + a_off;
+        const uint8_t *bp = slot + TS * r16 + 16 * kq;
+        // (plane 0's pairs as a bit mask in scalar registers, made opaque at every pair: left to itself the compiler
+        // hoists the 34 comparisons to the kernel's head and keeps them as lane masks in a VGPR, two v_readlane each)
+        uint64_t p0_mask = (G.p0_hi >= 64 ? ~0ull : (1ull << G.p0_hi) - 1) & ~((1ull << G.p0_lo) - 1);
+        v4i a[2][4], b[2][4];
+        auto load = [&](auto tc) {  // pair t's operands, in the order the pair uses them (plane 0 last)
+            constexpr int t = decltype(tc)::value, r = t & 1;
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int p = u == 0 ? 1 : u < 5 ? -1 : u == 7 ? 0 : u - 3, j = u - 1;
+                if (p >= 0) a[r][p] = *reinterpret_cast<const v4i *>(ap + (p >> 1) * FS + 16 * (p & 1) + 256 * (KP - 1 - t));
+                else b[r][j] = *reinterpret_cast<const v4i *>(bp + TS * (16 * j + t / 2) + 64 * (t & 1));
+            }
+        };
+        constexpr bool kFirstC0 = (EXP & 65536) != 0;  // (planes 1 .. 3: the first pair's MFMAs with the constant 0 as C)
+        if constexpr (!kFirstC0) {
+#pragma unroll
+            for (int p = 1; p < 4; p++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) pa[p][j] = v4i{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) pa[0][j] = v4i{0, 0, 0, 0};
+        load(std::integral_constant<int, 0>{});
+        auto pair = [&](auto self, auto tc) {
+            constexpr int t = decltype(tc)::value, r = t & 1;
+            if constexpr (t < KP) {
+                if constexpr (t + 1 < KP) load(std::integral_constant<int, t + 1>{});
+#pragma unroll
+                for (int p = 1; p < 4; p++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        if constexpr (kFirstC0 && t == 0)
+                            asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(pa[p][j]) : "v"(a[r][p]), "v"(b[r][j]));
+                        else
+                            pa[p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[r][p], b[r][j], pa[p][j], 0, 0, 0);
+                    }
+                // (u8: the next pass's bytes get their sign flip here, in the shadow of the wave's own MFMAs -- EXP 262144
+                // of the pair loop, four registers per pair, done a pair before the end)
+                if constexpr (FMT == HZSDR_FMT_U8 && (EXP & 262144) != 0) {
+                    constexpr int kFlipFirst = KP - 1 - (KU + 3) / 4;
+                    if constexpr (t == kFlipFirst) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+                    if constexpr (t >= kFlipFirst && 4 * (t - kFlipFirst) < KU) {
+#pragma unroll
+                        for (int u = 4 * (t - kFlipFirst); u < KU && u < 4 * (t - kFlipFirst) + 4; u++) {
+                            x[u] ^= (int)0x80808080;
+                            asm volatile("" : "+v"(x[u]));
+                        }
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 8; q++) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+                    if constexpr (t + 1 < KP) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // LDS read
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("" : "+s"(p0_mask));
+                if ((p0_mask >> t) & 1) {  // (uniform)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) pa[0][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[r][0], b[r][j], pa[0][j], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                self(self, std::integral_constant<int, t + 1>{});
+            }
+        };
+        pair(pair, std::integral_constant<int, 0>{});
+    };
+
     bool first_seg = true, first_stamp = true;
     const double k3 = __hiloint2double((1023 - G.shift) << 20, 0), k2 = k3 * 256.0, k1 = k3 * 65536.0, k0 = k3 * 16777216.0;  // 2^-S 256^d
     // a lane holds outputs 4 h + a (a = 0 .. 3) of tile n of each block: planes 2 f + pl at q = 4 a + 2 part + pl.
@@ -581,6 +674,45 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                     c2[pt] = (float)v;
                 }
                 y[b][aa] = make_float2(c2[0], c2[1]);
+            }
+    };
+    // The same combination over the per-plane loop's accumulators (kPlane): plane p, column block j (tiles 16 j + c), lane
+    // l = 16 g + c holds rows 4 g + k = 2 i + part, i.e. outputs i = 4 (l >> 5) + 2 ((l >> 4) & 1) + (k >> 1) of tiles
+    // c, 16 + c, 32 + c, 48 + c.  The pair loop's lane l = 32 h + n holds outputs 4 h + a of tiles n and 32 + n: lanes l
+    // and l ^ 16 each hold half of what the other needs -- one v_permlane16_swap per pair of values (odd 16-lane rows of
+    // its first operand trade with even rows of its second) puts every value where the pair loop has it.  Same operations
+    // in the same order per output as `planes`: the same bits.
+    auto planes16 = [&](const v4i(&pa)[4][4], float2(&y)[NB][4], double dcr, double dci) {
+        float z[4][2][2];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int pt = k & 1;
+                double v = __fma_rn((double)pa[3][j][k], k3, pt ? dci : dcr);
+                v = __fma_rn((double)pa[2][j][k], k2, v);
+                if constexpr ((EXP & 16384) != 0) {
+                    const int hi = (int)(((unsigned)pa[0][j][k] << 8) + (unsigned)pa[1][j][k]);
+                    v = __fma_rn((double)hi, k1, v);
+                } else {
+                    v = __fma_rn((double)pa[1][j][k], k1, v);
+                    v = __fma_rn((double)pa[0][j][k], k0, v);
+                }
+                z[j][k >> 1][pt] = (float)v;
+            }
+#pragma unroll
+        for (int b = 0; b < NB; b++)
+#pragma unroll
+            for (int a2 = 0; a2 < 2; a2++) {
+                float w[2][2];
+#pragma unroll
+                for (int pt = 0; pt < 2; pt++) {
+                    const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(z[2 * b][a2][pt]), __float_as_uint(z[2 * b + 1][a2][pt]), false, false);
+                    w[0][pt] = __uint_as_float(sw[0]);
+                    w[1][pt] = __uint_as_float(sw[1]);
+                }
+                y[b][a2] = make_float2(w[0][0], w[0][1]);
+                y[b][2 + a2] = make_float2(w[1][0], w[1][1]);
             }
     };
     // the elementwise program over a lane's outputs m = mb + 256 b + a of a pass in the run with phase line
@@ -901,7 +1033,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             // inactive pass never reads them)
             constexpr bool kFirstC0 = STRAIGHT && (EXP & 65536) != 0;
             v16i acc[2][NB];
-            if constexpr (!kFirstC0) {
+            [[maybe_unused]] v4i pacc[4][4];
+            if constexpr (!kFirstC0 && !kPlane) {
 #pragma unroll
                 for (int f = 0; f < 2; f++)
 #pragma unroll
@@ -914,7 +1047,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             // compiler use the constant: 64 clears per pass less, exact sums all the same (tools/mm2_glitch.hip; what
             // round 3 saw "lose terms" with the constant was the mixer's packed instruction, hz_firmm.h) -- and 1.8 us
             // per call SLOWER, measured A/B on one box: the first step's destinations then overlap its sources)
-            if constexpr (STRAIGHT && (EXP & 2048) == 0 && !kFirstC0) {
+            if constexpr (STRAIGHT && (EXP & 2048) == 0 && !kFirstC0 && !kPlane) {
 #pragma unroll
                 for (int f = 0; f < 2; f++)
 #pragma unroll
@@ -923,7 +1056,10 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             if constexpr (kDefer) {
                 if (!(active && (EXP & 2) == 0)) flush_deferred();
             }
-            if (active && (EXP & 2) == 0) {
+            if constexpr (kPlane) {
+                if (active && (EXP & 2) == 0) plane_loop(pacc, tab_off);
+            }
+            if (active && (EXP & 2) == 0 && !kPlane) {
                 // step s = GS g + j of the window: the A entries 2 s below the lane's first, B piece 2 j + h of
                 // tile n + g -- constants off two per-lane addresses (NG > 0) or off two running ones
                 constexpr int KS = NG * GS;
@@ -1101,7 +1237,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             if (active) {
                 const double *dc = reinterpret_cast<const double *>(tabp + tab_off + (size_t)G.ne * 128);
                 float2 y[NB][4];
-                planes(acc, y, dc[0] * k3, dc[1] * k3);
+                if constexpr (kPlane) planes16(pacc, y, dc[0] * k3, dc[1] * k3);
+                else planes(acc, y, dc[0] * k3, dc[1] * k3);
                 if constexpr ((EXP & 64) != 0) {  // (the stamp behind the combination, not in the middle of it)
 #pragma unroll
                     for (int b = 0; b < NB; b++)

@@ -24,7 +24,10 @@ static int launch(K kernel, dim3 grid, size_t lds, hipStream_t stream, A... args
 // What the library ships of the kernel's switches (hz_firmm2.h, EXP): round 5's instruction cuts.
 // (round 6: 1 << 25, the landing's rare sign flip as a uniform branch -- it was 80 vector instructions of every pass --, and
 // 1 << 26, the one-Shift program outside the loop over the stages)
-constexpr int kLibExp = 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 << 25) | (1 << 26);
+constexpr int kLibExp = 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 << 25) | (1 << 26) | (1 << 29);
+// (1 << 29: the per-plane v_mfma_i32_16x16x64_i8 loop of the 1024-tap window at D = 8, plane 0 on its window of step
+// pairs; hzsdr_chain_fir_options' loop_form 8 keeps the pair loop of two planes per 32x32x32 fragment, for A/B)
+constexpr int kPairExp = kLibExp & ~(1 << 29);
 
 template <int FMT>
 static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *in, float2 *out, const float2 *hist,
@@ -44,9 +47,12 @@ static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *i
     (void)num_cus;
     unsigned long long *no_stamps = nullptr;
     // (the straight-line matrix loop exists for the 1024-tap window: 17 groups; `rolled`: hzsdr_chain_fir_options'
-    // loop form -- 1, 2, 4 groups per trip, anything else the instantiation for any window -- for A/B measurements)
+    // loop form -- 8 the straight-line pair loop, 1, 2, 4 groups per trip, anything else the instantiation for any
+    // window -- for A/B measurements)
     if (g.ks == 17 * 4 && rolled == 0)
         return launch(fir_mm2_kernel<FMT, 8, 17, kLibExp>, dim3(grid), lds, stream, in, out, hist, new_hist, rhist, new_rhist, taps, n, g, L, P, F, B, no_stamps);
+    if (g.ks == 17 * 4 && rolled == 8)
+        return launch(fir_mm2_kernel<FMT, 8, 17, kPairExp>, dim3(grid), lds, stream, in, out, hist, new_hist, rhist, new_rhist, taps, n, g, L, P, F, B, no_stamps);
     if (g.ks == 17 * 4 && rolled == 1)
         return launch(fir_mm2_kernel<FMT, 8, 17, kLibExp, 1>, dim3(grid), lds, stream, in, out, hist, new_hist, rhist, new_rhist, taps, n, g, L, P, F, B, no_stamps);
     if (g.ks == 17 * 4 && rolled == 2)

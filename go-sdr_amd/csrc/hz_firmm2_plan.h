@@ -63,6 +63,9 @@ struct Geom {
     int e0;     // E of (i = 0, h = 0, s = 0)
     int shift;  // S: taps are q = round(h' 2^S)
     unsigned off;
+    // the step pairs [p0_lo, p0_hi) of the per-plane matrix loop (hz_firmm2.h, kPlane) on which digit plane 0 of some
+    // table entry they read may be nonzero, in every clock run's table (plane0_window); make_geom: all of them
+    int p0_lo, p0_hi;
 };
 
 // What a call hands the kernel.  The kernel arguments are read through the scalar cache, where a miss costs
@@ -254,7 +257,56 @@ inline Geom make_geom(int ntaps, int D, unsigned off, int shift) {
     g.ne = g.e0 + (D / 8) * (kT - 1) + 1;
     g.shift = shift;
     g.off = off;
+    g.p0_lo = 0;
+    g.p0_hi = g.ks / 2;
     return g;
+}
+
+// The step pairs on which the per-plane loop must multiply digit plane 0 (hz_firmm2.h, kPlane), for EVERY clock run's
+// table of the chain (hz_firmm_plan.h, digit_table: taps h[k] exp(-i omega k step) scale, whatever omega and step).
+//
+// Plane 0 of a table byte is zero when its coefficient q satisfies -128 W <= q <= 127 W, W = 2^16 + 2^8 + 1: the three
+// balanced base-256 digits d1, d2, d3 in [-128, 127] reach exactly that range, and digit_table's digits are THE
+// balanced representation (each r = q mod 256 in [-128, 127], q <- (q - r) / 256), so d0 = 0 iff q is inside it.  (Not
+// |q| < 2^23: q = 127 W + 1 = 8 355 712 has d0 = 1.)  A byte's coefficient is +-q_re or +-q_im of one tap, q =
+// llround(c 2^S) with c = (hr cr - hi ci) scale or (hr ci + hi cr) scale, and |c| <= hypot(hr, hi) scale (1 + 2^-48)
+// (Cauchy-Schwarz, cos^2 + sin^2 = 1 to a few ulp, a few roundings; hypot itself to an ulp).  So with m = hypot(hr, hi)
+// scale 2^S: |q| <= m (1 + 2^-48) + 1/2 -- and a tap with m <= 127 W - 1 has |q| <= 127 W - 1/2 + 2^-25, i.e. (q an
+// integer) |q| <= 127 W - 1: d0 = 0
+// in every run.  Only taps with m > 127 W - 1 are "hot".  Tap k sits in ONE entry, E = e0 + (k - w0 + e) / 8 with
+// its byte pair e = (w0 - k) mod 8 (digit_table: kap = 8 (E - e0) + w0 - e); pair t reads the entries (D / 8) i - kq -
+// 4 t + e0 (i = 0 .. 7 outputs, kq = 0 .. 3 pieces).  The window is the smallest range of pairs that holds every pair
+// reading an entry with a hot tap ([0, 0): none).
+inline void plane0_window(Geom &g, int D, const double *taps, double scale) {
+    constexpr double kW = 65536.0 + 256.0 + 1.0;
+    const int np = g.ks / 2, ne = g.ne;
+    bool *hot_e = new bool[ne]();
+    for (int k = 0; k < g.ntaps; k++) {
+        const double m = ldexp(hypot(taps[2 * k], taps[2 * k + 1]) * scale, g.shift);
+        if (m <= 127.0 * kW - 1.0) continue;  // (NaN: hot)
+        for (int e = 0; e < 8; e++) {  // byte pair e of entry E holds tap 8 (E - e0) + w0 - e
+            const int num = k - g.w0 + e;
+            if (num % 8 != 0) continue;
+            const int E = g.e0 + num / 8;
+            if (E >= 0 && E < ne) hot_e[E] = true;
+        }
+    }
+    int lo = np, hi = 0;
+    for (int t = 0; t < np; t++) {
+        bool hot = false;
+        for (int i = 0; i < kT && !hot; i++)
+            for (int kq = 0; kq < 4 && !hot; kq++) {
+                const int E = (D / 8) * i - kq - 4 * t + g.e0;
+                hot = E >= 0 && E < ne && hot_e[E];
+            }
+        if (hot) {
+            if (t < lo) lo = t;
+            hi = t + 1;
+        }
+    }
+    delete[] hot_e;
+    g.p0_lo = lo < hi ? lo : 0;
+    g.p0_hi = lo < hi ? hi : 0;
 }
 
 

@@ -139,6 +139,8 @@ template <int EXP, int MIXT = 1, int NGT = 17> static void run(void *const *in, 
     const size_t n = n_each * (size_t)g_batch;
     const unsigned off = (unsigned)((ntaps - 1 + D - 1) / D * D);
     mm2::Geom g = mm2::make_geom(ntaps, D, off, 40);
+    // (the per-plane loop's plane-0 window, EXP 1 << 29: P0=lo,hi step pairs; default every pair)
+    if (const char *v = getenv("P0")) sscanf(v, "%d,%d", &g.p0_lo, &g.p0_hi);
     EwProgram P{};
     if (shift) {
         P.n = 1;
@@ -431,6 +433,9 @@ int main(int argc, char **argv) {
     run<8, 0>(in, out, taps, tab, n, ntaps, true);
     run<32, 0>(in, out, taps, tab, n, ntaps, true);
     run<64 | 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22), 0>(in, out, taps, tab, n, ntaps, true);  // (kLibExp with stamps)
+    // the per-plane v_mfma_i32_16x16x64_i8 loop (1 << 29, hz_firmm2.h kPlane) without and with stamps
+    run<8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 << 29), 0>(in, out, taps, tab, n, ntaps, true);
+    run<64 | 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 << 29), 0>(in, out, taps, tab, n, ntaps, true);
     if (getenv("BISECT")) {  // which part of the epilogue waits for the partner's loop: without the mixer, without the stores
         run<64 | 4 | 8192 | 16384 | 65536 | 131072 | 262144 | 524288, 0>(in, out, taps, tab, n, ntaps, true);
         run<64 | 8 | 8192 | 16384 | 65536 | 131072 | 262144 | 524288, 0>(in, out, taps, tab, n, ntaps, true);
