@@ -113,7 +113,8 @@ int hzsdr_memcpy_d2h(hzsdr_ctx *ctx, void *dst_host, const void *src_device, siz
 /* sdr.ConvertBuffer(dst, src), conv.go:55-93; the twelve converters
  * iq_u8.go:75-121, iq_i8.go:71-119, iq_i16.go:116-162, iq_c64.go:77-117 and
  * the native kernels iq_u8_amd64.s:27-90 / iq_u8_amd64.go:26-38.  Equal
- * formats copy min(dst_len, src_len) samples (CopySamples, copy.go:31-52).
+ * formats copy min(dst_len, src_len) samples (CopySamples, copy.go:31-52),
+ * and may overlap: the result is memmove's, as Go's copy gives it.
  * *n_out = samples written.  Errors: DST_TOO_SMALL, FORMAT_UNKNOWN. */
 int hzsdr_convert(hzsdr_ctx *ctx, int dst_format, void *dst, size_t dst_len, int src_format,
                   const void *src, size_t src_len, size_t *n_out);
