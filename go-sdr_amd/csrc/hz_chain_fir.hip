@@ -180,7 +180,7 @@ static bool mm2_eligible(const hzsdr_chain *c) {
     const mm2::Geom g = mm2::make_geom((int)c->ntaps, (int)c->factor, c->off, 0);
     const int D = (int)c->factor;
     return mm2::image_bytes(D, g.ks) <= (size_t)mm2::kU * 64 * 16 && mm2::table_bytes(g.ne) <= (size_t)4 * mm2::kThreads * 16 &&
-           mm2::lds_bytes(D, g.ks, g.ne, g.ntaps) <= 160 * 1024 && g.ntaps + D * (mm2::kFixOut - 1) <= 5 * 256;
+           mm2::lds_bytes(D, g.ks, g.ne, g.ntaps, mm2::plane_form(D, g.ks, 0)) <= 160 * 1024 && g.ntaps + D * (mm2::kFixOut - 1) <= 5 * 256;
 }
 
 static void mm_geometry(hzsdr_chain *c) {

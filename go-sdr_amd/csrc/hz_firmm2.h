@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     const float2 *__restrict__ taps, size_t n_in, Geom G, Plan L, EwProgram P, Fix F, Batch B,
     unsigned long long *stamps = nullptr) {
     extern __shared__ __attribute__((aligned(16))) uint8_t mm_lds[];
-    constexpr int TB = tile_bytes(D), TS = tile_stride(D), PPT = TB / 16, GS = PPT / 2, NB = blocks_for(D);
+    constexpr int TB = tile_bytes(D), PPT = TB / 16, GS = PPT / 2, NB = blocks_for(D);
     constexpr int kPassOut = pass_out(D);
     // pieces per lane of a pass image: known when the window is (NG groups: pass_tiles - 1 + NG tiles of PPT pieces)
     // the matrix loop as straight-line code (NG > 0, UG = 0) or as a loop of UG groups per trip
@@ -197,10 +197,13 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // of steps, plane 0 only on the pairs [G.p0_lo, G.p0_hi) where some tap can have a nonzero top digit; see the loop)
     constexpr bool kPlane = STRAIGHT && D == 8 && (EXP & (1 << 29)) != 0;
     static_assert(!kPlane || (EXP & (256 | 524288 | (1 << 23) | (1 << 27) | (1 << 28))) == 0, "not with the pair loop's experiments");
+    static_assert(!kPlane || plane_form(D, NG * GS, 0), "the host sizes the LDS by plane_form");
+    // (the per-plane loop's slots: tiles 160 bytes apart, its reads are conflict-free there -- hz_firmm2_plan.h)
+    constexpr int TS = tile_stride(D, kPlane);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
     const int wb = blockIdx.x;
     const int n = l & 31, h = l >> 5;
-    const size_t tab_lds = table_lds(G.ne), slot_sz = slot_bytes(D, G.ks);
+    const size_t tab_lds = table_lds(G.ne), slot_sz = slot_bytes(D, G.ks, kPlane);
     uint8_t *const tabp = mm_lds;
     unsigned *const ctr = reinterpret_cast<unsigned *>(mm_lds + 2 * tab_lds);
     uint8_t *const slot = mm_lds + 2 * tab_lds + kCtlBytes + (size_t)wave * slot_sz;
@@ -227,10 +230,16 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // takes as long as the partner's loop" off such stamps).
     // (1 << 24, with 64: a row of stamps for EVERY pass of the wave, up to fifteen -- a call over four buffers gives a wave
     // eight; 8 KB of staging behind the kernel's own LDS, which the harness asks for -- tools/mfma_fir2.hip PASSES=1)
+    // (the per-plane form's LDS leaves 2 KB of the CU's 160: its stamped builds stage the stamps where the fix-up task's
+    // scratch is, and the scratch moves onto the slots of waves 0 and 1, retired by then -- behind a barrier that the
+    // shipped kernel does not need; the harness asks for no LDS beyond the kernel's own)
+    constexpr bool kStampShare = kPlane && (EXP & 64) != 0;
+    static_assert(!kStampShare || (8 * 16 * 8 * kWaves <= 8192 && 2 * slot_bytes(D, NG * GS, true) >= task_bytes(D, 1025)), "the shared areas fit");
     constexpr int kStampRows = (EXP & (1 << 24)) != 0 ? 16 : 4;
     int stamp_pass = 0;
     [[maybe_unused]] unsigned long long *const lstamp =
-        reinterpret_cast<unsigned long long *>(mm_lds + lds_bytes(D, G.ks, G.ne, G.ntaps)) + (size_t)wave * (8 * kStampRows);
+        reinterpret_cast<unsigned long long *>(mm_lds + lds_bytes(D, G.ks, G.ne, G.ntaps, kPlane) - (kStampShare ? task_bytes(D, G.ntaps) : 0)) +
+        (size_t)wave * (8 * kStampRows);
     if constexpr ((EXP & 64) != 0) {
         for (int i = l; i < 8 * kStampRows; i += 64) lstamp[i] = 0;
     }
@@ -310,7 +319,9 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     uint32_t fix_m0 = 0;
     int fix_cnt = 0;
     // (the tasks' scratch in LDS behind the slots: the window's samples, the taps beside them)
-    auto task_xs = [&](const Geom &G) { return reinterpret_cast<float2 *>(mm_lds + 2 * table_lds(G.ne) + kCtlBytes + (size_t)kWaves * slot_bytes(D, G.ks)); };
+    auto task_xs = [&](const Geom &G) {
+        return reinterpret_cast<float2 *>(mm_lds + 2 * table_lds(G.ne) + kCtlBytes + (kStampShare ? 0 : (size_t)kWaves * slot_bytes(D, G.ks, kPlane)));
+    };
     auto tasks_front_cold = [&](int round, const void *in, const float2 *hist, float2 *new_hist, const uint8_t *rhist, uint8_t *new_rhist,
                                 const float2 *taps, size_t n_in, const Geom &G, const Plan &L, const EwProgram &P, const Fix &F, const Batch &B) {
         // (sample pu of the concatenation: its buffer's virtual base)
@@ -558,15 +569,17 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // accumulators of four registers (the same 64).  Plane 0's MFMAs run on the pairs [G.p0_lo, G.p0_hi) only, one
     // uniform branch per pair.  Lane l: A row l & 15 (output (l & 15) >> 1, part l & 1), B column l & 15, K piece
     // kq = l >> 4 of the pair -- piece kq of the tile's window at 64 t bytes, and the table's entry E = (D / 8) i - kq -
-    // 4 t + e0, whose part and plane rows are the pair loop's own (T[f][E][part][pl]): no other table.  Operands one
+    // 4 t + e0, whose part and plane rows are the pair loop's own (T[f][E][part][pl]): no other table in memory -- in LDS
+    // the group's staging copy has put it plane-major, P[plane][E][part] (hz_firmm2_plan.h, plane_piece: in T's order a
+    // lane group's sixteen rows lie on eight 16-byte bank groups, and every A read took twice its cycles).  Operands one
     // pair ahead, one LDS read behind each of the first eight MFMAs; plane 0's operand is read on every pair (a read is
     // cheap, a branch in the middle of the reads is not).  tools/mfma_plane_skip.hip prices the two loops bare.
     [[maybe_unused]] auto plane_loop = [&](v4i(&pa)[4][4], int tab_off) {
         constexpr int KP = NG * GS / 2;                             // step pairs
-        constexpr int FS = 64 * (2 * (2 * KP + 4) + (D / 8) * (kT - 1) + 1);  // bytes of a fragment's entries (64 G.ne)
+        constexpr int NE = 2 * (2 * KP + 4) + (D / 8) * (kT - 1) + 1;  // (G.ne)
         const int r16 = l & 15, kq = l >> 4;
         // (the lane's entry of the LAST pair, kept from folding back: DS offsets are unsigned)
-        int a_off = 64 * ((D / 8) * (r16 >> 1) - kq + G.e0) + 32 * (r16 & 1) - 256 * (KP - 1) + tab_off;
+        int a_off = plane_a_offset(NE, G.e0, 0, KP - 1, r16, kq) + tab_off;
         asm volatile("" : "+v"(a_off));
         const uint8_t *ap = tabp + a_off;
         const uint8_t *bp = slot + TS * r16 + 16 * kq;
@@ -579,7 +592,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
             for (int u = 0; u < 8; u++) {
                 const int p = u == 0 ? 1 : u < 5 ? -1 : u == 7 ? 0 : u - 3, j = u - 1;
-                if (p >= 0) a[r][p] = *reinterpret_cast<const v4i *>(ap + (p >> 1) * FS + 16 * (p & 1) + 256 * (KP - 1 - t));
+                if (p >= 0) a[r][p] = *reinterpret_cast<const v4i *>(ap + 32 * NE * p + 128 * (KP - 1 - t));
                 else b[r][j] = *reinterpret_cast<const v4i *>(bp + TS * (16 * j + t / 2) + 64 * (t & 1));
             }
         };
@@ -976,20 +989,25 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             const v4i *tg = (const v4i *)ru.tab, *th = (const v4i *)rv.tab;
             // (one table after the other: both in flight at once, beside the first pass's bytes, spilled registers)
             v4i tq[kTU];
+            // (the per-plane loop's table: plane-major in LDS)
+            auto tab_piece = [&](int q) {
+                if constexpr (kPlane) return plane_piece(2 * (NG * GS + 4) + (D / 8) * (kT - 1) + 1, q);
+                else return q;
+            };
             if (first_seg) {
 #pragma unroll
                 for (int u = 0; u < kTU; u++) tq[u] = tid + u * kThreads < tp ? tg[tid + u * kThreads] : v4i{0, 0, 0, 0};
                 if (first_stamp) stamp(14);
 #pragma unroll
                 for (int u = 0; u < kTU; u++)
-                    if (tid + u * kThreads < tp) *reinterpret_cast<v4i *>(tabp + off_a + 16 * (size_t)(tid + u * kThreads)) = tq[u];
+                    if (tid + u * kThreads < tp) *reinterpret_cast<v4i *>(tabp + off_a + 16 * (size_t)tab_piece(tid + u * kThreads)) = tq[u];
             }
             if (b_here) {
 #pragma unroll
                 for (int u = 0; u < kTU; u++) tq[u] = tid + u * kThreads < tp ? th[tid + u * kThreads] : v4i{0, 0, 0, 0};
 #pragma unroll
                 for (int u = 0; u < kTU; u++)
-                    if (tid + u * kThreads < tp) *reinterpret_cast<v4i *>(tabp + off_b + 16 * (size_t)(tid + u * kThreads)) = tq[u];
+                    if (tid + u * kThreads < tp) *reinterpret_cast<v4i *>(tabp + off_b + 16 * (size_t)tab_piece(tid + u * kThreads)) = tq[u];
             }
         }
         first_seg = false;
@@ -1293,7 +1311,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // (Task t of a round goes to workgroup grid - 1 - t: the history tasks sit on the first sixteen workgroups' old
     // waves, and the few tasks of a call with one clock boundary should not queue up behind them.)
     for (int round = 0; (L.grid - 1 - wb) + round * L.grid < L.n_task; round++) {  // (uniform; round > 0: more tasks than workgroups)
-        if (round > 0) __syncthreads();
+        if (round > 0 || kStampShare) __syncthreads();
         tasks_front(round);
         __syncthreads();
         tasks_back();

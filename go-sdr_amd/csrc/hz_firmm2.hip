@@ -34,7 +34,9 @@ static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *i
                       float2 *new_hist, const uint8_t *rhist, uint8_t *new_rhist, const float2 *taps, size_t n, const Geom &g,
                       Plan L, const EwProgram &P, const Fix &F, const Batch &B, int rolled) {
     if (!factor_ok(D)) return HZSDR_ERR_INVALID_ARGUMENT;
-    const size_t lds = lds_bytes((int)D, g.ks, g.ne, g.ntaps);
+    // (the per-plane instantiation's slots are wider: the same flag picks the kernel below and sizes its LDS)
+    const bool plane = plane_form((int)D, g.ks, rolled);
+    const size_t lds = lds_bytes((int)D, g.ks, g.ne, g.ntaps, plane);
     if (D == 16) {  // (256 outputs per pass, one column block; the straight-line loop for the 1024-tap window: 9 groups of 8 steps)
         const int grid16 = std::max(1, L.grid);
         unsigned long long *no_stamps16 = nullptr;
@@ -49,7 +51,7 @@ static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *i
     // (the straight-line matrix loop exists for the 1024-tap window: 17 groups; `rolled`: hzsdr_chain_fir_options'
     // loop form -- 8 the straight-line pair loop, 1, 2, 4 groups per trip, anything else the instantiation for any
     // window -- for A/B measurements)
-    if (g.ks == 17 * 4 && rolled == 0)
+    if (plane)
         return launch(fir_mm2_kernel<FMT, 8, 17, kLibExp>, dim3(grid), lds, stream, in, out, hist, new_hist, rhist, new_rhist, taps, n, g, L, P, F, B, no_stamps);
     if (g.ks == 17 * 4 && rolled == 8)
         return launch(fir_mm2_kernel<FMT, 8, 17, kPairExp>, dim3(grid), lds, stream, in, out, hist, new_hist, rhist, new_rhist, taps, n, g, L, P, F, B, no_stamps);

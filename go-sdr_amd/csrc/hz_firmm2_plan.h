@@ -40,20 +40,48 @@ constexpr size_t image_bytes(int D, int ks) { return (size_t)(pass_tiles(D) - 1)
 // lane group) then falls on 16 different 16-byte bank groups (9 t + p mod 16 for 128-byte tiles), and --
 // unlike an XOR swizzle -- every address of the matrix loop is ONE per-lane base plus a constant: tile
 // n + g, piece 2 j + h, block b sit at base + tile_stride g + 32 j + 32 tile_stride b.
-constexpr int tile_stride(int D) { return tile_bytes(D) + 16; }
+// `plane`: the per-plane matrix loop (hz_firmm2.h, kPlane; plane_form below).  Its lane 16 kq + r reads piece kq of
+// tile r, and ds_read_b128 serves a wave in four groups of sixteen lanes that MIX two values of kq (lanes 0-3, 12-15
+// with kq and lanes 20-27 with kq + 1; 4-11, 16-19 and 28-31; the same + 32).  With a stride of 16 c bytes, c odd, c r
+// mod 16 takes every value, so the + 1 of kq always meets a 16-byte bank group that the other half of the lane group
+// uses: 2-way conflicts on every read at 144 bytes.  c = 2 mod 8 puts the two halves on even and on odd groups: 32 bytes
+// of padding, 160 (176, 192 and 208 conflict again).  tests/host/plane_layout.cpp counts the cycles of both.
+constexpr int tile_stride(int D, bool plane = false) { return tile_bytes(D) + (plane ? 32 : 16); }
+// The instantiation a launch takes (hz_firmm2.hip: launch_fmt) runs the per-plane loop: factor 8, the 1024-tap window's
+// 17 groups of 4 steps, the default loop form.  Host and kernel size the LDS by this one flag.
+constexpr bool plane_form(int D, int ks, int loop_form) { return D == 8 && ks == 17 * 4 && loop_form == 0; }
 // (the loop's look-ahead reads two steps past the last window: one tile behind the image)
-constexpr size_t slot_bytes(int D, int ks) {
-    return ((image_bytes(D, ks) / tile_bytes(D) + 1) * tile_stride(D) + 255) / 256 * 256;
+constexpr size_t slot_bytes(int D, int ks, bool plane = false) {
+    return ((image_bytes(D, ks) / tile_bytes(D) + 1) * tile_stride(D, plane) + 255) / 256 * 256;
 }
 // table: T[f][E][part][pl] of 16 bytes (digit plane 2 f + pl, most significant first), then (dc_re, dc_im), then the
 // mixer's eight step factors of the run (step_factors below)
 constexpr size_t table_bytes(int ne) { return (size_t)ne * 128 + 16 + 128; }
 constexpr size_t table_lds(int ne) { return (table_bytes(ne) + 255) / 256 * 256; }
 constexpr size_t kCtlBytes = 512;  // the queue's counter
-// two tables, the queue's counter, a slot per wave, the fix-up task's window (ntaps + D (kFixOut - 1) samples) and taps
-constexpr size_t lds_bytes(int D, int ks, int ne, int ntaps) {
-    return 2 * table_lds(ne) + kCtlBytes + kWaves * slot_bytes(D, ks) + ((size_t)(2 * ntaps + D * (kFixOut - 1)) * 8 + 255) / 256 * 256;
+// the fix-up task's window (ntaps + D (kFixOut - 1) samples) and taps
+constexpr size_t task_bytes(int D, int ntaps) { return ((size_t)(2 * ntaps + D * (kFixOut - 1)) * 8 + 255) / 256 * 256; }
+// two tables, the queue's counter, a slot per wave, the fix-up task's scratch
+constexpr size_t lds_bytes(int D, int ks, int ne, int ntaps, bool plane = false) {
+    return 2 * table_lds(ne) + kCtlBytes + kWaves * slot_bytes(D, ks, plane) + task_bytes(D, ntaps);
 }
+
+// The per-plane loop's tap table in LDS is PLANE-MAJOR: P[plane][E][part] of 16 bytes, permuted while it is staged (the
+// table in global memory keeps T[f][E][part][pl]; the pieces behind the 8 ne of the digits -- the constant term, the
+// step factors -- stay where they are).  Lane (r16, kq) of the loop reads row r16 = 2 i + part of entry E = i - kq -
+// 4 t + e0 on pair t: in T that is 64 (i - kq) + 32 part, sixteen lanes of a ds_read_b128 group on eight 16-byte bank
+// groups, 2-way; in P it is 32 (i - kq) + 16 part = 16 r16 - 32 kq, contiguous per kq and the two halves of a lane
+// group either apart or on the SAME addresses (a broadcast).
+// piece q of T -> its piece in LDS
+constexpr int plane_piece(int ne, int q) {
+    return q >= 8 * ne ? q : ((2 * (q / (4 * ne)) + (q & 1)) * ne + (q % (4 * ne)) / 4) * 2 + ((q >> 1) & 1);
+}
+// byte offset in the LDS table of what lane (r16, kq) reads as plane p's A operand on pair t (D = 8)
+constexpr int plane_a_offset(int ne, int e0, int p, int t, int r16, int kq) {
+    return 32 * ne * p + 32 * ((r16 >> 1) - kq - 4 * t + e0) + 16 * (r16 & 1);
+}
+// ... and in the tile slot as column block j's B operand: piece kq + 4 (t & 1) of tile 16 j + r16 + t / 2
+constexpr int plane_b_offset(int ts, int j, int t, int r16, int kq) { return ts * (16 * j + t / 2 + r16) + 64 * (t & 1) + 16 * kq; }
 
 struct Geom {
     int ntaps;

@@ -175,7 +175,9 @@ template <int EXP, int MIXT = 1, int NGT = 17> static void run(void *const *in, 
         F.m_b[0] = 4096 + mm2::kFixOut * F.n_task;
         R.n_task = F.n_task;
     }
-    const size_t lds = mm2::lds_bytes(D, g.ks, g.ne, g.ntaps) + ((EXP & 64) ? ((EXP & (1 << 24)) ? 8192 : 2048) : 0);  // (+ the stamps' staging area)
+    // (+ the stamps' staging area; the per-plane form's LDS has no room behind it: its stamped builds stage the stamps inside the kernel's own, hz_firmm2.h kStampShare)
+    constexpr bool kPlaneT = (EXP & (1 << 29)) != 0;
+    const size_t lds = mm2::lds_bytes(D, g.ks, g.ne, g.ntaps, kPlaneT) + (((EXP & 64) && !kPlaneT) ? ((EXP & (1 << 24)) ? 8192 : 2048) : 0);
     const unsigned grid = (unsigned)g_grid;
     auto k = mm2::fir_mm2_kernel<HZSDR_FMT_U8, D, NGT, EXP>;
     CK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -351,6 +353,9 @@ int main(int argc, char **argv) {
     if (getenv("PASSES")) {  // the per-pass stamp table (BATCH=4 for the benchmarked form)
         run<LIB6, 0>(in, out, taps, tab, n, ntaps, true);
         run<LIB6 | 64 | (1 << 24), 0>(in, out, taps, tab, n, ntaps, true);
+        // the per-plane loop (what the library ships; P0=lo,hi for its plane-0 window)
+        run<LIB6 | (1 << 29), 0>(in, out, taps, tab, n, ntaps, true);
+        run<LIB6 | (1 << 29) | 64 | (1 << 24), 0>(in, out, taps, tab, n, ntaps, true);
         if (getenv("SPLIT")) {  // where the power goes: the same launch without its mixer, without its stores, without both, without the input
             run<LIB6 | 4, 0>(in, out, taps, tab, n, ntaps, true);
             run<LIB6 | 8, 0>(in, out, taps, tab, n, ntaps, true);

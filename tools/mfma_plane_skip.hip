@@ -10,6 +10,12 @@
 //          plane-0 window [LO, HI) plane 0 is SKIPPED (12 MFMAs and 7 reads instead of 16 and 8), or issued with a
 //          zero A (ZERO), or issued with random bytes like the others (the loop without any zero plane).
 //
+// The PLANE rows read their operands at lds + 16 lane -- contiguous, no bank conflict -- unless they say otherwise: the
+// rows "kernel's lanes" read with the addresses of the kernel's lanes (r16 = lane & 15, kq = lane >> 4: A row r16 of
+// entry i - kq - 4 t + e0, B piece kq of tile r16), plane 0's A on every pair as the kernel does, in the layout the
+// kernel had first (the table in its memory order T[f][E][part][pl], tiles 144 bytes apart: every read 2-way
+// conflicted) and in the one it has now (plane-major table, tiles 160 bytes apart: hz_firmm2_plan.h).
+//
 // Reads run AH pairs (PLANE) or 2 steps (PAIR) ahead of their MFMAs, rings of AH + 1, placed one read behind each
 // MFMA (sched_group_barrier) as the kernel places them.  Reports per form: ns per pass per SIMD (two waves, each
 // pass once), the shader clock the waves saw (s_memtime cycles per 10 ns of s_memrealtime), cycles per MFMA, and
@@ -17,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+
+#include "hz_firmm2_plan.h"
 
 #include <algorithm>
 #include <utility>
@@ -28,9 +36,15 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 // LDS: R = 24 KB of random bytes (A fragments), Z = 1 KB of zeros, H = 1 KB with the even lanes' 16 bytes zero
-// (PAIR's fragment 0 where plane 0 is zero: lane n & 1 is the plane of its row), then 6 KB of B per wave
-constexpr int kR = 0, kZ = 24576, kH = kZ + 1024, kB = kH + 1024, kBW = 6144, kLds = kB + 8 * kBW;
+// (PAIR's fragment 0 where plane 0 is zero: lane n & 1 is the plane of its row), then a slot of B per wave (the
+// contiguous rows use 6 KB of it)
+constexpr int kR = 0, kZ = 24576, kH = kZ + 1024, kB = kH + 1024, kBW = 13056, kLds = kB + 8 * kBW;
 constexpr int kPairs = 34, kSteps = 68;
+// the kernel's geometry at 1024 taps (hz_firmm2_plan.h: make_geom)
+constexpr int kNe = 152, kE0 = 144;
+enum { LAY_FLAT = 0, LAY_FIRST = 1, LAY_NOW = 2 };
+static_assert(hz::mm2::plane_a_offset(kNe, kE0, 3, 0, 15, 0) + 16 <= kZ && 64 * (7 + kE0) + 32 + 64 * kNe + 32 <= kZ, "A addresses inside the random area");
+static_assert(hz::mm2::plane_b_offset(160, 3, kPairs - 1, 15, 3) + 16 <= kBW, "B addresses inside the wave's slot");
 
 enum { FILL_SKIP = 0, FILL_ZERO = 1, FILL_RANDOM = 2 };
 
@@ -109,18 +123,29 @@ __global__ __launch_bounds__(512) void pair_pass(unsigned long long *out, int tr
 }
 
 // one plane per fragment: pair t reads A (t, p) for its planes and B (t, j); plane 0 outside [LO, HI) as FILL says
-template <int LO, int HI, int FILL, int AH>
+template <int LO, int HI, int FILL, int AH, int LAY = LAY_FLAT>
 __global__ __launch_bounds__(512) void plane_pass(unsigned long long *out, int trips, int *sink) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     fill_lds(lds, blockIdx.x);
     const int l = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint8_t *ab = lds + 16 * l, *bb = lds + kB + kBW * wave + 16 * l;
+    // (the kernel's lanes: per-lane bases, the pair and the plane / block at constant offsets)
+    const int r16 = l & 15, kq = l >> 4;
+    int a_lane = LAY == LAY_NOW ? hz::mm2::plane_a_offset(kNe, kE0, 0, kPairs - 1, r16, kq) : 64 * ((r16 >> 1) - kq - 4 * (kPairs - 1) + kE0) + 32 * (r16 & 1);
+    asm volatile("" : "+v"(a_lane));  // (the last pair's entry as the base: unsigned offsets, as the kernel)
+    const uint8_t *al = lds + kR + a_lane, *bl = lds + kB + kBW * wave + (LAY == LAY_NOW ? 160 : 144) * r16 + 16 * kq;
     auto a_addr = [&](int t, int p) -> const v4i * {
+        if constexpr (LAY == LAY_NOW) return reinterpret_cast<const v4i *>(al + 32 * kNe * p + 128 * (kPairs - 1 - t));
+        if constexpr (LAY == LAY_FIRST) return reinterpret_cast<const v4i *>(al + (p >> 1) * 64 * kNe + 16 * (p & 1) + 256 * (kPairs - 1 - t));
         if (p == 0 && FILL == FILL_ZERO && (t < LO || t >= HI)) return reinterpret_cast<const v4i *>(ab + kZ);
         return reinterpret_cast<const v4i *>(ab + kR + ((4 * t + p) % 24) * 1024);
     };
-    auto b_addr = [&](int t, int j) { return reinterpret_cast<const v4i *>(bb + ((4 * t + j) % 6) * 1024); };
-    auto has0 = [](int t) { return FILL != FILL_SKIP || (t >= LO && t < HI); };
+    auto b_addr = [&](int t, int j) {
+        if constexpr (LAY != LAY_FLAT) return reinterpret_cast<const v4i *>(bl + (LAY == LAY_NOW ? 160 : 144) * (16 * j + t / 2) + 64 * (t & 1));
+        return reinterpret_cast<const v4i *>(bb + ((4 * t + j) % 6) * 1024);
+    };
+    static_assert(LAY == LAY_FLAT || FILL != FILL_ZERO, "the kernel's lanes read the table itself");
+    auto has0 = [](int t) { return LAY != LAY_FLAT || FILL != FILL_SKIP || (t >= LO && t < HI); };  // (plane 0's A: the kernel reads it on every pair)
     constexpr int RG = AH + 1;
     v4i c[4][4];
     const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
@@ -146,7 +171,7 @@ __global__ __launch_bounds__(512) void plane_pass(unsigned long long *out, int t
 #pragma unroll
                 for (int j = 0; j < 4; j++) c[p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t % RG][p], b[t % RG][j], c[p][j], 0, 0, 0);
             constexpr int nm = h0 ? 16 : 12;
-            constexpr int nr = t + AH < kPairs ? (FILL != FILL_SKIP || (t + AH >= LO && t + AH < HI) ? 8 : 7) : 0;
+            constexpr int nr = t + AH < kPairs ? (LAY != LAY_FLAT || FILL != FILL_SKIP || (t + AH >= LO && t + AH < HI) ? 8 : 7) : 0;
 #pragma unroll
             for (int i = 0; i < nm; i++) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -213,6 +238,10 @@ int main(int argc, char **argv) {
         run("PLANE 16x16x64, plane 0 skipped outside, 0.13 (2 ahead)", plane_pass<LO, HI, FILL_SKIP, 2>, kSkip, 16, dout, sink, us);
         run("PLANE 16x16x64, all random, skip 0 (reads 1 ahead)", plane_pass<LO, HI, FILL_RANDOM, 1>, 544, 16, dout, sink, us);
         run("PLANE 16x16x64, plane 0 skipped outside, 0.13 (1 ahead)", plane_pass<LO, HI, FILL_SKIP, 1>, kSkip, 16, dout, sink, us);
+        run("... kernel's lanes, table as in memory, tiles 144 B apart", plane_pass<LO, HI, FILL_SKIP, 1, LAY_FIRST>, kSkip, 16, dout, sink, us);
+        run("... kernel's lanes, plane-major table, tiles 160 B apart", plane_pass<LO, HI, FILL_SKIP, 1, LAY_NOW>, kSkip, 16, dout, sink, us);
+        run("PLANE all random, skip 0 (1 ahead), kernel's lanes, 144 B", plane_pass<LO, HI, FILL_RANDOM, 1, LAY_FIRST>, 544, 16, dout, sink, us);
+        run("PLANE all random, skip 0 (1 ahead), kernel's lanes, 160 B", plane_pass<LO, HI, FILL_RANDOM, 1, LAY_NOW>, 544, 16, dout, sink, us);
     }
     return 0;
 }

@@ -200,7 +200,7 @@ int main(int argc, char **argv) {
     R.n_ops = P.n;
     R.grid = 256;
     mm2::phase_fix(P.op[0].tau_shift, P.segs.t0[0], P.segs.step[0], 0, &R.run[0].phi, &R.run[0].dphi);
-    const size_t lds = mm2::lds_bytes(D, g.ks, g.ne, g.ntaps);
+    const size_t lds = mm2::lds_bytes(D, g.ks, g.ne, g.ntaps, false);  // (the pair loop's slots: the checksums are its accumulators')
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
     printf("device %s, %d CUs, clock %d kHz; %d launches per leg, %d taps, %d passes per launch\n", prop.gcnArchName, prop.multiProcessorCount,
