@@ -867,6 +867,16 @@ int hzsdr_fft_plan_batch(hzsdr_ctx *ctx, void *iq, void *freq, size_t n, size_t 
     if (batch == 0 || !iq || !freq) return HZSDR_ERR_INVALID_ARGUMENT;
     if (direction != HZSDR_FFT_FORWARD && direction != HZSDR_FFT_BACKWARD) return HZSDR_ERR_INVALID_ARGUMENT;
     HZ_TRY(enter(ctx));
+    if (pow2 && fft_two_step_ok(n)) {
+        // the two-step launches carry the batch in gridDim.y (launch_cols, launch_rows, launch_rows_small): refused
+        // here, before the tables and the scratch, instead of as a launch failure inside the first transform
+        int max_y = 0;
+        HZ_HIP(ctx, hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, ctx->device));
+        if (batch > (size_t)max_y)
+            return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT,
+                        "fft: a batch of a power-of-two length 2^14 ... 2^24 must be <= the device's grid height, " +
+                            std::to_string(max_y));
+    }
     if (n > 1) {  // plan-time cost, like any planner: the tables (a chirp transform's: formed once per context and length)
         HZ_TRY(fft_prepare(ctx, n));
         // ... and the two-step lengths' scratch between the passes

@@ -230,7 +230,12 @@ int hzsdr_downsample(hzsdr_ctx *ctx, int to_format, void *to, size_t to_len, int
  * in float64 once per context and length, at plan time). */
 int hzsdr_fft_plan(hzsdr_ctx *ctx, void *iq_c64, size_t iq_len, void *freq_c64, size_t freq_len,
                    int direction, hzsdr_fft **out);
-/* `batch` independent transforms over consecutive length-n blocks of both buffers. */
+/* `batch` independent transforms over consecutive length-n blocks of both buffers.
+ * Powers of two 2^14 ... 2^24 run as two passes whose launches carry the batch in the grid's second dimension, so
+ * their batch is limited to the device's hipDeviceAttributeMaxGridDimY (65536 on an MI355X: 8 GiB per buffer at
+ * n = 2^14 already).  A larger one -> INVALID_ARGUMENT here, before any table or scratch is allocated; split it over
+ * several plans.  Every other length takes any batch its buffers hold: shorter powers of two carry it in the grid's
+ * first dimension, chirp transforms walk it in pieces of 2^25 / M transforms. */
 int hzsdr_fft_plan_batch(hzsdr_ctx *ctx, void *iq_c64, void *freq_c64, size_t n, size_t batch,
                          int direction, hzsdr_fft **out);
 /* Plan.Transform(), fft/fft.go:52-55. */

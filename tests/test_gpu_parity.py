@@ -602,8 +602,8 @@ def _rel_l2(got, want):
 def test_fft_against_float64(env, n):
     """Tolerance: relative L2 error <= 3e-7 * log2(N) + 1e-7 against numpy's
     float64 FFT (float32 butterflies; the reference pins no values: SURVEY 2b).
-    Sizes: radix-4 core (4..128, 8192), radix-16 core (256..4096), global radix-2
-    (1, 2, 2^14), two-step (2^16..2^24: kerberos 64 Ki, graft 256 Ki)."""
+    Sizes: radix-4 core (4..128), packed-math radix-16 core (256..8192, fv::ok), global
+    radix-2 pass (1 and 2 only), two-step (2^14..2^24: kerberos 64 Ki, graft 256 Ki)."""
     tol = 3e-7 * max(1, math.log2(n)) + 1e-7
     batch = 3 if n <= 8192 else (2 if n <= (1 << 18) else 1)
     x = rand_c64(n, n * batch)

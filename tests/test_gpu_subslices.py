@@ -21,13 +21,11 @@ import importlib
 import numpy as np
 import pytest
 
-from util import assert_fir_close, bits_equal, rand_c64, rand_i16, rand_i8, rand_u8, zeros
+from util import (ES, GUARD, SENT, Guarded, assert_fir_close, bits_equal, dtype_of, rand_c64, rand_i16, rand_i8, rand_u8,
+                  zeros)
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
-GUARD = 64  # bytes of sentinel either side of a slice (a multiple of 32: the slice's residue is its offset's)
-ES = {"c64": 8, "i16": 4, "u8": 2, "i8": 2}
 FMTS = {"c64": 1, "u8": 2, "i16": 3, "i8": 4}
 OFFS = {"c64": range(4), "i16": range(4), "u8": range(8), "i8": range(8)}  # every residue of 16 bytes
 LENS = [0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 63, 64, 65, 255, 256, 257, 4097, 100_003]
@@ -83,65 +81,9 @@ def data(fmt, n, seed=1):
     return _small(fmt, n, seed) if n <= (1 << 20) else _make(fmt, n, seed)
 
 
-def dtype_of(fmt):
-    return zeros(fmt, 0).dtype
-
-
 def sentinel(fmt, n):
     """A host array of the format holding the sentinel byte everywhere: what an unwritten output slice holds."""
     return np.full(n * ES[fmt], SENT, np.uint8).view(dtype_of(fmt)).reshape(zeros(fmt, n).shape)
-
-
-def typed(torch, raw, fmt):
-    if fmt == "c64":
-        return raw.view(torch.complex64)
-    if fmt == "i16":
-        return raw.view(torch.int16).view(-1, 2)
-    if fmt == "i8":
-        return raw.view(torch.int8).view(-1, 2)
-    return raw.view(-1, 2)
-
-
-class Guarded:
-    """`n` samples of `fmt`, `off` samples (plus GUARD bytes) into a sentinel-filled device allocation (or into `raw`,
-    another Guarded's allocation: a second view of the same bytes)."""
-
-    def __init__(self, torch, fmt, n, off, fill=None, raw=None):
-        es = ES[fmt]
-        self.fmt, self.n = fmt, n
-        self.lo = GUARD + off * es
-        self.hi = self.lo + n * es
-        if raw is None:
-            total = self.hi + GUARD + (-(self.hi + GUARD) % 8)
-            raw = torch.full((total,), SENT, dtype=torch.uint8, device="cuda")
-        self.raw = raw
-        assert raw.data_ptr() % 256 == 0, "the allocator's alignment changed: %#x" % raw.data_ptr()
-        self.t = typed(torch, raw, fmt)[self.lo // es:self.hi // es]
-        if n:  # (an empty slice has no address: data_ptr() is 0)
-            assert self.t.data_ptr() % 32 == (off * es) % 32, (fmt, off, self.t.data_ptr() % 32)
-        if fill is not None and n:
-            self.t.copy_(torch.from_numpy(np.array(fill)))
-
-    def bytes(self):
-        return self.raw.cpu().numpy()
-
-    def values(self):
-        return self.bytes()[self.lo:self.hi].view(dtype_of(self.fmt)).reshape(zeros(self.fmt, self.n).shape)
-
-    def check(self, want, what):
-        """The guards intact and the slice equal to `want` byte for byte (want None: the guards only)."""
-        b = self.bytes()
-        assert (b[:self.lo] == SENT).all(), (what, "guard in front written", int((b[:self.lo] != SENT).sum()))
-        assert (b[self.hi:] == SENT).all(), (what, "guard behind written", int((b[self.hi:] != SENT).sum()))
-        if want is not None:
-            w = np.ascontiguousarray(want).view(np.uint8).ravel()
-            g = b[self.lo:self.hi]
-            assert w.size == g.size, (what, w.size, g.size)
-            if not np.array_equal(g, w):
-                bad = np.flatnonzero((g != w).reshape(self.n, -1).any(1))
-                raise AssertionError("%s: %d of %d samples differ, the first at %d of the slice"
-                                     % (what, bad.size, self.n, bad[0]))
-        return b
 
 
 def _tables(orc, src_fmt, dst_fmt):
