@@ -410,6 +410,14 @@ class Context:
         return Spectrum(self, src_fmt, n, hop, avg, window, scale, NegativeFirst if order is None else order, db,
                         sample_rate)
 
+    def channelizer(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
+        """The polyphase channelizer (include/hzsdr_channelizer.h, channelizer.Channelizer): `channels` channels
+        (a power of two, 256 .. 8192) from the prototype `taps` (P * channels float32 values,
+        channelizer.channelizer_taps), frames `hop` samples apart (default `channels`); order NEGATIVE_FIRST (default)
+        or ZERO_FIRST; layout "frames" (frames x channels) or "channels" (channels x frames)."""
+        from .channelizer import Channelizer, NegativeFirst
+        return Channelizer(self, src_fmt, channels, taps, hop, NegativeFirst if order is None else order, layout)
+
 
 class LookupTable:
     """sdr.LookupTable (iq_lookup_table.go:36-50)."""
@@ -808,6 +816,8 @@ class Ring:
 
 from ._capi import (ORDER_NEGATIVE_FIRST, ORDER_ZERO_FIRST, SPECTRUM_FORM_AUTO,  # noqa: E402
                     SPECTRUM_FORM_FRAME_PARALLEL, SPECTRUM_FORM_ROW_WALK)
+from ._capi import CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR  # noqa: E402
+from .channelizer import Channelizer, channelizer_taps  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

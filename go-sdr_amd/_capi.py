@@ -193,7 +193,18 @@ ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST = 0, 1  # fft.ZeroFirst = false, fft.Nega
 SPECTRUM_POWER, SPECTRUM_DB = 0, 1
 SPECTRUM_FORM_AUTO, SPECTRUM_FORM_ROW_WALK, SPECTRUM_FORM_FRAME_PARALLEL = 0, 1, 2
 
-for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items()):
+# name -> (restype, argtypes); every symbol include/hzsdr_channelizer.h declares
+CHANNELIZER_SIGNATURES = {
+    "hzsdr_channelizer_create": (i32, [vp, i32, sz, C.POINTER(f32), sz, sz, i32, i32, pvp]),
+    "hzsdr_channelizer_push": (i32, [vp, vp, sz, vp, sz, sz, psz]),
+    "hzsdr_channelizer_frames_for": (i32, [vp, sz, psz]),
+    "hzsdr_channelizer_pending": (i32, [vp, psz, C.POINTER(u64)]),
+    "hzsdr_channelizer_reset": (i32, [vp]),
+    "hzsdr_channelizer_free": (i32, [vp]),
+}
+CHANNELIZER_FRAME_MAJOR, CHANNELIZER_CHANNEL_MAJOR = 0, 1
+
+for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/hzsdr.h"
+#include "../../include/hzsdr_channelizer.h"
 #include "../../include/hzsdr_spectrum.h"
 
 namespace hzsdr {
@@ -920,6 +921,50 @@ private:
     const Context &x_;
     size_t n_;
     hzsdr_spectrum *s_ = nullptr;
+};
+
+// The polyphase channelizer (include/hzsdr_channelizer.h): Push consumes every sample it is given and returns the
+// frames that complete as complex64, frames x channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames
+// (HZSDR_CHANNELIZER_CHANNEL_MAJOR, the pitch being the frames of the push), in the channelizer's fft.Order
+// (fft/result.go:34-47).
+class Channelizer {
+public:
+    Channelizer(const Context &x, int src_format, size_t channels, const std::vector<float> &taps, size_t hop,
+                int order = HZSDR_ORDER_NEGATIVE_FIRST, int layout = HZSDR_CHANNELIZER_FRAME_MAJOR)
+        : x_(x), m_(channels) {
+        check(x_.raw(), hzsdr_channelizer_create(x_.raw(), src_format, channels, taps.empty() ? nullptr : taps.data(), taps.size(), hop,
+                                                 order, layout, &c_));
+    }
+    ~Channelizer() { if (c_) hzsdr_channelizer_free(c_); }
+    Channelizer(const Channelizer &) = delete;
+    Channelizer &operator=(const Channelizer &) = delete;
+    size_t FramesFor(size_t n_in) const {
+        size_t f = 0;
+        check(x_.raw(), hzsdr_channelizer_frames_for(c_, n_in, &f));
+        return f;
+    }
+    // (a HOST context's buffers: the frames come back in a vector)
+    std::vector<std::complex<float>> Push(Samples in) {
+        const size_t want = FramesFor(in.length);
+        std::vector<std::complex<float>> out(want * m_);
+        size_t frames = 0;
+        check(x_.raw(), hzsdr_channelizer_push(c_, in.data, in.length, out.empty() ? nullptr : out.data(), want, want, &frames));
+        return out;
+    }
+    // -> (samples held for the next frame, index of the next frame)
+    std::pair<size_t, uint64_t> Pending() const {
+        size_t h = 0;
+        uint64_t j = 0;
+        check(x_.raw(), hzsdr_channelizer_pending(c_, &h, &j));
+        return {h, j};
+    }
+    void Reset() { check(x_.raw(), hzsdr_channelizer_reset(c_)); }
+    size_t Channels() const { return m_; }
+
+private:
+    const Context &x_;
+    size_t m_;
+    hzsdr_channelizer *c_ = nullptr;
 };
 }  // namespace fft
 }  // namespace hzsdr

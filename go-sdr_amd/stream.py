@@ -837,3 +837,22 @@ def spectrum_rows(r, spectrum, block=READER_BLOCK):
         rows = spectrum.push(buf[:k])
         if len(rows):
             yield rows, r.sample_rate(), spectrum.order
+
+
+# ---- channels of a Reader (include/hzsdr_channelizer.h) ----------------------------------------
+
+def channelizer_frames(r, channelizer, block=READER_BLOCK):
+    """Read `r` to its end in blocks of `block` samples, push them through `channelizer` (a channelizer.Channelizer
+    of the reader's format on a HOST context) and yield (frames, channel_rate, order) for every block that completes
+    frames: `frames` in the channelizer's layout, channel_rate = r.sample_rate() / hop."""
+    if channelizer.src_fmt != r.sample_format():
+        raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+    buf = make_samples(r.sample_format(), block)
+    while True:
+        try:
+            k = r.read(buf)
+        except EOF:
+            return
+        frames = channelizer.push(buf[:k])
+        if frames.shape[1 if channelizer.channel_major else 0]:
+            yield frames, channelizer.channel_rate(r.sample_rate()), channelizer.order
