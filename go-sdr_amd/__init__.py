@@ -418,6 +418,15 @@ class Context:
         from .channelizer import Channelizer, NegativeFirst
         return Channelizer(self, src_fmt, channels, taps, hop, NegativeFirst if order is None else order, layout)
 
+    def synthesizer(self, dst_fmt, channels, taps, hop=None, order=None, layout="frames"):
+        """The polyphase synthesis bank (include/hzsdr_synthesizer.h, synthesizer.Synthesizer), the channelizer's
+        adjoint: frames of `channels` channel values (a power of two, 256 .. 8192; layout "frames": frames x channels,
+        "channels": channels x frames; order NEGATIVE_FIRST (default) or ZERO_FIRST) back into one stream of dst_fmt
+        samples, `hop` samples per frame (default `channels`), with the prototype `taps` (P * channels float32 values:
+        channelizer.channelizer_taps, synthesizer.wola_taps)."""
+        from .synthesizer import NegativeFirst, Synthesizer
+        return Synthesizer(self, dst_fmt, channels, taps, hop, NegativeFirst if order is None else order, layout)
+
 
 class LookupTable:
     """sdr.LookupTable (iq_lookup_table.go:36-50)."""
@@ -818,6 +827,7 @@ from ._capi import (ORDER_NEGATIVE_FIRST, ORDER_ZERO_FIRST, SPECTRUM_FORM_AUTO, 
                     SPECTRUM_FORM_FRAME_PARALLEL, SPECTRUM_FORM_ROW_WALK)
 from ._capi import CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR  # noqa: E402
 from .channelizer import Channelizer, channelizer_taps  # noqa: E402
+from .synthesizer import Synthesizer, wola_taps  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

@@ -204,7 +204,19 @@ CHANNELIZER_SIGNATURES = {
 }
 CHANNELIZER_FRAME_MAJOR, CHANNELIZER_CHANNEL_MAJOR = 0, 1
 
-for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items()):
+# name -> (restype, argtypes); every symbol include/hzsdr_synthesizer.h declares
+SYNTHESIZER_SIGNATURES = {
+    "hzsdr_synthesizer_create": (i32, [vp, i32, sz, C.POINTER(f32), sz, sz, i32, i32, pvp]),
+    "hzsdr_synthesizer_push": (i32, [vp, vp, sz, sz, vp, sz, psz]),
+    "hzsdr_synthesizer_flush": (i32, [vp, vp, sz, psz]),
+    "hzsdr_synthesizer_pending": (i32, [vp, psz, C.POINTER(u64)]),
+    "hzsdr_synthesizer_group_frames": (i32, [vp, psz]),
+    "hzsdr_synthesizer_reset": (i32, [vp]),
+    "hzsdr_synthesizer_free": (i32, [vp]),
+}
+
+for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
+                             *SYNTHESIZER_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

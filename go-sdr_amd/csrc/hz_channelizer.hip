@@ -11,6 +11,7 @@
 // frames are dealt to workgroups that share an XCD (and so an L2), which keeps the re-reads and the taps in that L2.
 #include "hz_chain_host.h"
 #include "../../include/hzsdr_channelizer.h"
+#include "hz_polyphase.h"
 
 struct hzsdr_channelizer {
     hzsdr_ctx *ctx;
@@ -56,18 +57,6 @@ struct ChanArgs {
 
 // one term of the fold: THE expression every path evaluates (one fused multiply-add per component)
 __device__ __forceinline__ cf chan_fold(cf acc, float g, float2 x) { return cf{__fmaf_rn(g, x.x, acc.x), __fmaf_rn(g, x.y, acc.y)}; }
-
-// output position of ZeroFirst channel k (FrequencySlice.Shift, fft/result.go:82-97)
-__device__ __forceinline__ unsigned chan_pos(unsigned k, unsigned m, bool neg_first) { return neg_first ? (k + m / 2) & (m - 1) : k; }
-
-// The XCD-aware deal: the hardware hands consecutive workgroup ids to the eight XCDs in turn; this maps the ids that
-// share an XCD to a contiguous run of frame groups (bijective for any grid), so that the L/D frames that read one
-// sample, and the neighbouring frames that complete one 64-byte segment of a channel-major row, meet in one L2.
-// A speed choice only: every workgroup computes the frames of its group whatever the placement.
-__device__ __forceinline__ size_t chan_group(unsigned id, unsigned nwg) {
-    const unsigned q = nwg / 8, r = nwg % 8, x = id % 8;
-    return (size_t)(x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + id / 8;
-}
 
 // a value every lane of the wave holds the same of, as a scalar
 __device__ __forceinline__ int64_t chan_uniform(int64_t v) {

@@ -1,0 +1,347 @@
+// hz_synthesizer.hip -- the polyphase synthesis bank (include/hzsdr_synthesizer.h), the adjoint of the channelizer of
+// hz_channelizer.hip: every input frame of M channel values goes through one backward transform of the workgroup core
+// of hz_fftv.h, and the output stream is the overlap-add of the transforms' outputs, repeated with period M and
+// weighted by the prototype's taps.  The L - D partial sums behind the samples written and the rotation
+// (stream position of the next frame) mod M stay with the object between pushes.
+//
+// Two kernels per group of frames.  synthesizer_frames_kernel: a frame per transform group (fv::tpt(M) lanes), the
+// sixteen inputs of a lane loaded straight into the backward transform's first-pass slots from pos(k), w_j stored in
+// natural order to a device scratch.  synthesizer_ola_kernel: a lane per output position, the terms of the frames that
+// cover it in ascending order.  A position is covered by ceil(L / D) frames: consecutive frames are dealt to workgroups
+// that share an XCD, so that the second kernel's re-reads of w meet in one L2.  The held state makes a cut between two
+// frames free, so a push of any length is processed in groups whose scratch stays within kSynthScratchBytes.
+#include "hz_chain_host.h"
+#include "../../include/hzsdr_synthesizer.h"
+#include "hz_polyphase.h"
+
+struct hzsdr_synthesizer {
+    hzsdr_ctx *ctx;
+    int fmt;
+    size_t m, ntaps, hop;
+    int order, layout;
+    hz::fv::FvTabs tabs{};
+    float *taps = nullptr;                 // the prototype, L values
+    float2 *hold[2] = {nullptr, nullptr};  // the L - D partial sums behind the samples written: read one, write the other
+    int hcur = 0;
+    float2 *w = nullptr;  // the transforms' outputs of one group of frames
+    size_t wcap = 0;      // ... frames it has room for
+    size_t held = 0;      // partial sums held: 0 before the first frame, L - D after it
+    size_t rot = 0;       // (stream position of the next frame's first sample) mod M
+    uint64_t frame = 0;   // index of the next frame
+};
+
+namespace hz {
+
+// The scratch one group of frames may take (group_frames * M * 8 bytes): small enough to stay in the memory-side cache
+// between the two kernels, large enough that the launches of a group do not show.
+constexpr size_t kSynthScratchBytes = (size_t)16 << 20;
+
+static size_t synth_group_frames(const hzsdr_synthesizer *s) { return kSynthScratchBytes / (s->m * sizeof(float2)); }
+
+// one term of the overlap-add: THE expression every path evaluates (one fused multiply-add per component)
+__device__ __forceinline__ float2 synth_term(float2 acc, float g, float2 w) { return make_float2(__fmaf_rn(g, w.x, acc.x), __fmaf_rn(g, w.y, acc.y)); }
+
+// hzsdr_convert's c64 -> dst arithmetic (hz_convert.hip: conv1<C64_*>) on one finished sum
+template <int FMT> struct SynthDst;
+template <> struct SynthDst<HZSDR_FMT_C64> {
+    using t = float2;
+    static __device__ __forceinline__ t cvt(float2 v) { return v; }
+};
+template <> struct SynthDst<HZSDR_FMT_U8> {
+    using t = uint16_t;
+    static __device__ __forceinline__ t cvt(float2 v) { return (uint16_t)(f32_to_u8(v.x) | (f32_to_u8(v.y) << 8)); }
+};
+template <> struct SynthDst<HZSDR_FMT_I8> {
+    using t = uint16_t;
+    static __device__ __forceinline__ t cvt(float2 v) { return (uint16_t)(f32_to_i8(v.x) | (f32_to_i8(v.y) << 8)); }
+};
+template <> struct SynthDst<HZSDR_FMT_I16> {
+    using t = uint32_t;
+    static __device__ __forceinline__ t cvt(float2 v) { return f32_to_i16(v.x) | (f32_to_i16(v.y) << 16); }
+};
+
+// w[f][.] = M * IDFT_M(Y[f][.]) for the F frames of a group.  Frame-major: in[f * M + pos(k)]; channel-major:
+// in[pos(k) * stride + f].
+template <int M, int LAYOUT>
+__global__ __launch_bounds__(fv::block(M)) void synthesizer_frames_kernel(const float2 *__restrict__ in, size_t stride, size_t F, const cf4 *tab,
+                                                                          float2 *__restrict__ w, int neg_first) {
+    constexpr int TPT = fv::tpt(M), XPB = fv::xpb(M), R0 = fv::first_radix(M);
+    constexpr bool WAVE = TPT <= 64;
+    const int sub = XPB == 1 ? 0 : threadIdx.x / TPT, lane = XPB == 1 ? (int)threadIdx.x : threadIdx.x % TPT;
+    cf *lds = fv_lds() + sub * fv::lds_elems(M);
+    const size_t f = chan_group(blockIdx.x, gridDim.x) * XPB + sub;
+    const bool live = f < F;
+    const size_t fr = live ? f : F - 1;  // (dead transforms run the last frame and drop it)
+    cf v[16];
+    // frequency side = the radix-16 edge layout of the backward transform's first pass
+    if constexpr (LAYOUT == HZSDR_CHANNELIZER_FRAME_MAJOR) {
+        const float2 *x = in + fr * M;
+#pragma unroll
+        for (int q = 0; q < 16; q++) v[q] = fv::from2(x[chan_pos(fv::edge_off<M, 16>(q) + lane, M, neg_first)]);
+    } else {
+        const float2 *x = in + fr;
+#pragma unroll
+        for (int q = 0; q < 16; q++) v[q] = fv::from2(x[(size_t)chan_pos(fv::edge_off<M, 16>(q) + lane, M, neg_first) * stride]);
+    }
+    // one wave per transform up to M = 1024 (the wave orders its own LDS operations), a workgroup beyond
+    fv::backward<M, WAVE>(v, lds, tab, lane);
+    if (!live) return;
+    // time side = the edge layout of the last pass's radix
+    float2 *o = w + f * M + lane;
+#pragma unroll
+    for (int q = 0; q < 16; q++) o[fv::edge_off<M, R0>(q)] = fv::to2(v[q]);
+}
+
+// The overlap-add of one group.  Positions u count from the group's first frame; the stream position is T0 + u with
+// T0 mod M = rot.  Frame j of the group covers [jD, jD + L).
+struct SynthOla {
+    const float2 *w;        // F rows of M
+    const float *taps;      // L
+    const float2 *hold_in;  // `held` partial sums at u = 0 ..
+    float2 *hold_out;       // receives the sums at u = n_out ..
+    unsigned F, D, L, mask;  // mask = M - 1
+    unsigned rot, held, n_out, total;
+};
+
+// One lane per position u < total: acc = the old partial sum where one exists, else +0; then the group's frames that
+// cover u, j ascending.  Across the lanes of a wave the loads of w_j[(rot + u) mod M] and g[u - jD] are contiguous but
+// for the wrap.  The first n_out sums are finished: converted and stored; the rest are the new held state.
+// (F = 0, n_out = total = held: the flush.)
+template <int FMT>
+__global__ __launch_bounds__(kThreads) void synthesizer_ola_kernel(SynthOla a, typename SynthDst<FMT>::t *__restrict__ out) {
+    const unsigned u = blockIdx.x * kThreads + threadIdx.x;
+    if (u >= a.total) return;
+    float2 acc = u < a.held ? a.hold_in[u] : make_float2(0.f, 0.f);
+    if (a.F) {
+        const unsigned j_lo = u >= a.L ? (u - a.L) / a.D + 1 : 0, j_hi = min(a.F - 1, u / a.D);
+        const unsigned n = j_hi - j_lo + 1;  // (at least one: D <= L leaves no gap)
+        const size_t M = (size_t)a.mask + 1;
+        const float2 *wp = a.w + (size_t)j_lo * M + ((a.rot + u) & a.mask);
+        const float *gp = a.taps + (u - j_lo * a.D);
+        unsigned k = 0;
+#pragma unroll 1
+        for (; k + 4 <= n; k += 4) {
+            float2 ww[4];
+            float gg[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                ww[i] = wp[(size_t)i * M];
+                gg[i] = *(gp - (size_t)i * a.D);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc = synth_term(acc, gg[i], ww[i]);
+            wp += 4 * M;
+            gp -= (size_t)4 * a.D;
+            // (the trip's eight loads in flight before the first use: channelizer_frames_kernel's note applies)
+            __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 64, 0);
+        }
+#pragma unroll 1
+        for (; k < n; k++) {
+            acc = synth_term(acc, *gp, *wp);
+            wp += M;
+            gp -= a.D;
+        }
+    }
+    if (u < a.n_out)
+        out[u] = SynthDst<FMT>::cvt(acc);
+    else
+        a.hold_out[u - a.n_out] = acc;
+}
+
+template <int M>
+static int synth_frames_m(hzsdr_synthesizer *s, const float2 *in, size_t stride, size_t F) {
+    constexpr int XPB = fv::xpb(M);
+    const dim3 grid((unsigned)((F + XPB - 1) / XPB)), block(fv::block(M));
+    const size_t lds = (size_t)XPB * fv::lds_elems(M) * sizeof(cf);
+    const int neg = s->order == HZSDR_ORDER_NEGATIVE_FIRST;
+    if (s->layout == HZSDR_CHANNELIZER_FRAME_MAJOR)
+        HZ_TRY(launch_fv(synthesizer_frames_kernel<M, HZSDR_CHANNELIZER_FRAME_MAJOR>, grid, block, lds, s->ctx->stream, in, stride, F, s->tabs.bwd, s->w, neg));
+    else
+        HZ_TRY(launch_fv(synthesizer_frames_kernel<M, HZSDR_CHANNELIZER_CHANNEL_MAJOR>, grid, block, lds, s->ctx->stream, in, stride, F, s->tabs.bwd, s->w, neg));
+    HZ_HIP(s->ctx, hipGetLastError());
+    return HZSDR_OK;
+}
+
+static int synth_frames(hzsdr_synthesizer *s, const float2 *in, size_t stride, size_t F) {
+    switch (s->m) {
+    case 256: return synth_frames_m<256>(s, in, stride, F);
+    case 512: return synth_frames_m<512>(s, in, stride, F);
+    case 1024: return synth_frames_m<1024>(s, in, stride, F);
+    case 2048: return synth_frames_m<2048>(s, in, stride, F);
+    case 4096: return synth_frames_m<4096>(s, in, stride, F);
+    case 8192: return synth_frames_m<8192>(s, in, stride, F);
+    default: return HZSDR_ERR_INVALID_ARGUMENT;
+    }
+}
+
+static int synth_ola(hzsdr_synthesizer *s, const SynthOla &a, void *out) {
+    const dim3 grid((a.total + kThreads - 1) / kThreads), block(kThreads);
+    switch (s->fmt) {
+    case HZSDR_FMT_C64: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_C64>, grid, block, 0, s->ctx->stream, a, (float2 *)out); break;
+    case HZSDR_FMT_U8: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_U8>, grid, block, 0, s->ctx->stream, a, (uint16_t *)out); break;
+    case HZSDR_FMT_I8: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_I8>, grid, block, 0, s->ctx->stream, a, (uint16_t *)out); break;
+    default: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_I16>, grid, block, 0, s->ctx->stream, a, (uint32_t *)out); break;
+    }
+    HZ_HIP(s->ctx, hipGetLastError());
+    return HZSDR_OK;
+}
+
+// room in the scratch for the largest group of a push of n frames (grow-only, before anything is launched)
+static int synth_scratch(hzsdr_synthesizer *s, size_t n) {
+    const size_t want = std::min(n, synth_group_frames(s));
+    if (want <= s->wcap) return HZSDR_OK;
+    if (s->w) {
+        HZ_HIP(s->ctx, hipStreamSynchronize(s->ctx->stream));  // (enqueued work may still read the old one)
+        HZ_HIP(s->ctx, hipFree(s->w));
+        s->w = nullptr;
+        s->wcap = 0;
+    }
+    HZ_HIP(s->ctx, hipMalloc((void **)&s->w, want * s->m * sizeof(float2)));
+    s->wcap = want;
+    return HZSDR_OK;
+}
+
+}  // namespace hz
+
+extern "C" {
+
+int hzsdr_synthesizer_create(hzsdr_ctx *ctx, int dst_format, size_t channels, const float *taps, size_t n_taps, size_t hop,
+                             int order, int layout, hzsdr_synthesizer **out) {
+    using namespace hz;
+    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    const size_t m = channels;
+    if (format_size(dst_format) == 0) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "synthesizer: unknown destination format");
+    if (m < 256 || m > 8192 || (m & (m - 1)) != 0)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: the channel count is a power of two, 256 ... 8192");
+    if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null taps");
+    if (n_taps == 0 || n_taps % m != 0 || n_taps > 32 * m)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: the prototype has P * channels taps, 1 <= P <= 32");
+    if (hop == 0 || hop > m) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: the hop is 1 ... channels");
+    if (order != HZSDR_ORDER_ZERO_FIRST && order != HZSDR_ORDER_NEGATIVE_FIRST)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: unknown fft order");
+    if (layout != HZSDR_CHANNELIZER_FRAME_MAJOR && layout != HZSDR_CHANNELIZER_CHANNEL_MAJOR)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: unknown input layout");
+    HZ_TRY(enter(ctx));
+    hzsdr_synthesizer *s = new hzsdr_synthesizer{ctx, dst_format, m, n_taps, hop, order, layout};
+    auto undo = [&](int rc) {
+        hzsdr_synthesizer_free(s);
+        return rc;
+    };
+    int rc = get_fv_tables(ctx, m, &s->tabs);  // (plan-time: the transform's tables, not inside the first push)
+    if (rc != HZSDR_OK) return undo(rc);
+    hipError_t e = hipMalloc((void **)&s->taps, n_taps * sizeof(float));
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&s->hold[i], n_taps * sizeof(float2));
+    if (e == hipSuccess) e = hipMemcpyAsync(s->taps, taps, n_taps * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (taps is the caller's: free to go when create returns)
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "synthesizer_create", __FILE__, __LINE__));
+    *out = s;
+    return HZSDR_OK;
+}
+
+int hzsdr_synthesizer_push(hzsdr_synthesizer *s, const void *frames, size_t n_frames, size_t in_stride, void *out, size_t out_cap,
+                           size_t *samples_written) {
+    using namespace hz;
+    if (samples_written) *samples_written = 0;
+    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
+    hzsdr_ctx *ctx = s->ctx;
+    const bool chmajor = s->layout == HZSDR_CHANNELIZER_CHANNEL_MAJOR;
+    const size_t M = s->m, D = s->hop, L = s->ntaps, n_out = n_frames * D;
+    if (n_frames && !frames) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null input");
+    if (chmajor && in_stride < n_frames) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: in_stride is below the frames of the push");
+    if (out_cap < n_out) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "synthesizer: output buffer too small for the samples of the push");
+    if (n_out && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null output");
+    HZ_TRY(enter(ctx));
+    if (n_frames == 0) return HZSDR_OK;
+    HZ_TRY(synth_scratch(s, n_frames));
+    const size_t fs = (size_t)format_size(s->fmt);
+    Stage st(ctx);
+    const void *din;
+    void *dout;
+    size_t dstride = in_stride;
+    if (!chmajor || in_stride == n_frames) {
+        HZ_TRY(st.in(0, frames, n_frames * M * sizeof(float2), &din));
+    } else if (!st.host() || st.pinned_by_us(frames, ((M - 1) * in_stride + n_frames) * sizeof(float2))) {
+        din = frames;
+    } else {  // a HOST context's channel-major rows with a pitch: dense on the device, copied in row by row
+        HZ_TRY(ensure_slot(ctx, 0, M * n_frames * sizeof(float2)));
+        HZ_HIP(ctx, hipMemcpy2DAsync(ctx->slots[0].ptr, n_frames * sizeof(float2), frames, in_stride * sizeof(float2),
+                                     n_frames * sizeof(float2), M, hipMemcpyHostToDevice, ctx->stream));
+        din = ctx->slots[0].ptr;
+        dstride = n_frames;
+    }
+    HZ_TRY(st.out(1, out, n_out * fs, &dout));
+    const size_t group = synth_group_frames(s);
+    for (size_t f0 = 0; f0 < n_frames; f0 += group) {
+        const size_t F = std::min(group, n_frames - f0);
+        HZ_TRY(synth_frames(s, (const float2 *)din + (chmajor ? f0 : f0 * M), dstride, F));
+        const SynthOla a{s->w, s->taps, s->hold[s->hcur], s->hold[s->hcur ^ 1], (unsigned)F, (unsigned)D, (unsigned)L, (unsigned)(M - 1),
+                         (unsigned)s->rot, (unsigned)s->held, (unsigned)(F * D), (unsigned)(F * D + (L - D))};
+        HZ_TRY(synth_ola(s, a, (char *)dout + f0 * D * fs));
+        s->hcur ^= 1;
+        s->held = L - D;
+        s->rot = (s->rot + (F & (M - 1)) * D) & (M - 1);  // (running value mod M: no product of stream length)
+        s->frame += F;
+    }
+    HZ_TRY(st.finish());
+    if (samples_written) *samples_written = n_out;
+    return HZSDR_OK;
+}
+
+int hzsdr_synthesizer_flush(hzsdr_synthesizer *s, void *out, size_t out_cap, size_t *samples_written) {
+    using namespace hz;
+    if (samples_written) *samples_written = 0;
+    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
+    hzsdr_ctx *ctx = s->ctx;
+    const size_t n = s->held;
+    if (out_cap < n) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "synthesizer: output buffer too small for the held samples");
+    if (n && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null output");
+    HZ_TRY(enter(ctx));
+    if (n) {
+        Stage st(ctx);
+        void *dout;
+        HZ_TRY(st.out(1, out, n * (size_t)format_size(s->fmt), &dout));
+        const SynthOla a{nullptr, s->taps, s->hold[s->hcur], nullptr, 0u, (unsigned)s->hop, (unsigned)s->ntaps, (unsigned)(s->m - 1),
+                         0u, (unsigned)n, (unsigned)n, (unsigned)n};
+        HZ_TRY(synth_ola(s, a, dout));
+        HZ_TRY(st.finish());
+    }
+    s->held = s->rot = 0;
+    s->frame = 0;
+    if (samples_written) *samples_written = n;
+    return HZSDR_OK;
+}
+
+int hzsdr_synthesizer_pending(const hzsdr_synthesizer *s, size_t *samples_held, uint64_t *frame_index) {
+    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
+    if (samples_held) *samples_held = s->held;
+    if (frame_index) *frame_index = s->frame;
+    return HZSDR_OK;
+}
+
+int hzsdr_synthesizer_group_frames(const hzsdr_synthesizer *s, size_t *frames) {
+    if (!s || !frames) return HZSDR_ERR_INVALID_ARGUMENT;
+    *frames = hz::synth_group_frames(s);
+    return HZSDR_OK;
+}
+
+int hzsdr_synthesizer_reset(hzsdr_synthesizer *s) {
+    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
+    // (the held sums are only read behind a later push's own writes: nothing to clear, nothing to wait for)
+    s->held = s->rot = 0;
+    s->frame = 0;
+    return HZSDR_OK;
+}
+
+int hzsdr_synthesizer_free(hzsdr_synthesizer *s) {
+    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    for (void *p : {(void *)s->taps, (void *)s->hold[0], (void *)s->hold[1], (void *)s->w})
+        if (p) (void)hipFree(p);
+    delete s;
+    return HZSDR_OK;
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@
 #include "../../include/hzsdr.h"
 #include "../../include/hzsdr_channelizer.h"
 #include "../../include/hzsdr_spectrum.h"
+#include "../../include/hzsdr_synthesizer.h"
 
 namespace hzsdr {
 
@@ -965,6 +966,58 @@ private:
     const Context &x_;
     size_t m_;
     hzsdr_channelizer *c_ = nullptr;
+};
+// The polyphase synthesis bank (include/hzsdr_synthesizer.h), the channelizer's adjoint: Push consumes frames of
+// `channels` complex64 values, frames x channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames
+// (HZSDR_CHANNELIZER_CHANNEL_MAJOR, the pitch being the frames of the push), in the synthesizer's fft.Order
+// (fft/result.go:34-47), and returns the frames * hop samples they complete in the destination format; Flush returns
+// the stream's tail and starts over.
+class Synthesizer {
+public:
+    Synthesizer(const Context &x, int dst_format, size_t channels, const std::vector<float> &taps, size_t hop,
+                int order = HZSDR_ORDER_NEGATIVE_FIRST, int layout = HZSDR_CHANNELIZER_FRAME_MAJOR)
+        : x_(x), fmt_(dst_format), m_(channels), hop_(hop) {
+        check(x_.raw(), hzsdr_synthesizer_create(x_.raw(), dst_format, channels, taps.empty() ? nullptr : taps.data(), taps.size(), hop,
+                                                 order, layout, &s_));
+    }
+    ~Synthesizer() { if (s_) hzsdr_synthesizer_free(s_); }
+    Synthesizer(const Synthesizer &) = delete;
+    Synthesizer &operator=(const Synthesizer &) = delete;
+    // (a HOST context's buffers: the samples come back in a Buffer of the destination format)
+    Buffer Push(const std::vector<std::complex<float>> &frames) {
+        const size_t f = frames.size() / m_;
+        Buffer out(fmt_, f * hop_);
+        size_t n = 0;
+        check(x_.raw(), hzsdr_synthesizer_push(s_, frames.empty() ? nullptr : frames.data(), f, f, out.view.length ? out.view.data : nullptr,
+                                               out.view.length, &n));
+        return out;
+    }
+    Buffer Flush() {
+        Buffer out(fmt_, Pending().first);
+        size_t n = 0;
+        check(x_.raw(), hzsdr_synthesizer_flush(s_, out.view.length ? out.view.data : nullptr, out.view.length, &n));
+        return out;
+    }
+    // -> (partial sums held behind the samples written, index of the next frame)
+    std::pair<size_t, uint64_t> Pending() const {
+        size_t h = 0;
+        uint64_t j = 0;
+        check(x_.raw(), hzsdr_synthesizer_pending(s_, &h, &j));
+        return {h, j};
+    }
+    size_t GroupFrames() const {
+        size_t f = 0;
+        check(x_.raw(), hzsdr_synthesizer_group_frames(s_, &f));
+        return f;
+    }
+    void Reset() { check(x_.raw(), hzsdr_synthesizer_reset(s_)); }
+    size_t Channels() const { return m_; }
+
+private:
+    const Context &x_;
+    int fmt_;
+    size_t m_, hop_;
+    hzsdr_synthesizer *s_ = nullptr;
 };
 }  // namespace fft
 }  // namespace hzsdr

@@ -856,3 +856,18 @@ def channelizer_frames(r, channelizer, block=READER_BLOCK):
         frames = channelizer.push(buf[:k])
         if frames.shape[1 if channelizer.channel_major else 0]:
             yield frames, channelizer.channel_rate(r.sample_rate()), channelizer.order
+
+
+# ---- channels back into one stream (include/hzsdr_synthesizer.h) -------------------------------
+
+def synthesizer_samples(frames_iterable, synthesizer):
+    """Push every block of frames of `frames_iterable` (complex64, in the synthesizer's layout) through `synthesizer`
+    (a synthesizer.Synthesizer) and yield each push's samples, then the flush: concatenated, the whole stream,
+    (frames - 1) * hop + len(taps) samples, ready for a Writer of the synthesizer's format."""
+    for frames in frames_iterable:
+        samples = synthesizer.push(frames)
+        if samples.shape[0]:
+            yield samples
+    tail = synthesizer.flush()
+    if tail.shape[0]:
+        yield tail
