@@ -427,6 +427,13 @@ class Context:
         from .synthesizer import NegativeFirst, Synthesizer
         return Synthesizer(self, dst_fmt, channels, taps, hop, NegativeFirst if order is None else order, layout)
 
+    def resampler(self, src_fmt, up, down, taps=None, streams=1):
+        """The polyphase rational resampler (include/hzsdr_resampler.h, resampler.Resampler): `streams` rows of
+        src_fmt samples at up/down times their rate, complex64, scipy.signal.upfirdn's definition.  `taps`: float32
+        values (default resampler.resampler_taps(up, down))."""
+        from .resampler import Resampler
+        return Resampler(self, src_fmt, up, down, taps, streams)
+
 
 class LookupTable:
     """sdr.LookupTable (iq_lookup_table.go:36-50)."""
@@ -828,6 +835,8 @@ from ._capi import (ORDER_NEGATIVE_FIRST, ORDER_ZERO_FIRST, SPECTRUM_FORM_AUTO, 
 from ._capi import CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR  # noqa: E402
 from .channelizer import Channelizer, channelizer_taps  # noqa: E402
 from .synthesizer import Synthesizer, wola_taps  # noqa: E402
+from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM  # noqa: E402
+from .resampler import Resampler, resampler_taps  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

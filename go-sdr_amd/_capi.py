@@ -215,8 +215,21 @@ SYNTHESIZER_SIGNATURES = {
     "hzsdr_synthesizer_free": (i32, [vp]),
 }
 
+# name -> (restype, argtypes); every symbol include/hzsdr_resampler.h declares
+RESAMPLER_SIGNATURES = {
+    "hzsdr_resampler_create": (i32, [vp, i32, sz, sz, C.POINTER(f32), sz, sz, pvp]),
+    "hzsdr_resampler_push": (i32, [vp, vp, sz, sz, vp, sz, sz, psz]),
+    "hzsdr_resampler_flush": (i32, [vp, vp, sz, sz, psz]),
+    "hzsdr_resampler_outputs_for": (i32, [vp, sz, psz]),
+    "hzsdr_resampler_pending": (i32, [vp, C.POINTER(u64), C.POINTER(u64), psz]),
+    "hzsdr_resampler_plan": (i32, [vp, psz, C.POINTER(i32)]),
+    "hzsdr_resampler_reset": (i32, [vp]),
+    "hzsdr_resampler_free": (i32, [vp]),
+}
+RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM = 1, 2, 4
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
-                             *SYNTHESIZER_SIGNATURES.items()):
+                             *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -20,11 +20,13 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
 #include "../../include/hzsdr.h"
 #include "../../include/hzsdr_channelizer.h"
+#include "../../include/hzsdr_resampler.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1020,4 +1022,62 @@ private:
     hzsdr_synthesizer *s_ = nullptr;
 };
 }  // namespace fft
+
+namespace stream {
+// The polyphase rational resampler (include/hzsdr_resampler.h): `streams` rows of src_format samples at up/down times
+// their rate, complex64, scipy.signal.upfirdn's definition.  Push consumes `n` samples of every row (row s starts
+// s * in_stride samples into `in`; dense rows when in_stride is 0) and returns the outputs they complete, dense rows of
+// the returned count; Flush returns the outputs that still depend on samples pushed and starts over.
+class Resampler {
+public:
+    Resampler(const Context &x, int src_format, size_t up, size_t down, const std::vector<float> &taps, size_t streams = 1)
+        : x_(x), streams_(streams) {
+        check(x_.raw(), hzsdr_resampler_create(x_.raw(), src_format, up, down, taps.empty() ? nullptr : taps.data(), taps.size(), streams, &r_));
+    }
+    ~Resampler() { if (r_) hzsdr_resampler_free(r_); }
+    Resampler(const Resampler &) = delete;
+    Resampler &operator=(const Resampler &) = delete;
+    // (a HOST context's buffers: view.length is streams * count, row s at s * count)
+    Buffer Push(const void *in, size_t n, size_t in_stride = 0) {
+        const size_t count = OutputsFor(n);
+        Buffer out(HZSDR_FMT_C64, streams_ * count);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_resampler_push(r_, n ? in : nullptr, n, in_stride ? in_stride : n, count ? out.view.data : nullptr, count, count, &w));
+        return out;
+    }
+    Buffer Flush() {
+        const size_t count = std::get<2>(Pending());
+        Buffer out(HZSDR_FMT_C64, streams_ * count);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_resampler_flush(r_, count ? out.view.data : nullptr, count, count, &w));
+        return out;
+    }
+    size_t OutputsFor(size_t n) const {
+        size_t c = 0;
+        check(x_.raw(), hzsdr_resampler_outputs_for(r_, n, &c));
+        return c;
+    }
+    // -> (samples consumed, index of the next output, outputs a flush would write now), per stream
+    std::tuple<uint64_t, uint64_t, size_t> Pending() const {
+        uint64_t n = 0, m = 0;
+        size_t f = 0;
+        check(x_.raw(), hzsdr_resampler_pending(r_, &n, &m, &f));
+        return {n, m, f};
+    }
+    // -> (outputs per workgroup, HZSDR_RESAMPLER_FORM_*)
+    std::pair<size_t, int> Plan() const {
+        size_t t = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_resampler_plan(r_, &t, &f));
+        return {t, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_resampler_reset(r_)); }
+    size_t Streams() const { return streams_; }
+
+private:
+    const Context &x_;
+    size_t streams_;
+    hzsdr_resampler *r_ = nullptr;
+};
+}  // namespace stream
 }  // namespace hzsdr

@@ -871,3 +871,54 @@ def synthesizer_samples(frames_iterable, synthesizer):
     tail = synthesizer.flush()
     if tail.shape[0]:
         yield tail
+
+
+# ---- a Reader at another rate (include/hzsdr_resampler.h) --------------------------------------
+
+def resampler_samples(r, resampler, block=READER_BLOCK):
+    """Read `r` to its end in blocks of `block` samples, push them through `resampler` (a one-stream
+    resampler.Resampler of the reader's format on a HOST context) and yield each push's outputs, then the flush:
+    concatenated, scipy.signal.upfirdn of the whole stream, complex64 at r.sample_rate() * up / down."""
+    if resampler.src_fmt != r.sample_format():
+        raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+    buf = make_samples(r.sample_format(), block)
+    while True:
+        try:
+            k = r.read(buf)
+        except EOF:
+            break
+        out = resampler.push(buf[:k])
+        if out.shape[0]:
+            yield out
+    tail = resampler.flush()
+    if tail.shape[0]:
+        yield tail
+
+
+class ResampleReader(Reader):
+    """A Reader of complex64 at inp.sample_rate() * up / down: `inp` read in blocks of `block` samples through
+    `resampler` (resampler_samples), the flush behind the input's last sample included."""
+
+    def __init__(self, inp, resampler, block=READER_BLOCK):
+        self.inp, self.resampler = inp, resampler
+        self.blocks = resampler_samples(inp, resampler, block)
+        self.cur, self.off = None, 0
+
+    def read(self, samples):
+        if fmt_of(samples) != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        while self.cur is None or self.off == self.cur.shape[0]:
+            try:
+                self.cur, self.off = next(self.blocks), 0
+            except StopIteration:
+                raise EOF()
+        n = min(length(samples), self.cur.shape[0] - self.off)
+        samples[:n] = self.cur[self.off:self.off + n]
+        self.off += n
+        return n
+
+    def sample_format(self):
+        return FMT_C64
+
+    def sample_rate(self):
+        return self.resampler.sample_rate(self.inp.sample_rate())
