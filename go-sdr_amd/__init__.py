@@ -835,7 +835,7 @@ from ._capi import (ORDER_NEGATIVE_FIRST, ORDER_ZERO_FIRST, SPECTRUM_FORM_AUTO, 
 from ._capi import CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR  # noqa: E402
 from .channelizer import Channelizer, channelizer_taps  # noqa: E402
 from .synthesizer import Synthesizer, wola_taps  # noqa: E402
-from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM  # noqa: E402
+from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM, RESAMPLER_FORM_WINDOW_PADDED  # noqa: E402
 from .resampler import Resampler, resampler_taps  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 

@@ -226,7 +226,7 @@ RESAMPLER_SIGNATURES = {
     "hzsdr_resampler_reset": (i32, [vp]),
     "hzsdr_resampler_free": (i32, [vp]),
 }
-RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM = 1, 2, 4
+RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM, RESAMPLER_FORM_WINDOW_PADDED = 1, 2, 4, 8
 
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items()):

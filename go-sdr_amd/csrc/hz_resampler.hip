@@ -385,7 +385,7 @@ int hzsdr_resampler_plan(const hzsdr_resampler *r, size_t *tile_outputs, int *fo
     if (tile_outputs) *tile_outputs = r->g.T;
     if (form)
         *form = (r->g.direct ? HZSDR_RESAMPLER_FORM_DIRECT : 0) | (r->g.taps_global ? HZSDR_RESAMPLER_FORM_TAPS_GLOBAL : 0) |
-                (r->g.taps_uniform ? HZSDR_RESAMPLER_FORM_TAPS_UNIFORM : 0);
+                (r->g.taps_uniform ? HZSDR_RESAMPLER_FORM_TAPS_UNIFORM : 0) | (r->g.pad ? HZSDR_RESAMPLER_FORM_WINDOW_PADDED : 0);
     return HZSDR_OK;
 }
 

@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _is_torch, ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib, MEM_HOST  # noqa: F401
-from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM
+from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM, RESAMPLER_FORM_WINDOW_PADDED
 
 _NP_IN = {FMT_C64: (np.complex64, 8), FMT_U8: (np.uint8, 2), FMT_I8: (np.int8, 2), FMT_I16: (np.int16, 4)}
 
@@ -66,8 +66,9 @@ class Resampler:
 
     def plan(self):
         """(outputs per workgroup, kernel form): the form is a sum of RESAMPLER_FORM_DIRECT (no input window in LDS),
-        RESAMPLER_FORM_TAPS_GLOBAL (the polyphase table is read from memory, not LDS) and RESAMPLER_FORM_TAPS_UNIFORM
-        (U divides D: the one row in use is read as scalars common to a wave)."""
+        RESAMPLER_FORM_TAPS_GLOBAL (the polyphase table is read from memory, not LDS), RESAMPLER_FORM_TAPS_UNIFORM
+        (U divides D: the one row in use is read as scalars common to a wave) and RESAMPLER_FORM_WINDOW_PADDED (the
+        window in LDS has one empty slot behind every 32 samples)."""
         t, f = C.c_size_t(0), C.c_int32(0)
         self.ctx._ck(lib.hzsdr_resampler_plan(self._h, C.byref(t), C.byref(f)))
         return t.value, f.value
@@ -181,4 +182,4 @@ class Resampler:
 
 
 __all__ = ["Resampler", "resampler_taps", "RESAMPLER_FORM_DIRECT", "RESAMPLER_FORM_TAPS_GLOBAL",
-           "RESAMPLER_FORM_TAPS_UNIFORM"]
+           "RESAMPLER_FORM_TAPS_UNIFORM", "RESAMPLER_FORM_WINDOW_PADDED"]

@@ -65,10 +65,13 @@ typedef struct hzsdr_resampler hzsdr_resampler;
  * Without _TAPS_GLOBAL the polyphase table is in LDS; with it the table is
  * read from memory (it is past the LDS budget).  _TAPS_UNIFORM: U divides D,
  * every output has phase 0, and the table's one row is read as scalars common
- * to a wave (neither from LDS nor lane by lane). */
+ * to a wave (neither from LDS nor lane by lane).  _WINDOW_PADDED: the window
+ * in LDS has one empty slot behind every 32 samples (D/U is 2 or more; never
+ * together with _DIRECT). */
 #define HZSDR_RESAMPLER_FORM_DIRECT 1
 #define HZSDR_RESAMPLER_FORM_TAPS_GLOBAL 2
 #define HZSDR_RESAMPLER_FORM_TAPS_UNIFORM 4
+#define HZSDR_RESAMPLER_FORM_WINDOW_PADDED 8
 
 /* A resampler by up/down over `streams` rows of src_format samples
  * (iq.go:110-126) with the filter `taps` (n_taps float32 host values, free to

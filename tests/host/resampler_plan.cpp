@@ -8,6 +8,9 @@
 //   P n_in ok count n m phi rel held flush a push: resampler_step's result and the flush count behind it
 // Beside them, with no expectation needed: every output of a tile gets the (i, phi) that a 64-bit division gives from
 // the kernel's lane arithmetic (reciprocal, then add-and-carry), and the reciprocal is exact on its whole range.
+// A search of every (U, D, Q) a create accepts for the largest LDS request among the forms with a window prints
+// "largest lds: U D Q window bytes" (the loops nest U, Q, D: the first shape in that order to reach the maximum), and
+// the forms of the shapes named by "G U D Q" lines print as "form: U D Q T direct global uniform pad bytes".
 // Prints "resampler_plan ok".
 #include <cinttypes>
 #include <cstdio>
@@ -79,6 +82,20 @@ int main(int argc, char **argv) {
                 CHECK(g.taps_global == ((uint64_t)U * g.pitch > kTableMax), "U=%u Q=%u", U, Q);
             }
     }
+    // the largest LDS request of a form with a window, over every shape a create accepts (Q taps per phase need at
+    // least (Q - 1) U + 1 taps in all): the GPU tests run the shape this prints
+    {
+        Geom best{};
+        uint32_t bu = 0, bd = 0, bq = 0;
+        for (uint32_t U = 1; U <= kMaxRate; U++)
+            for (uint32_t Q = 1; Q <= kMaxPhaseTaps && (uint64_t)(Q - 1) * U + 1 <= kMaxTaps; Q++)
+                for (uint32_t D = 1; D <= kMaxRate; D++) {
+                    const Geom g = resampler_geom(U, D, Q);
+                    if (!g.direct && g.lds_bytes > best.lds_bytes) best = g, bu = U, bd = D, bq = Q;
+                }
+        CHECK(best.lds_bytes <= (size_t)(kWindowMax + kWindowMax / 32 + 1) * 8 + (size_t)kTableMax * 4, "lds %zu", best.lds_bytes);
+        printf("largest lds: %u %u %u %u %zu\n", bu, bd, bq, best.window, best.lds_bytes);
+    }
     if (argc < 2) {
         printf("usage: resampler_plan CASES\n");
         return 2;
@@ -96,6 +113,11 @@ int main(int argc, char **argv) {
             CHECK(sscanf(line + 1, "%llu %llu %llu %llu %llu %llu %llu %llu", a, a + 1, a + 2, a + 3, a + 4, a + 5, a + 6, a + 7) == 8, "parse");
             U = (uint32_t)a[0], D = (uint32_t)a[1], Q = (uint32_t)a[2], L = (uint32_t)a[3];
             s.n = a[4], s.m = a[5], s.phi = (uint32_t)a[6], s.rel = (uint32_t)a[7];
+        } else if (line[0] == 'G') {
+            CHECK(sscanf(line + 1, "%llu %llu %llu", a, a + 1, a + 2) == 3, "parse");
+            const Geom g = resampler_geom((uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2]);
+            printf("form: %llu %llu %llu %u %d %d %d %d %zu\n", a[0], a[1], a[2], g.T, (int)g.direct, (int)g.taps_global, (int)g.taps_uniform,
+                   (int)g.pad, g.lds_bytes);
         } else if (line[0] == 'T') {
             CHECK(sscanf(line + 1, "%llu %llu %llu %llu %llu %llu", a, a + 1, a + 2, a + 3, a + 4, a + 5) == 6, "parse");
             const Tile t = resampler_tile(s.rel, s.phi, U, D, Q, (uint32_t)a[0], a[1]);

@@ -1,6 +1,15 @@
 """The polyphase channelizer (include/hzsdr_channelizer.h) on the GPU: frames against the float64 restatements of
-tests/channelizer_ref.py within B(M, P) = 3e-7 log2 M + 6e-8 (P + 2), per frame and per channel; and bit for bit
-across pushes, memory spaces, layouts, orders and runs."""
+tests/channelizer_ref.py within B(M, P) = 3e-7 log2 M + 6e-8 (P + 2), per frame and per channel, at all six sizes,
+through both fold paths and up to P = 32; every tap read out on its own by impulse trains, per bin against the
+single-precision yardstick of tests/util.py (tests/readout.py); and bit for bit across pushes, memory spaces, layouts,
+orders and runs.
+
+test_tap_readout's worst ratio kernel / max(yardstick, 2^-23) over both fold paths, as max_bin | rel_l2 (it prints
+them; K = 4 is asserted; the FFT core alone measures 1.43 | 0.97 on impulses at these sizes, and the fold adds one
+exact product).  Observed on an MI355X:
+
+    not measured
+"""
 import ctypes as C
 import importlib
 import os
@@ -10,8 +19,9 @@ import numpy as np
 import pytest
 
 import channelizer_ref as ref
+import readout as ro
 from conftest import ROOT
-from util import FMT, splitmix64
+from util import FFT_K, FMT, assert_fft_rows_close, splitmix64
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +113,7 @@ STREAMS = 4
 
 
 @pytest.mark.parametrize("fmt", ["u8", "i8", "i16", "c64"])
-@pytest.mark.parametrize("m", [256, 1024, 2048, 8192])
+@pytest.mark.parametrize("m", [256, 512, 1024, 2048, 4096, 8192])
 def test_frames_against_float64(hz, orc, ctx, fmt, m):
     """Every frame within B over its channels, every channel within B over its frames.
 
@@ -113,9 +123,10 @@ def test_frames_against_float64(hz, orc, ctx, fmt, m):
     (B / 1.5e-7)^2 = 600 times below the mean power, which makes an ordinary rounding error exceed B, has probability
     1 / 600 per channel: expected in a thousand channels.  So the columns are taken over the frames of STREAMS = 4
     independent streams (reset between them, which the test thereby covers): with k independent draws the probability
-    is (k / 600)^k / k! = 1e-10 per channel."""
+    is (k / 600)^k / k! = 1e-10 per channel.  The smallest and the largest size also run the longest prototype the
+    bank accepts, P = 32."""
     worst = 0.0
-    for p, d in ((1, m), (3, m), (8, m // 2), (4, 3 * m // 4), (2, 100), (8, 1)):
+    for p, d in ((1, m), (3, m), (8, m // 2), (4, 3 * m // 4), (2, 100), (8, 1)) + (((32, m // 2),) if m in (256, 8192) else ()):
         frames = 2 * xpb(m) + 5  # (several workgroups, the last partly dead)
         n = (frames - 1) * d + p * m + (d - 1) // 2  # (a ragged tail shorter than the hop)
         g = hz.channelizer_taps(m, p)
@@ -132,9 +143,81 @@ def test_frames_against_float64(hz, orc, ctx, fmt, m):
     print(f"{fmt} M={m}: worst GPU / float64 relative L2 {worst:.3e}")
 
 
+@pytest.mark.parametrize("fmt", ["u8", "i8", "i16", "c64"])
+@pytest.mark.parametrize("m", [256, 512, 1024, 2048, 4096, 8192])
+def test_frames_that_start_in_held_samples(hz, orc, ctx, fmt, m):
+    """The kernel's second fold path against the reference itself, not through "cuts equal one push": the stream
+    arrives in two pushes, the first leaving nearly L samples held, so that at least xpb + 2 frames of the second
+    (more than one workgroup's) start in held samples, beside frames that lie wholly in the second push.  Rows and
+    columns as above, the columns over STREAMS streams."""
+    for p, d in ((8, m // 2), (8, 1)):
+        L = p * m
+        first = L + 2 * d + (d - 1) // 2  # three frames, then L - d + (d - 1) // 2 samples held
+        held = first - 3 * d
+        inside = -(-held // d)  # frames of the second push that start in held samples
+        frames = 3 + inside + xpb(m) + 2 if d > 1 else 3 + 2 * xpb(m) + 5
+        n = (frames - 1) * d + L + d // 3
+        assert min(inside, frames - 3) >= xpb(m) + 2 and 0 < held < L
+        g = hz.channelizer_taps(m, p)
+        ch = ctx.channelizer(FMT[fmt], m, g, hop=d, order=hz.ZERO_FIRST)
+        got, want = [], []
+        for stream in range(STREAMS):
+            x = raw(fmt, n, seed=m * 137 + p * 11 + d + 1000 * stream)
+            ch.reset()
+            a = ch.push(dev(x[:first]))
+            assert a.shape[0] == 3 and ch.pending() == (held, 3)
+            b = ch.push(dev(x[first:]))
+            assert b.shape[0] == frames - 3
+            got.append(torch.cat([a, b]).cpu().numpy())
+            want.append(ref.channels_fold(converted(orc, x), g, m, d))
+        ch.close()
+        check_rows_and_columns(np.concatenate(got), np.concatenate(want), m, p, f"{fmt} M={m} P={p} D={d}, {min(inside, frames - 3)} frames from held samples")
+
+
+# ---- 1b. every tap on its own ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", ["c64", "i16"])
+@pytest.mark.parametrize("m,p,d,every", [(256, 2, 129, False), (512, 2, 257, False), (1024, 2, 513, False), (2048, 2, 1025, False),
+                                         (4096, 2, 2049, False), (8192, 2, 4097, False), (256, 2, 1, True)])
+def test_tap_readout(hz, ctx, fmt, m, p, d, every):
+    """One impulse of power-of-two amplitude every L samples: every window of L samples holds exactly one, the fold
+    is ONE exact product, and frame j is the M-point transform of a one-hot vector g[l_j] amp.  Every frame per bin
+    against that transform within K = FFT_K of the single-precision yardstick -- relative to the frame's own tap, so
+    a wrong small tap cannot hide behind large ones.  An odd hop (the rotation differs from frame to frame); once in
+    one push (every frame through the first fold path) and once cut after three frames with L - D / 2 samples held,
+    so that the second push's first frames start in held samples and take the second path: four of them at the hop
+    M / 2 + 1 (fewer than L samples can be held, so no cut gives more at this P and hop), L - 1 of the L + 2 xpb + 2
+    at D = 1, where every one of the 512 taps of M = 256, P = 2 is read, by either path.  (The second path over more
+    than a workgroup's frames at every size is test_frames_that_start_in_held_samples.)  A frame whose tap is
+    exactly 0 is all zero."""
+    L = p * m
+    frames = L + 2 * xpb(m) + 5 if every else 2 * xpb(m) + 5 + (L // d)
+    n = (frames - 1) * d + L + d // 2
+    g = hz.channelizer_taps(m, p)
+    assert np.array_equal(g, ro.bank_taps(m, p))
+    x, conv = ro.channelizer_train(fmt, n, L, first=L - 1 if every else L // 3)
+    ls, u, want = ro.channelizer_onehots(conv, g, m, d, frames)
+    if every:
+        assert set(ls.tolist()) == set(range(L)), "not every tap is read"
+    cut = L + 2 * d + d // 2  # three frames, then frames that start in held samples
+    ch = ctx.channelizer(FMT[fmt], m, g, hop=d, order=hz.ZERO_FIRST)
+    zero = np.flatnonzero(g[ls] == 0)
+    ratio = (0.0, 0.0)
+    for cuts in ([0, n], [0, cut, n]):
+        ch.reset()
+        got = push_all(ch, dev(x), cuts).cpu().numpy()
+        assert got.shape == (frames, m) and not np.isnan(got.view(np.float32)).any()
+        assert not got[zero].any(), "a frame of a zero tap is not all zero"
+        r = assert_fft_rows_close(got, u, what=f"{fmt} M={m} P={p} D={d} cuts {cuts}", k=FFT_K, want64=want)
+        ratio = tuple(max(a, b) for a, b in zip(ratio, r))
+    ch.close()
+    print(f"{fmt} M={m} P={p} D={d}: {frames} frames, {len(set(ls.tolist()))} taps read; kernel / max(yardstick, 2^-23): "
+          f"max_bin {ratio[0]:.2f} rel_l2 {ratio[1]:.2f}")
+
+
 # ---- 2. the definition -----------------------------------------------------------------------------
 
-@pytest.mark.parametrize("m,p,d", [(256, 8, 192), (1024, 4, 1024)])
+@pytest.mark.parametrize("m,p,d", [(256, 8, 192), (1024, 4, 1024), (4096, 2, 3072)])
 def test_against_the_definition(hz, orc, ctx, m, p, d):
     frames = 2 * xpb(m) + 3
     n = (frames - 1) * d + p * m + d // 3

@@ -1,6 +1,8 @@
 """The polyphase rational resampler (include/hzsdr_resampler.h) on the GPU: every block of 256 outputs against the
-float64 restatement of tests/resampler_ref.py within bound(Q) = 6e-8 (Q + 2); bit for bit across cuts, memory spaces,
-stream counts, pitches, sub-slices and runs; behind the GPU channelizer; errors and state; the C and C++ layers."""
+float64 restatement of tests/resampler_ref.py within bound(Q) = 6e-8 (Q + 2), over a list of shapes that takes every
+kernel form the planner can choose and its largest LDS request; every table entry read out on its own by impulse
+trains, EQUAL to the float64 reference (tests/readout.py); bit for bit across cuts, memory spaces, stream counts,
+pitches, sub-slices and runs; behind the GPU channelizer; errors and state; the C and C++ layers."""
 import ctypes as C
 import importlib
 import os
@@ -9,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import readout as ro
 import resampler_ref as ref
 from conftest import ROOT
 from util import FMT, splitmix64
@@ -18,11 +21,17 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 BLOCK = 256
-# (U, D, L) of the accuracy list
-SHAPES = [(3, 2, 24), (2, 3, 50), (160, 147, 1920), (1, 8, 128), (8, 1, 64), (7, 5, 3), (5, 5, 20), (1, 1024, 256), (1024, 1, 2048),
-          (147, 160, 18816)]
-# beside the list: the direct form with the table in memory, which no shape of the list takes
-EXTRA_SHAPES = [(32, 1024, 8192)]
+# (U, D, L) of the accuracy list (tests/readout.py has it, with the planner's tiles, for the CPU tests too)
+SHAPES = [s[:3] for s in ro.RESAMPLER_SHAPES[:-1]]
+# beside the list: the direct form with the table in memory
+EXTRA_SHAPES = [s[:3] for s in ro.RESAMPLER_SHAPES[-1:]]
+TILE = {s[:3]: s[3] for s in ro.RESAMPLER_SHAPES}
+# the shapes whose blocks are checked for i8 and i16 sources too: T1024 pad (lds at the largest request, uniform), T256
+# pad (lds at the largest request, global), both direct forms and one plain shape
+ALL_SOURCES = {(2, 5, 50), (1, 4, 64), (170, 845, 5440), (26, 498, 6110), (40, 300, 8000), (1, 1024, 256), (32, 1024, 8192), (3, 2, 24)}
+# the 11 combinations resampler_geom can reach: (tile, window padded, table form, direct)
+FORMS = {(1024, pad, table, False) for pad in (False, True) for table in ("lds", "global", "uniform")} | {
+    (256, True, table, False) for table in ("lds", "global", "uniform")} | {(256, False, table, True) for table in ("lds", "global")}
 
 
 @pytest.fixture(scope="module")
@@ -44,11 +53,7 @@ def hctx(hz):
     c.close()
 
 
-def taps_of(up, down, ntaps):
-    """a Kaiser-windowed sinc of any length, cutoff 1 / max(U, D), scaled to sum U, float32"""
-    t = np.arange(ntaps, dtype=np.float64) - (ntaps - 1) / 2.0
-    h = np.sinc(t / max(up, down)) * np.kaiser(ntaps, 8.0)
-    return (h * (up / h.sum())).astype(np.float32)
+taps_of = ro.kaiser_taps  # a Kaiser-windowed sinc of any length, cutoff 1 / max(U, D), scaled to sum U, float32
 
 
 def white(fmt, n, seed):
@@ -106,9 +111,13 @@ def run(rs, x, cuts=None, flush=True, check=None):
     return np.concatenate(out, axis=-1)
 
 
-def samples_for(count, up, down):
-    """the fewest samples after which `count` outputs have been written"""
-    return -(-count * down // up)
+samples_for = ro.samples_for  # the fewest samples after which `count` outputs have been written
+
+
+def form_of(hz, tile, form):
+    """the planner's report as (tile, window padded, table form, direct)"""
+    table = "global" if form & hz.RESAMPLER_FORM_TAPS_GLOBAL else "uniform" if form & hz.RESAMPLER_FORM_TAPS_UNIFORM else "lds"
+    return tile, bool(form & hz.RESAMPLER_FORM_WINDOW_PADDED), table, bool(form & hz.RESAMPLER_FORM_DIRECT)
 
 
 def check_blocks(got, want, q, what):
@@ -133,12 +142,14 @@ def check_blocks(got, want, q, what):
 @pytest.mark.parametrize("up,down,ntaps", SHAPES + EXTRA_SHAPES)
 def test_blocks_against_float64(hz, ctx, up, down, ntaps):
     """Streams whose output counts land on T - 1, T, T + 1 and 2 T + 3 (as near as U/D allows; three workgroups),
-    c64 and u8, every block of 256 outputs of pushes and flush against upfirdn_poly of the converted samples."""
+    c64 and u8 (i8 and i16 too for the shapes of ALL_SOURCES), every block of 256 outputs of pushes and flush against
+    upfirdn_poly of the converted samples."""
     h = taps_of(up, down, ntaps)
     q = -(-ntaps // up)
-    for fmt in ("c64", "u8"):
+    for fmt in (("c64", "u8", "i8", "i16") if (up, down, ntaps) in ALL_SOURCES else ("c64", "u8")):
         rs = ctx.resampler(FMT[fmt], up, down, h)
         tile, form = rs.plan()
+        assert tile == TILE[(up, down, ntaps)]
         worst = 0.0
         for target in (tile - 1, tile, tile + 1, 2 * tile + 3):
             n = samples_for(target, up, down)
@@ -158,12 +169,26 @@ def test_blocks_against_float64(hz, ctx, up, down, ntaps):
 
 
 def test_the_list_covers_every_form(hz, ctx):
-    """Over the accuracy list both values of the taps-in-LDS switch and both window forms occur: a changed threshold
-    cannot quietly leave a form untested."""
-    forms = {}
-    for up, down, ntaps in SHAPES:
+    """Over the accuracy list every combination of tile, window padding, table form and direct that the planner can
+    reach occurs, by the planner's own report: a changed threshold cannot quietly leave a form untested.  The i8 and
+    i16 shapes cover a padded four-chain, a padded one-chain and both direct forms."""
+    forms, combos = {}, {}
+    for up, down, ntaps in SHAPES + EXTRA_SHAPES:
         with ctx.resampler(hz.FMT_C64, up, down, taps_of(up, down, ntaps)) as rs:
-            forms[(up, down, ntaps)] = rs.plan()[1]
+            tile, form = rs.plan()
+        combos[(up, down, ntaps)] = form_of(hz, tile, form)
+        if (up, down, ntaps) in SHAPES:
+            forms[(up, down, ntaps)] = form
+    print(combos)
+    assert set(combos.values()) == FORMS and len(FORMS) == 11, sorted(FORMS - set(combos.values()))
+    assert {(t, p, d) for t, p, _, d in (combos[s] for s in ALL_SOURCES)} >= {(1024, True, False), (256, True, False), (256, False, True)}
+    # the shapes the findings named take the forms they were added for, the largest LDS requests among them
+    for shape, combo in {(1, 2, 31): (1024, True, "uniform", False), (1, 4, 64): (1024, True, "uniform", False),
+                         (2, 5, 50): (1024, True, "lds", False), (64, 135, 7000): (1024, True, "global", False),
+                         (3, 20, 90): (256, True, "lds", False), (40, 300, 8000): (256, True, "global", False),
+                         (170, 845, 5440): (1024, True, "lds", False), (26, 498, 6110): (256, True, "lds", False)}.items():
+        assert combos[shape] == combo, (shape, combos[shape])
+    # (that (26, 498, 6110) is the planner's largest LDS request is asserted where the search runs: tests/test_resampler_plan.py)
     direct = {bool(f & hz.RESAMPLER_FORM_DIRECT) for f in forms.values()}
     tglobal = {bool(f & hz.RESAMPLER_FORM_TAPS_GLOBAL) for f in forms.values()}
     print(forms)
@@ -176,6 +201,51 @@ def test_the_list_covers_every_form(hz, ctx):
     for up, down, ntaps in EXTRA_SHAPES:
         with ctx.resampler(hz.FMT_C64, up, down, taps_of(up, down, ntaps)) as rs:
             assert rs.plan()[1] == hz.RESAMPLER_FORM_DIRECT | hz.RESAMPLER_FORM_TAPS_GLOBAL
+
+
+# ---- 1b. every table entry on its own ---------------------------------------------------------------
+
+@pytest.mark.parametrize("shape", ro.RESAMPLER_SHAPES, ids=lambda s: "U%d-D%d-L%d" % s[:3])
+def test_tap_readout(hz, ctx, shape):
+    """Q rows, row r zero but for impulses of power-of-two amplitude at r, r + Q, r + 2 Q, ...: every output is ONE
+    exact product h[phi_m + q U] amp, every other term fma(h, +-0, acc), so pushes and flush EQUAL the float64
+    reference rounded to complex64 -- no tolerance.  Across the rows every output meets every q: every entry of the
+    polyphase table that a stream can read is read (the share is computed from the definition's indices and must be
+    100 %).  Cut inside the first Q - 1 samples and at T - 1 outputs, then flushed, so the held tail's values are read
+    out too.  c64, i8 and i16 (u8's conversion has no zero); the one shape whose rows would be a gigabyte runs i8
+    alone over T + 3 outputs."""
+    up, down, ntaps, tile = shape
+    q = -(-ntaps // up)
+    h = taps_of(up, down, ntaps)
+    count = ro.readout_outputs(shape)
+    n = samples_for(count, up, down)
+    # `exist` counts the entries hp[phi][q] with phi + q U < L whose phase a stream can have: phi a multiple of
+    # gcd(U, D).  Where U and D share a factor (as at (5, 5, 20)) no input reaches the other phases, so they are left
+    # out of the 100 %; for coprime U and D this is every entry with phi + q U < L.
+    read, exist = ro.resampler_coverage(n, ntaps, up, down)
+    assert read == exist > 0, f"{read} of {exist} table entries read"
+    c0 = max(1, (q - 1) // 2)
+    cuts = sorted({0, min(c0, n), min(max(c0, samples_for(tile - 1, up, down)), n), n})
+    for fmt in (("i8",) if shape == ro.READOUT_SMALL else ("c64", "i8", "i16")):
+        raw = ro.train_rows(fmt, n, q)
+        x = dev(raw if q > 1 else raw[0])
+        del raw
+        if fmt != "c64":  # the values were chosen so that the conversion is an exact power of two
+            assert np.array_equal(as_c64(ctx, x[0] if q > 1 else x).cpu().numpy(), ro.train(fmt, n, q, first=0)[1])
+        with ctx.resampler(FMT[fmt], up, down, h, streams=q) as rs:
+            assert rs.plan()[0] == tile
+            got = run(rs, x, cuts).cpu().numpy().reshape(q, -1)
+        total = ref.total_outputs(n, ntaps, up, down)
+        assert got.shape[1] == ref.stream_outputs(n, ntaps, up, down) >= count
+        assert not got[:, total:].any(), "outputs of padding taps alone are not zero"
+        for r in range(q):
+            want = ref.upfirdn_poly(h, ro.train(fmt, n, q, first=r)[1], up, down)
+            if not ro.readout_equal(got[r, :total], want):
+                bad = np.flatnonzero(~(got[r, :total] == want.astype(np.complex64)))
+                m = int(bad[0])
+                raise AssertionError(f"U={up} D={down} L={ntaps} {fmt} row {r}: {bad.size} outputs differ, the first m = {m} "
+                                     f"(phi {m * down % up}, i {m * down // up}): {got[r, m]} for {want[m]}")
+    print(f"U={up} D={down} L={ntaps} Q={q}: {read} of {exist} table entries read and equal over {q} rows of {got.shape[1]} outputs, cuts {cuts}")
 
 
 # ---- 2. identity -----------------------------------------------------------------------------------
@@ -194,7 +264,7 @@ def test_identity_equals_convert(hz, ctx, fmt):
 
 # ---- 3. cuts ---------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("up,down,ntaps", [(3, 2, 24), (160, 147, 1920), (1, 8, 128)])
+@pytest.mark.parametrize("up,down,ntaps", [(3, 2, 24), (160, 147, 1920), (1, 8, 128), (2, 5, 50)])
 @pytest.mark.parametrize("fmt", ["c64", "u8"])
 def test_cuts_bit_identical(hz, ctx, up, down, ntaps, fmt):
     h = taps_of(up, down, ntaps)
@@ -236,7 +306,8 @@ def test_cuts_bit_identical(hz, ctx, up, down, ntaps, fmt):
 
 # ---- 4. streams and pitch --------------------------------------------------------------------------
 
-@pytest.mark.parametrize("streams,fmt,up,down,ntaps", [(5, "u8", 3, 2, 24), (256, "c64", 2, 3, 50), (5, "c64", 1, 1024, 256)])
+@pytest.mark.parametrize("streams,fmt,up,down,ntaps", [(5, "u8", 3, 2, 24), (256, "c64", 2, 3, 50), (5, "c64", 1, 1024, 256),
+                                                      (5, "i16", 2, 5, 50)])
 def test_streams_and_pitch(hz, ctx, hctx, streams, fmt, up, down, ntaps):
     """Rows that differ, an input pitch above n, an output pitch above the count: every row bit-equal to a
     single-stream object on that row, guard columns intact; HOST results bit-equal to DEVICE ones."""

@@ -1,7 +1,16 @@
 """The polyphase synthesis bank (include/hzsdr_synthesizer.h) on the GPU: the output stream against the float64
 restatements of tests/synthesizer_ref.py within B(M, Q) = 3e-7 log2 M + 6e-8 (Q + 2), Q = ceil(L / D), per block of M
 outputs; bit for bit across pushes, internal groups, memory spaces, layouts, orders and runs; and against the GPU
-channelizer, as its adjoint and as its inverse."""
+channelizer, as its adjoint and as its inverse.  All six sizes, up to P = 32; every tap read out on its own by frames
+with a single non-zero value (tests/readout.py), per output position against a few float32 ulps of that position's
+own tap.
+
+test_tap_readout's worst (|got - want| / (|g[t - j0 D]| |amp|) - 2^-24) as a multiple of max(yardstick, 2^-23) (it
+prints them; the transform's part of the bound allows K = 4, the yardstick is scipy's single-precision backward
+transform of the same one-hot frame).  Observed on an MI355X:
+
+    not measured
+"""
 import ctypes as C
 import importlib
 import os
@@ -11,9 +20,10 @@ import numpy as np
 import pytest
 
 import channelizer_ref as cref
+import readout as ro
 import synthesizer_ref as ref
 from conftest import ROOT
-from util import FMT, splitmix64
+from util import FFT_FLOOR, FMT, splitmix64
 
 pytestmark = pytest.mark.gpu
 
@@ -82,21 +92,19 @@ def run(sy, y, cuts=None, flush=True):
     return np.concatenate(out)
 
 
-def block_errors(got, want, m):
-    """relative L2 of every block of M outputs, the ragged last one included"""
-    d = np.asarray(got).astype(np.complex128) - want
-    return np.array([np.linalg.norm(d[a:a + m]) / np.linalg.norm(want[a:a + m]) for a in range(0, want.shape[0], m)])
+block_errors = ro.block_errors  # relative L2 of every block of M outputs, the ragged last one included
 
 
 # ---- 1. accuracy against float64 -------------------------------------------------------------------
 
-@pytest.mark.parametrize("m", [256, 1024, 2048, 8192])
+@pytest.mark.parametrize("m", [256, 512, 1024, 2048, 4096, 8192])
 def test_stream_against_float64(hz, ctx, m):
     """Every block of M outputs within B(M, Q) of the float64 overlap-add.  The error of a block scales with the taps
     that weight it, as its norm does, so the stream's edge blocks (whose norm is far below the middle's) are held to
-    the same relative bound."""
+    the same relative bound.  The smallest and the largest size also run the longest prototype the bank accepts,
+    P = 32."""
     worst = 0.0
-    for p, d in ((1, m), (3, m), (8, m // 2), (4, 3 * m // 4), (2, 100), (1, 1)):
+    for p, d in ((1, m), (3, m), (8, m // 2), (4, 3 * m // 4), (2, 100), (1, 1)) + (((32, m // 2),) if m in (256, 8192) else ()):
         f = 2 * xpb(m) + 5  # (several workgroups, the last partly dead)
         L = p * m
         g = hz.channelizer_taps(m, p)
@@ -115,9 +123,57 @@ def test_stream_against_float64(hz, ctx, m):
     print(f"M={m}: worst GPU / float64 relative L2 per block {worst:.3e}")
 
 
+# ---- 1b. every tap on its own ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("order", ["zero", "negative"])
+@pytest.mark.parametrize("m", [256, 512, 1024, 2048, 4096, 8192])
+def test_tap_readout(hz, ctx, m, order):
+    """F frames, all zero except Y[j0][k0] = amp: output position t in [j0 D, j0 D + L) is g[t - j0 D] amp
+    exp(+2 pi i k0 t / M), everything outside that span exactly zero.  Per output
+
+        |got - want| <= (FFT_K max(y, 2^-23) + 2^-24) |g[t - j0 D]| |amp|
+
+    with y the max_bin of scipy's single-precision backward transform of that one-hot frame and 2^-24 the one
+    rounding of the product with the tap: nothing in it is measured on the kernel, and a wrong small tap cannot hide
+    behind large ones.  j0 in the middle of a workgroup's frames (never the stream's first frame, which has no
+    overlap partner before it and the rotation 0: frame 1 where a workgroup holds one frame), the last frame of a push
+    and the first of the next; k0 = 1, M / 2 + 1 and about M / 3; an odd hop; M = 1024 also channel-major."""
+    p, d = 2, m // 2 + 1
+    L = p * m
+    f = 2 * xpb(m) + 5
+    cut = xpb(m) + 3
+    g = hz.channelizer_taps(m, p)
+    amp = 0.5 - 0.25j
+    o = hz.ZERO_FIRST if order == "zero" else hz.NEGATIVE_FIRST
+    worst = 0.0
+    for layout in (("frames", "channels") if m == 1024 else ("frames",)):
+        sy = ctx.synthesizer(hz.FMT_C64, m, g, hop=d, order=o, layout=layout)
+        for k0 in (1, m // 2 + 1, (m // 3) | 1):
+            bound = ro.synthesizer_bound(m, k0, amp)
+            floor = max(ro.synthesizer_yardstick(m, k0, amp), FFT_FLOOR)
+            for j0 in (max(1, xpb(m) // 2), cut - 1, cut):
+                y = np.zeros((f, m), np.complex64)
+                y[j0, int(cref.pos(k0, m, o == hz.NEGATIVE_FIRST))] = amp
+                got = run(sy, dev(y.T if layout == "channels" else y), [0, cut, f]).cpu().numpy()
+                want, scale = ro.synthesizer_want(g, m, d, f, j0, k0, amp)
+                assert got.shape == want.shape and not np.isnan(got.view(np.float32)).any()
+                span = scale > 0
+                outside = np.ones(want.shape[0], bool)
+                outside[j0 * d:j0 * d + L] = False
+                assert not got[outside].any(), f"M={m} {order} {layout} k0={k0} j0={j0}: output outside the frame's span"
+                assert not got[~span & ~outside].any(), "a zero tap's output is not zero"
+                err = np.abs(got.astype(np.complex128) - want)[span] / scale[span]
+                at = int(np.flatnonzero(span)[err.argmax()])
+                assert (err <= bound).all(), (f"M={m} {order} {layout} k0={k0} j0={j0}: position {at} (tap {at - j0 * d}): "
+                                              f"{err.max():.3e} of the tap > {bound:.3e}")
+                worst = max(worst, (err.max() - 2.0 ** -24) / floor)
+        sy.close()
+    print(f"M={m} {order}: worst (error / tap - 2^-24) / max(yardstick, 2^-23) = {worst:.2f}")
+
+
 # ---- 2. the definition -----------------------------------------------------------------------------
 
-@pytest.mark.parametrize("m,p,d", [(256, 8, 192), (1024, 4, 1024)])
+@pytest.mark.parametrize("m,p,d", [(256, 8, 192), (1024, 4, 1024), (512, 3, 100)])
 def test_against_the_definition(hz, ctx, m, p, d):
     f = max(2 * xpb(m) + 5, (p * m) // d + 6)  # (a steady region exists: F D > L - D)
     L = p * m

@@ -83,6 +83,8 @@ def test_constants_match_header(hz):
     assert int(defs["HZSDR_RESAMPLER_FORM_DIRECT"]) == hz.RESAMPLER_FORM_DIRECT == 1
     assert int(defs["HZSDR_RESAMPLER_FORM_TAPS_GLOBAL"]) == hz.RESAMPLER_FORM_TAPS_GLOBAL == 2
     assert int(defs["HZSDR_RESAMPLER_FORM_TAPS_UNIFORM"]) == hz.RESAMPLER_FORM_TAPS_UNIFORM == 4
+    assert int(defs["HZSDR_RESAMPLER_FORM_WINDOW_PADDED"]) == hz.RESAMPLER_FORM_WINDOW_PADDED == 8
+    assert hz.RESAMPLER_FORM_WINDOW_PADDED is importlib.import_module("go-sdr_amd.resampler").RESAMPLER_FORM_WINDOW_PADDED
 
 
 def test_python_layers_are_exported(hz):

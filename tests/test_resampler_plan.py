@@ -2,11 +2,15 @@
 and checked against Python's big integers (tests/host/resampler_plan.cpp): counts, the running phase and relative
 index, the held samples and the flush count of random pushes from stream positions up to 2^62 -- a 2^32 crossing
 among them, which no GPU test can push -- the window of random tiles, the lanes' (i, phi), and the reciprocal of U
-over the whole range the kernel uses."""
+over the whole range the kernel uses.  The same program searches every shape for the largest LDS request and reports
+the form of each shape of the GPU tests' accuracy list: the shape the list names as the largest is that maximum, and
+the list's tiles are the planner's."""
 import os
 import random
 import subprocess
 import tempfile
+
+import readout as ro
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPAN_MAX = 1 << 62  # rs::kSpanMax
@@ -57,9 +61,24 @@ def test_resampler_plan_under_asan_ubsan():
                                "-o", exe])
         text = cases(20261017, 400)
         assert text.count("\nP") > 4000 and text.count("\nT") > 4000
+        text += "".join(f"G {u} {d} {-(-ntaps // u)}\n" for u, d, ntaps, _ in ro.RESAMPLER_SHAPES)
         with open(data, "w") as f:
             f.write(text)
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
         out = subprocess.run([exe, data], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
         assert out.returncode == 0, out.stdout[-4000:]
         assert "resampler_plan ok" in out.stdout, out.stdout[-2000:]
+    lines = out.stdout.splitlines()
+    # the largest LDS request among the forms with a window, and the accuracy list's shape that asks for it
+    largest = [tuple(int(v) for v in s.split(":")[1].split()) for s in lines if s.startswith("largest lds:")]
+    assert largest == [ro.LARGEST_LDS], largest
+    u, d, q, window, nbytes = ro.LARGEST_LDS
+    assert nbytes > 64 * 1024, "the largest request no longer passes the 64 KiB a launch gets without asking"
+    forms = {tuple(v[:3]): v[3:] for v in ([int(t) for t in s.split(":")[1].split()] for s in lines if s.startswith("form:"))}
+    mine = [s for s in ro.RESAMPLER_SHAPES if (s[0], s[1], -(-s[2] // s[0])) == (u, d, q)]
+    assert len(mine) == 1 and forms[(u, d, q)][5] == nbytes, "the accuracy list lacks the shape of the largest LDS request"
+    for up, down, ntaps, tile in ro.RESAMPLER_SHAPES:
+        assert forms[(up, down, -(-ntaps // up))][0] == tile, (up, down, ntaps)
+    # every reachable (tile, padded, table, direct) combination occurs in the list, by the planner's own report
+    combos = {(t, bool(pad), "global" if tg else "uniform" if tu else "lds", bool(direct)) for t, direct, tg, tu, pad, _ in forms.values()}
+    assert len(combos) == 11, sorted(combos)
