@@ -434,6 +434,13 @@ class Context:
         from .resampler import Resampler
         return Resampler(self, src_fmt, up, down, taps, streams)
 
+    def demodulator(self, src_fmt, mode, taps=None, down=1, streams=1):
+        """The demodulator bank (include/hzsdr_demod.h, demod.Demodulator): FM, phase, envelope or power (DEMOD_*) of
+        `streams` rows of src_fmt samples, then the real post-filter `taps` (float32 values, default [1.0]: the bare
+        detector) and a decimation by `down`; real float32."""
+        from .demod import Demodulator
+        return Demodulator(self, src_fmt, mode, taps, down, streams)
+
 
 class LookupTable:
     """sdr.LookupTable (iq_lookup_table.go:36-50)."""
@@ -837,6 +844,8 @@ from .channelizer import Channelizer, channelizer_taps  # noqa: E402
 from .synthesizer import Synthesizer, wola_taps  # noqa: E402
 from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM, RESAMPLER_FORM_WINDOW_PADDED  # noqa: E402
 from .resampler import Resampler, resampler_taps  # noqa: E402
+from ._capi import DEMOD_FM, DEMOD_PHASE, DEMOD_ENVELOPE, DEMOD_POWER, DEMOD_FORM_HALF_TILE, DEMOD_FORM_TRANSPOSED  # noqa: E402
+from .demod import Demodulator, fm_gain  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

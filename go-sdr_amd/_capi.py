@@ -228,8 +228,22 @@ RESAMPLER_SIGNATURES = {
 }
 RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM, RESAMPLER_FORM_WINDOW_PADDED = 1, 2, 4, 8
 
+# name -> (restype, argtypes); every symbol include/hzsdr_demod.h declares
+DEMOD_SIGNATURES = {
+    "hzsdr_demod_create": (i32, [vp, i32, i32, sz, C.POINTER(f32), sz, sz, pvp]),
+    "hzsdr_demod_push": (i32, [vp, vp, sz, sz, vp, sz, sz, psz]),
+    "hzsdr_demod_flush": (i32, [vp, vp, sz, sz, psz]),
+    "hzsdr_demod_outputs_for": (i32, [vp, sz, psz]),
+    "hzsdr_demod_pending": (i32, [vp, C.POINTER(u64), C.POINTER(u64), psz]),
+    "hzsdr_demod_plan": (i32, [vp, psz, C.POINTER(i32)]),
+    "hzsdr_demod_reset": (i32, [vp]),
+    "hzsdr_demod_free": (i32, [vp]),
+}
+DEMOD_FM, DEMOD_PHASE, DEMOD_ENVELOPE, DEMOD_POWER = 1, 2, 3, 4
+DEMOD_FORM_HALF_TILE, DEMOD_FORM_TRANSPOSED = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
-                             *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items()):
+                             *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

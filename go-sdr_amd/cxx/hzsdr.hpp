@@ -27,6 +27,7 @@
 #include "../../include/hzsdr.h"
 #include "../../include/hzsdr_channelizer.h"
 #include "../../include/hzsdr_resampler.h"
+#include "../../include/hzsdr_demod.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1078,6 +1079,65 @@ private:
     const Context &x_;
     size_t streams_;
     hzsdr_resampler *r_ = nullptr;
+};
+
+// The demodulator bank (include/hzsdr_demod.h): HZSDR_DEMOD_FM, _PHASE, _ENVELOPE or _POWER of `streams` rows of
+// src_format samples, then the real post-filter `taps` (empty: [1.0], the bare detector) and a decimation by `down`;
+// real float32.  Push consumes `n` samples of every row (row s starts s * in_stride samples into `in`; dense rows when
+// in_stride is 0) and returns the outputs they complete, dense rows of the returned count; Flush returns the outputs
+// that still depend on samples pushed and starts over.
+class Demodulator {
+public:
+    Demodulator(const Context &x, int src_format, int mode, const std::vector<float> &taps = {}, size_t down = 1, size_t streams = 1)
+        : x_(x), streams_(streams) {
+        const float one = 1.0f;
+        check(x_.raw(), hzsdr_demod_create(x_.raw(), src_format, mode, down, taps.empty() ? &one : taps.data(), taps.empty() ? 1 : taps.size(),
+                                           streams, &d_));
+    }
+    ~Demodulator() { if (d_) hzsdr_demod_free(d_); }
+    Demodulator(const Demodulator &) = delete;
+    Demodulator &operator=(const Demodulator &) = delete;
+    // (row s of the result is [s * count, (s + 1) * count) with count = size() / Streams())
+    std::vector<float> Push(const void *in, size_t n, size_t in_stride = 0) {
+        const size_t count = OutputsFor(n);
+        std::vector<float> out(streams_ * count);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_demod_push(d_, n ? in : nullptr, n, in_stride ? in_stride : n, count ? out.data() : nullptr, count, count, &w));
+        return out;
+    }
+    std::vector<float> Flush() {
+        const size_t count = std::get<2>(Pending());
+        std::vector<float> out(streams_ * count);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_demod_flush(d_, count ? out.data() : nullptr, count, count, &w));
+        return out;
+    }
+    size_t OutputsFor(size_t n) const {
+        size_t c = 0;
+        check(x_.raw(), hzsdr_demod_outputs_for(d_, n, &c));
+        return c;
+    }
+    // -> (samples consumed, index of the next output, outputs a flush would write now), per stream
+    std::tuple<uint64_t, uint64_t, size_t> Pending() const {
+        uint64_t n = 0, m = 0;
+        size_t f = 0;
+        check(x_.raw(), hzsdr_demod_pending(d_, &n, &m, &f));
+        return {n, m, f};
+    }
+    // -> (outputs per workgroup, HZSDR_DEMOD_FORM_*)
+    std::pair<size_t, int> Plan() const {
+        size_t t = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_demod_plan(d_, &t, &f));
+        return {t, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_demod_reset(d_)); }
+    size_t Streams() const { return streams_; }
+
+private:
+    const Context &x_;
+    size_t streams_;
+    hzsdr_demod *d_ = nullptr;
 };
 }  // namespace stream
 }  // namespace hzsdr

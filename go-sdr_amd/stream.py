@@ -922,3 +922,25 @@ class ResampleReader(Reader):
 
     def sample_rate(self):
         return self.resampler.sample_rate(self.inp.sample_rate())
+
+
+# ---- a Reader demodulated (include/hzsdr_demod.h) ----------------------------------------------
+
+def demodulator_blocks(r, demodulator, block=READER_BLOCK):
+    """Read `r` to its end in blocks of `block` samples, push them through `demodulator` (a one-stream
+    demod.Demodulator of the reader's format on a HOST context) and yield each push's outputs, then the flush last:
+    concatenated, the whole demodulated stream, float32 at r.sample_rate() / down."""
+    if demodulator.src_fmt != r.sample_format():
+        raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+    buf = make_samples(r.sample_format(), block)
+    while True:
+        try:
+            k = r.read(buf)
+        except EOF:
+            break
+        out = demodulator.push(buf[:k])
+        if out.shape[0]:
+            yield out
+    tail = demodulator.flush()
+    if tail.shape[0]:
+        yield tail
