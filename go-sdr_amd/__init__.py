@@ -441,6 +441,13 @@ class Context:
         from .demod import Demodulator
         return Demodulator(self, src_fmt, mode, taps, down, streams)
 
+    def tuner_bank(self, src_fmt, words, taps, down=1):
+        """The tuner bank (include/hzsdr_tuner.h, tuner.TunerBank): one pass over a stream of src_fmt samples, a tuner
+        per entry of `words` (uint32 frequency words, tuner_word(freq_hz, sample_rate)), the shared prototype filter
+        `taps` (float32 values) and a decimation by `down`; complex64, one row per tuner."""
+        from .tuner import TunerBank
+        return TunerBank(self, src_fmt, words, taps, down)
+
 
 class LookupTable:
     """sdr.LookupTable (iq_lookup_table.go:36-50)."""
@@ -846,6 +853,8 @@ from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_
 from .resampler import Resampler, resampler_taps  # noqa: E402
 from ._capi import DEMOD_FM, DEMOD_PHASE, DEMOD_ENVELOPE, DEMOD_POWER, DEMOD_FORM_HALF_TILE, DEMOD_FORM_TRANSPOSED  # noqa: E402
 from .demod import Demodulator, fm_gain  # noqa: E402
+from ._capi import TUNER_FORM_CHUNKED, TUNER_FORM_TRANSPOSED, TUNER_READ_TAPS, TUNER_READ_T2, TUNER_READ_T1, TUNER_READ_T0  # noqa: E402
+from .tuner import TunerBank, tuner_word  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

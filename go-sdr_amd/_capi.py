@@ -242,8 +242,24 @@ DEMOD_SIGNATURES = {
 DEMOD_FM, DEMOD_PHASE, DEMOD_ENVELOPE, DEMOD_POWER = 1, 2, 3, 4
 DEMOD_FORM_HALF_TILE, DEMOD_FORM_TRANSPOSED = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_tuner.h declares
+TUNER_SIGNATURES = {
+    "hzsdr_tuner_create": (i32, [vp, i32, C.POINTER(C.c_uint32), sz, sz, C.POINTER(f32), sz, pvp]),
+    "hzsdr_tuner_push": (i32, [vp, vp, sz, vp, sz, sz, psz]),
+    "hzsdr_tuner_flush": (i32, [vp, vp, sz, sz, psz]),
+    "hzsdr_tuner_outputs_for": (i32, [vp, sz, psz]),
+    "hzsdr_tuner_pending": (i32, [vp, C.POINTER(u64), C.POINTER(u64), psz]),
+    "hzsdr_tuner_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_tuner_set_words": (i32, [vp, sz, sz, C.POINTER(C.c_uint32)]),
+    "hzsdr_tuner_readout": (i32, [vp, i32, sz, vp, sz]),
+    "hzsdr_tuner_reset": (i32, [vp]),
+    "hzsdr_tuner_free": (i32, [vp]),
+}
+TUNER_FORM_CHUNKED, TUNER_FORM_TRANSPOSED = 1, 2
+TUNER_READ_TAPS, TUNER_READ_T2, TUNER_READ_T1, TUNER_READ_T0 = 1, 2, 3, 4
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
-                             *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items()):
+                             *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

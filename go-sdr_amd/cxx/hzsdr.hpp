@@ -28,6 +28,7 @@
 #include "../../include/hzsdr_channelizer.h"
 #include "../../include/hzsdr_resampler.h"
 #include "../../include/hzsdr_demod.h"
+#include "../../include/hzsdr_tuner.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1138,6 +1139,69 @@ private:
     const Context &x_;
     size_t streams_;
     hzsdr_demod *d_ = nullptr;
+};
+
+// The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word
+// (word = round(f / fs * 2^32) mod 2^32), the shared prototype filter `taps` and a decimation by `down`; complex64.
+// Push consumes `n` samples and returns the outputs they complete as dense rows, row k of the returned count per row
+// at [k * count, (k + 1) * count); Flush returns the outputs that still depend on samples pushed and starts over.
+class TunerBank {
+public:
+    TunerBank(const Context &x, int src_format, const std::vector<uint32_t> &words, const std::vector<float> &taps, size_t down = 1)
+        : x_(x), tuners_(words.size()), qp_((taps.size() + 1) & ~(size_t)1) {
+        check(x_.raw(), hzsdr_tuner_create(x_.raw(), src_format, words.data(), words.size(), down, taps.data(), taps.size(), &t_));
+    }
+    ~TunerBank() { if (t_) hzsdr_tuner_free(t_); }
+    TunerBank(const TunerBank &) = delete;
+    TunerBank &operator=(const TunerBank &) = delete;
+    std::vector<std::complex<float>> Push(const void *in, size_t n) {
+        const size_t count = OutputsFor(n);
+        std::vector<std::complex<float>> out(tuners_ * count);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_tuner_push(t_, n ? in : nullptr, n, count ? out.data() : nullptr, count, count, &w));
+        return out;
+    }
+    std::vector<std::complex<float>> Flush() {
+        const size_t count = std::get<2>(Pending());
+        std::vector<std::complex<float>> out(tuners_ * count);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_tuner_flush(t_, count ? out.data() : nullptr, count, count, &w));
+        return out;
+    }
+    size_t OutputsFor(size_t n) const {
+        size_t c = 0;
+        check(x_.raw(), hzsdr_tuner_outputs_for(t_, n, &c));
+        return c;
+    }
+    // -> (samples consumed, index of the next output, outputs per row a flush would write now)
+    std::tuple<uint64_t, uint64_t, size_t> Pending() const {
+        uint64_t n = 0, m = 0;
+        size_t f = 0;
+        check(x_.raw(), hzsdr_tuner_pending(t_, &n, &m, &f));
+        return {n, m, f};
+    }
+    // -> (outputs per workgroup, rows of the real matrix per workgroup, HZSDR_TUNER_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t t = 0, r = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_tuner_plan(t_, &t, &r, &f));
+        return {t, r, f};
+    }
+    // the words of tuners [first, first + words.size()), in effect from the next push on
+    void Retune(size_t first, const std::vector<uint32_t> &words) { check(x_.raw(), hzsdr_tuner_set_words(t_, first, words.size(), words.data())); }
+    // HZSDR_TUNER_READ_TAPS of tuner `index` (the taps rounded up to an even count of complex64 values), or one of the three tables
+    std::vector<std::complex<float>> Readout(int what, size_t index = 0) const {
+        std::vector<std::complex<float>> out(what == HZSDR_TUNER_READ_TAPS ? qp_ : what == HZSDR_TUNER_READ_T0 ? 1024 : 2048);
+        check(x_.raw(), hzsdr_tuner_readout(t_, what, index, out.data(), out.size()));
+        return out;
+    }
+    void Reset() { check(x_.raw(), hzsdr_tuner_reset(t_)); }
+    size_t Tuners() const { return tuners_; }
+
+private:
+    const Context &x_;
+    size_t tuners_, qp_;
+    hzsdr_tuner *t_ = nullptr;
 };
 }  // namespace stream
 }  // namespace hzsdr

@@ -944,3 +944,25 @@ def demodulator_blocks(r, demodulator, block=READER_BLOCK):
     tail = demodulator.flush()
     if tail.shape[0]:
         yield tail
+
+
+# ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
+
+def tuner_rows(r, bank, block=READER_BLOCK):
+    """Read `r` to its end in blocks of `block` samples, push them through `bank` (a tuner.TunerBank of the reader's
+    format on a HOST context) and yield each push's (tuners, count) rows, then the flush last: concatenated along the
+    columns, every tuner's whole stream, complex64 at r.sample_rate() / down."""
+    if bank.src_fmt != r.sample_format():
+        raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+    buf = make_samples(r.sample_format(), block)
+    while True:
+        try:
+            k = r.read(buf)
+        except EOF:
+            break
+        out = bank.push(buf[:k])
+        if out.shape[-1]:
+            yield out
+    tail = bank.flush()
+    if tail.shape[-1]:
+        yield tail
