@@ -6,7 +6,9 @@ it must not (other factors, misaligned buffers, short calls, HZ_FIR_FFT=1, in-or
 
 What the matrix form adds to the late mixer's tests (test_gpu_latemix.py):
   * the filter sums are exact integer arithmetic on the quantised taps: a relative L2 error an
-    order of magnitude under the transform path's is asserted;
+    order of magnitude under the transform path's is asserted here; the exactness itself -- every
+    output bit for bit against integer sums -- is tests/test_gpu_fir_exact.py's, over the reference
+    of tests/firmm_ref.py (held to the planner headers by tests/test_firmm_ref_cpu.py);
   * chunks of 2048 outputs on the call's grid, owned by one clock run each; outputs whose window
     crosses a run boundary, the stream start or a run without a table come from the fix-up
     tasks -- calls that start on a boundary, cross several, wrap at 2*pi;
