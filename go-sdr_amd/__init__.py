@@ -441,6 +441,14 @@ class Context:
         from .demod import Demodulator
         return Demodulator(self, src_fmt, mode, taps, down, streams)
 
+    def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
+        """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
+        channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
+        (channels * P float32 values; channelizer.channelizer_taps), frames `hop` samples apart (default `channels`);
+        order NEGATIVE_FIRST (default, ascending signed frequency) or ZERO_FIRST; layout "frames" or "channels"."""
+        from .chanbank import ChannelBank, NegativeFirst
+        return ChannelBank(self, src_fmt, channels, taps, hop, NegativeFirst if order is None else order, layout)
+
     def tuner_bank(self, src_fmt, words, taps, down=1):
         """The tuner bank (include/hzsdr_tuner.h, tuner.TunerBank): one pass over a stream of src_fmt samples, a tuner
         per entry of `words` (uint32 frequency words, tuner_word(freq_hz, sample_rate)), the shared prototype filter
@@ -855,6 +863,8 @@ from ._capi import DEMOD_FM, DEMOD_PHASE, DEMOD_ENVELOPE, DEMOD_POWER, DEMOD_FOR
 from .demod import Demodulator, fm_gain  # noqa: E402
 from ._capi import TUNER_FORM_CHUNKED, TUNER_FORM_TRANSPOSED, TUNER_READ_TAPS, TUNER_READ_T2, TUNER_READ_T1, TUNER_READ_T0  # noqa: E402
 from .tuner import TunerBank, tuner_word  # noqa: E402
+from ._capi import CHANBANK_FORM_A_LDS, CHANBANK_READ_DFT, CHANBANK_READ_TAPS  # noqa: E402
+from .chanbank import ChannelBank  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

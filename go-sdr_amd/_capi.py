@@ -258,8 +258,23 @@ TUNER_SIGNATURES = {
 TUNER_FORM_CHUNKED, TUNER_FORM_TRANSPOSED = 1, 2
 TUNER_READ_TAPS, TUNER_READ_T2, TUNER_READ_T1, TUNER_READ_T0 = 1, 2, 3, 4
 
+# name -> (restype, argtypes); every symbol include/hzsdr_chanbank.h declares
+CHANBANK_SIGNATURES = {
+    "hzsdr_chanbank_create": (i32, [vp, i32, sz, C.POINTER(f32), sz, sz, i32, i32, pvp]),
+    "hzsdr_chanbank_push": (i32, [vp, vp, sz, vp, sz, sz, psz]),
+    "hzsdr_chanbank_frames_for": (i32, [vp, sz, psz]),
+    "hzsdr_chanbank_pending": (i32, [vp, psz, C.POINTER(u64)]),
+    "hzsdr_chanbank_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_chanbank_readout": (i32, [vp, i32, sz, vp, sz]),
+    "hzsdr_chanbank_reset": (i32, [vp]),
+    "hzsdr_chanbank_free": (i32, [vp]),
+}
+CHANBANK_FORM_A_LDS = 1
+CHANBANK_READ_DFT, CHANBANK_READ_TAPS = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
-                             *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items()):
+                             *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
+                             *CHANBANK_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -1,0 +1,382 @@
+// hz_chanbank.hip -- the channel bank (include/hzsdr_chanbank.h): the polyphase channelizer for any M from 2 to 255.
+// Frames of a raw IQ stream converted in the loads, folded with the prototype's taps into Mp values indexed by absolute
+// time modulo M, then y = W u as a float32 matrix product on v_mfma_f32_16x16x4_f32 -- A (2M x 2Mp, the DFT table as a
+// real matrix in MFMA operand order, made at create) times B (2Mp x T, the tile's folded frames) -- and stored as
+// complex rows (frame-major) or as one stream per channel (channel-major).  The term of the fold is hz_chanbank_math.h
+// (shared with tests/host/chanbank_ref.cpp), the host arithmetic (counts, tile, both layouts, position map, table) is
+// hz_chanbank_plan.h.
+//
+// One kernel.  A workgroup of four waves takes T consecutive frames of a push, tile after tile.  The fold gives
+// 2^fold_shift lanes to a frame (a wave folds 64 >> fold_shift frames at once; consecutive lanes read consecutive
+// samples but for the rotation's wrap point) and writes B into LDS, (re, im) of one r side by side at an odd pitch: its
+// stores spread over the banks and every B-operand read is 32 consecutive floats per half wave.  The rotation jD mod M
+// is applied to the load indices; the padding r and the frames behind the push's last one are +0.  Then the 16-row
+// tiles of A are dealt to the waves in groups of two; a wave holds 2 x T/16 accumulators and per k-step loads
+// two values of A (from LDS where A fits beside B, else coalesced from device memory: 256 bytes per wave and
+// value) and T/16 of B.  Channel-major runs the MFMA as A B: a lane holds 16 consecutive frames' worth of one channel
+// pair across its 16-lane group, stored as runs of 128 bytes per channel.  Frame-major runs it as (A B)^T = B^T A^T --
+// the SAME operand registers exchanged, the same chain of fused steps per output since a product commutes -- so that a
+// 16-lane group holds (re, im) of 8 consecutive channels of one frame and stores 64 consecutive bytes of its row.
+// make NO_PK_F32=1 (csrc/Makefile): no packed float32 instruction in this unit's device code, as in hz_tuner.hip
+#if defined(HZSDR_NO_PK_F32) && defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+
+#include "hz_chain_host.h"
+#include "../../include/hzsdr_chanbank.h"
+#include "hz_chanbank_math.h"
+#include "hz_chanbank_plan.h"
+
+struct hzsdr_chanbank {
+    hzsdr_ctx *ctx;
+    int fmt;
+    uint32_t M, L, D;
+    int order, layout;
+    hz::cp::Geom g{};
+    uint64_t magic = 0;
+    std::vector<float> taps_host;
+    std::vector<hz::cb::c32> W;            // M rows of Mp
+    float *taps = nullptr;                 // the prototype, L values
+    float *a_dev = nullptr;                // A in operand order
+    float2 *tail[2] = {nullptr, nullptr};  // the samples held for the next frame, converted: read one, write the other
+    int tcur = 0;
+    hz::cp::State st{};
+};
+
+namespace hz {
+
+struct CbArgs {
+    const void *in;
+    const float2 *tail;
+    const float *taps, *A;
+    uint64_t held, F, tiles;  // samples held; frames of the push; its tiles
+    size_t stride;            // channel-major row pitch
+    uint64_t magic;
+    uint32_t M, Mp, P, D, rot, steps, pitch, groups, fold_shift, b_floats, a_floats, neg_first;
+};
+
+typedef float cb_f4 __attribute__((ext_vector_type(4)));
+
+// NC: 16-frame column tiles of the workgroup's tile (T = 16 NC); A_LDS: A is staged in LDS behind B
+template <int FMT, int NC, bool A_LDS, int LAYOUT>
+__global__ __launch_bounds__(cp::kThreads) void chanbank_tile_kernel(CbArgs a, float2 *__restrict__ out) {
+    using RT = typename Raw<FMT>::t;
+    constexpr uint32_t T = NC * 16;
+    [[maybe_unused]] constexpr uint32_t NR = cp::kGroupTiles;
+    extern __shared__ __align__(16) unsigned char cb_lds[];
+    float *B = (float *)cb_lds;
+    [[maybe_unused]] float *Al = B + a.b_floats;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    [[maybe_unused]] const uint32_t n = lane & 15u, kk = lane >> 4;
+
+    if constexpr (A_LDS)
+        for (uint32_t i = tid; i < a.a_floats; i += cp::kThreads) Al[i] = a.A[i];  // (visible behind the first tile's barrier)
+
+    const uint32_t fold_lanes = 1u << a.fold_shift, fold_frames = 64u >> a.fold_shift;
+    const uint32_t fsub = lane >> a.fold_shift, r0 = lane & (fold_lanes - 1u);
+
+    for (uint64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        if (tile != blockIdx.x) __syncthreads();  // (the last tile's B is read no more)
+        const uint64_t f0 = tile * T;
+        // ---- the fold: B[2r + c][fl] of the tile's frames f0 + fl ----
+        {
+            const uint32_t rot0 = cp::chanbank_rot(a.rot, f0, a.D, a.M);
+            for (uint32_t fl = wave * fold_frames + fsub; fl < T; fl += cp::kWaves * fold_frames) {
+                const uint64_t f = f0 + fl;
+                const bool live = f < a.F;
+                const uint32_t w = rot0 + fl * a.D, s = w - cp::chanbank_div(w, a.magic) * a.M;
+                const uint64_t base = f * a.D;  // the frame's first sample in held ++ in
+                for (uint32_t r = r0; r < a.Mp; r += fold_lanes) {
+                    cb::c32 acc{0.0f, 0.0f};
+                    if (live && r < a.M) {
+                        uint32_t o = cp::chanbank_offset(r, s, a.M);
+                        for (uint32_t p = 0; p < a.P; p++, o += a.M) {
+                            const uint64_t v = base + o;
+                            const float2 x = v < a.held ? a.tail[v] : Raw<FMT>::cvt(((const RT *)a.in)[v - a.held]);
+                            acc = cb::chanbank_fold(acc, a.taps[o], cb::c32{x.x, x.y});
+                        }
+                    }
+                    *(float2 *)(B + cp::chanbank_b_index(2 * r, fl, a.pitch)) = make_float2(acc.re, acc.im);
+                }
+            }
+        }
+        __syncthreads();
+        // ---- the product: the groups of row tiles, dealt to the waves ----
+#if defined(__HIP_DEVICE_COMPILE__)
+        for (uint32_t grp = wave; grp < a.groups; grp += cp::kWaves) {
+            cb_f4 acc[NR][NC];
+#pragma unroll
+            for (uint32_t i = 0; i < NR; i++)
+#pragma unroll
+                for (uint32_t j = 0; j < NC; j++) acc[i][j] = cb_f4{0.0f, 0.0f, 0.0f, 0.0f};
+            const uint32_t rt0 = grp * NR;
+            const size_t a_tile = (size_t)a.steps * 64;
+            const float *ap = (A_LDS ? (const float *)Al : a.A) + (size_t)rt0 * a_tile + lane;
+            // lane (n, kk) of a B read: element (4 s + kk, 16 j + n)
+            const float *bp = B + cp::chanbank_b_index(kk, n, a.pitch);
+            const uint32_t b_step = 4u * a.pitch;  // two r down
+            for (uint32_t s = 0; s < a.steps; s++) {
+                float av[NR], bv[NC];
+#pragma unroll
+                for (uint32_t i = 0; i < NR; i++) av[i] = ap[i * a_tile + (size_t)s * 64];
+#pragma unroll
+                for (uint32_t j = 0; j < NC; j++) bv[j] = bp[s * b_step + j * 32u];
+#pragma unroll
+                for (uint32_t i = 0; i < NR; i++)
+#pragma unroll
+                    for (uint32_t j = 0; j < NC; j++) {
+                        if constexpr (LAYOUT == HZSDR_CHANNELIZER_CHANNEL_MAJOR)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+                        else
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[j], av[i], acc[i][j], 0, 0, 0);
+                    }
+            }
+            // D layout: column lane & 15, row (lane >> 4) * 4 + reg
+#pragma unroll
+            for (uint32_t i = 0; i < NR; i++) {
+                if constexpr (LAYOUT == HZSDR_CHANNELIZER_CHANNEL_MAJOR) {
+                    // rows are rows of A: registers (0, 1) and (2, 3) are (re, im) of two channels; columns are frames
+#pragma unroll
+                    for (uint32_t hh = 0; hh < 2; hh++) {
+                        const uint32_t k = (rt0 + i) * 8u + kk * 2u + hh;
+                        if (k >= a.M) continue;
+                        float2 *o = out + (size_t)cp::chanbank_pos(k, a.M, a.neg_first) * a.stride;
+#pragma unroll
+                        for (uint32_t j = 0; j < NC; j++) {
+                            const uint64_t f = f0 + j * 16u + n;
+                            if (f < a.F) o[f] = make_float2(acc[i][j][2 * hh], acc[i][j][2 * hh + 1]);
+                        }
+                    }
+                } else {
+                    // columns are rows of A: the lane's n is (channel, component); rows are frames
+                    const uint32_t k = (rt0 + i) * 8u + (n >> 1);
+                    if (k >= a.M) continue;
+                    float *o = (float *)out + (size_t)cp::chanbank_pos(k, a.M, a.neg_first) * 2u + (n & 1u);
+#pragma unroll
+                    for (uint32_t j = 0; j < NC; j++)
+#pragma unroll
+                        for (uint32_t q = 0; q < 4; q++) {
+                            const uint64_t f = f0 + j * 16u + kk * 4u + q;
+                            if (f < a.F) o[f * (2u * a.M)] = acc[i][j][q];
+                        }
+                }
+            }
+        }
+#endif
+    }
+}
+
+// the samples held for the next frame: V[start .. start + cnt) converted
+template <int FMT>
+__global__ __launch_bounds__(kThreads) void chanbank_tail_kernel(CbArgs a, uint64_t start, uint64_t cnt, float2 *__restrict__ tail_out) {
+    using RT = typename Raw<FMT>::t;
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * kThreads) {
+        const uint64_t v = start + i;
+        tail_out[i] = v < a.held ? a.tail[v] : Raw<FMT>::cvt(((const RT *)a.in)[v - a.held]);
+    }
+}
+
+template <int FMT, int NC, bool A_LDS>
+static int cb_launch_form(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
+    // (tile after tile in a workgroup once the chip is full many times over: A is staged once per workgroup)
+    const uint64_t cap = (uint64_t)c->ctx->num_cus * 16;
+    const dim3 grid((unsigned)(a.tiles < cap ? a.tiles : cap)), block(cp::kThreads);
+    if (c->layout == HZSDR_CHANNELIZER_FRAME_MAJOR)
+        HZ_TRY(launch_fv(chanbank_tile_kernel<FMT, NC, A_LDS, HZSDR_CHANNELIZER_FRAME_MAJOR>, grid, block, c->g.lds_bytes, c->ctx->stream, a, out));
+    else
+        HZ_TRY(launch_fv(chanbank_tile_kernel<FMT, NC, A_LDS, HZSDR_CHANNELIZER_CHANNEL_MAJOR>, grid, block, c->g.lds_bytes, c->ctx->stream, a, out));
+    HZ_HIP(c->ctx, hipGetLastError());
+    return HZSDR_OK;
+}
+
+template <int FMT>
+static int cb_launch_fmt(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
+    const bool al = c->g.a_lds;
+    if (c->g.col_tiles == 4) return al ? cb_launch_form<FMT, 4, true>(c, a, out) : cb_launch_form<FMT, 4, false>(c, a, out);
+    return cb_launch_form<FMT, 2, false>(c, a, out);  // (M above 128: A is far past the budget)
+}
+
+static int cb_launch(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
+    switch (c->fmt) {
+    case HZSDR_FMT_C64: return cb_launch_fmt<HZSDR_FMT_C64>(c, a, out);
+    case HZSDR_FMT_U8: return cb_launch_fmt<HZSDR_FMT_U8>(c, a, out);
+    case HZSDR_FMT_I8: return cb_launch_fmt<HZSDR_FMT_I8>(c, a, out);
+    default: return cb_launch_fmt<HZSDR_FMT_I16>(c, a, out);
+    }
+}
+
+template <int FMT>
+static void cb_tail_fmt(hzsdr_chanbank *c, const CbArgs &a, uint64_t start, uint64_t cnt) {
+    hipLaunchKernelGGL(chanbank_tail_kernel<FMT>, dim3(blocks_for(c->ctx, (size_t)cnt)), dim3(kThreads), 0, c->ctx->stream, a, start, cnt,
+                       c->tail[c->tcur ^ 1]);
+}
+
+static int cb_tail(hzsdr_chanbank *c, const CbArgs &a, uint64_t start, uint64_t cnt) {
+    switch (c->fmt) {
+    case HZSDR_FMT_C64: cb_tail_fmt<HZSDR_FMT_C64>(c, a, start, cnt); break;
+    case HZSDR_FMT_U8: cb_tail_fmt<HZSDR_FMT_U8>(c, a, start, cnt); break;
+    case HZSDR_FMT_I8: cb_tail_fmt<HZSDR_FMT_I8>(c, a, start, cnt); break;
+    default: cb_tail_fmt<HZSDR_FMT_I16>(c, a, start, cnt); break;
+    }
+    HZ_HIP(c->ctx, hipGetLastError());
+    return HZSDR_OK;
+}
+
+}  // namespace hz
+
+extern "C" {
+
+int hzsdr_chanbank_create(hzsdr_ctx *ctx, int src_format, size_t channels, const float *taps, size_t n_taps, size_t hop, int order,
+                          int layout, hzsdr_chanbank **out) {
+    using namespace hz;
+    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    const size_t m = channels;
+    if (format_size(src_format) == 0) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "chanbank: unknown source format");
+    if (m < cp::kMinChannels || m > cp::kMaxChannels)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the channel count is 2 ... 255 (hzsdr_channelizer.h from 256 on)");
+    if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: null taps");
+    if (n_taps == 0 || n_taps % m != 0 || n_taps > cp::kMaxTapsPerChannel * m)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the prototype has P * channels taps, 1 <= P <= 32");
+    if (hop == 0 || hop > m) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the hop is 1 ... channels");
+    if (order != HZSDR_ORDER_ZERO_FIRST && order != HZSDR_ORDER_NEGATIVE_FIRST)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: unknown fft order");
+    if (layout != HZSDR_CHANNELIZER_FRAME_MAJOR && layout != HZSDR_CHANNELIZER_CHANNEL_MAJOR)
+        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: unknown output layout");
+    HZ_TRY(enter(ctx));
+    hzsdr_chanbank *c = new hzsdr_chanbank{ctx, src_format, (uint32_t)m, (uint32_t)n_taps, (uint32_t)hop, order, layout};
+    c->g = cp::chanbank_geom(c->M);
+    c->magic = cp::chanbank_magic(c->M);
+    c->taps_host.assign(taps, taps + n_taps);
+    c->W = cp::chanbank_tables(c->M);
+    const std::vector<float> A = cp::chanbank_fill_a(c->g, c->W);
+    auto undo = [&](int rc) {
+        hzsdr_chanbank_free(c);
+        return rc;
+    };
+    hipError_t e = hipMalloc((void **)&c->taps, n_taps * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&c->a_dev, A.size() * sizeof(float));
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&c->tail[i], n_taps * sizeof(float2));
+    if (e == hipSuccess) e = hipMemcpyAsync(c->taps, taps, n_taps * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->a_dev, A.data(), A.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (taps is the caller's and A is local: free to go when create returns)
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "chanbank_create", __FILE__, __LINE__));
+    *out = c;
+    return HZSDR_OK;
+}
+
+int hzsdr_chanbank_frames_for(const hzsdr_chanbank *c, size_t n_in, size_t *frames) {
+    if (!c || !frames) return HZSDR_ERR_INVALID_ARGUMENT;
+    const hz::cp::Step p = hz::cp::chanbank_step(c->st, c->M, c->L, c->D, n_in);
+    if (!p.ok) return hz::fail(c->ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the push is too long");
+    *frames = (size_t)p.F;
+    return HZSDR_OK;
+}
+
+int hzsdr_chanbank_push(hzsdr_chanbank *c, const void *in, size_t n_in, void *out, size_t out_frames_cap, size_t out_stride,
+                        size_t *frames_written) {
+    using namespace hz;
+    if (frames_written) *frames_written = 0;
+    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
+    hzsdr_ctx *ctx = c->ctx;
+    if (n_in && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: null input");
+    const cp::Step p = cp::chanbank_step(c->st, c->M, c->L, c->D, n_in);
+    if (!p.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the push is too long");
+    const bool chmajor = c->layout == HZSDR_CHANNELIZER_CHANNEL_MAJOR;
+    const size_t F = (size_t)p.F, M = c->M;
+    if (out_frames_cap < F) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "chanbank: output buffer too small for the frames of the push");
+    if (chmajor && out_stride < F) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "chanbank: out_stride is below the frames of the push");
+    if (F && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: null output");
+    HZ_TRY(enter(ctx));
+    if (n_in == 0) return HZSDR_OK;
+    Stage st(ctx);
+    const void *din;
+    void *dout = nullptr;
+    size_t dstride = out_stride;
+    bool back2d = false;  // a HOST context's channel-major rows: dense on the device, copied back row by row
+    HZ_TRY(st.in(0, in, n_in * (size_t)format_size(c->fmt), &din));
+    if (F) {
+        if (!chmajor) {
+            HZ_TRY(st.out(1, out, F * M * sizeof(float2), &dout));
+        } else if (!st.host() || st.pinned_by_us(out, ((M - 1) * out_stride + F) * sizeof(float2))) {
+            dout = out;
+        } else {
+            HZ_TRY(ensure_slot(ctx, 1, M * F * sizeof(float2)));
+            dout = ctx->slots[1].ptr;
+            dstride = F;
+            back2d = true;
+        }
+    }
+    const cp::Geom &g = c->g;
+    const CbArgs a{din, c->tail[c->tcur], c->taps, c->a_dev, c->st.held, p.F, (p.F + g.T - 1) / g.T, dstride, c->magic,
+                   c->M, g.Mp, c->L / c->M, c->D, c->st.rot, g.steps, g.pitch, g.groups, g.fold_shift, g.b_floats, (uint32_t)g.a_floats,
+                   (uint32_t)(c->order == HZSDR_ORDER_NEGATIVE_FIRST)};
+    if (F) HZ_TRY(cb_launch(c, a, (float2 *)dout));
+    if (p.next.held) {
+        HZ_TRY(cb_tail(c, a, p.V - p.next.held, p.next.held));
+        c->tcur ^= 1;
+    }
+    c->st = p.next;
+    if (back2d)
+        HZ_HIP(ctx, hipMemcpy2DAsync(out, out_stride * sizeof(float2), dout, F * sizeof(float2), F * sizeof(float2), M, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+    HZ_TRY(st.finish());
+    if (frames_written) *frames_written = F;
+    return HZSDR_OK;
+}
+
+int hzsdr_chanbank_pending(const hzsdr_chanbank *c, size_t *samples_held, uint64_t *frame_index) {
+    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
+    if (samples_held) *samples_held = (size_t)c->st.held;
+    if (frame_index) *frame_index = c->st.frame;
+    return HZSDR_OK;
+}
+
+int hzsdr_chanbank_plan(const hzsdr_chanbank *c, size_t *tile_frames, size_t *tile_rows, int *form) {
+    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
+    if (tile_frames) *tile_frames = c->g.T;
+    if (tile_rows) *tile_rows = (size_t)c->g.row_tiles * 16;
+    if (form) *form = c->g.a_lds ? HZSDR_CHANBANK_FORM_A_LDS : 0;
+    return HZSDR_OK;
+}
+
+int hzsdr_chanbank_readout(const hzsdr_chanbank *c, int what, size_t index, void *dst, size_t cap) {
+    using namespace hz;
+    if (!c || !dst) return HZSDR_ERR_INVALID_ARGUMENT;
+    const void *src;
+    size_t n, size;
+    switch (what) {
+    case HZSDR_CHANBANK_READ_DFT:
+        if (index >= c->M) return fail(c->ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: no such row of the table");
+        src = c->W.data() + index * c->g.Mp, n = c->g.Mp, size = sizeof(cb::c32);
+        break;
+    case HZSDR_CHANBANK_READ_TAPS: src = c->taps_host.data(), n = c->L, size = sizeof(float); break;
+    default: return fail(c->ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: unknown read-out");
+    }
+    if (cap < n) return fail(c->ctx, HZSDR_ERR_DST_TOO_SMALL, "chanbank: the read-out buffer is too small");
+    memcpy(dst, src, n * size);
+    return HZSDR_OK;
+}
+
+int hzsdr_chanbank_reset(hzsdr_chanbank *c) {
+    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
+    // (the held samples are only read behind a later push's own writes: nothing to clear, nothing to wait for)
+    c->st = hz::cp::State{};
+    return HZSDR_OK;
+}
+
+int hzsdr_chanbank_free(hzsdr_chanbank *c) {
+    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->ctx->device);
+    (void)hipStreamSynchronize(c->ctx->stream);
+    for (void *p : {(void *)c->taps, (void *)c->a_dev, (void *)c->tail[0], (void *)c->tail[1]})
+        if (p) (void)hipFree(p);
+    delete c;
+    return HZSDR_OK;
+}
+
+}  // extern "C"
+
+#if defined(HZSDR_NO_PK_F32) && defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif

@@ -29,6 +29,7 @@
 #include "../../include/hzsdr_resampler.h"
 #include "../../include/hzsdr_demod.h"
 #include "../../include/hzsdr_tuner.h"
+#include "../../include/hzsdr_chanbank.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -970,6 +971,67 @@ private:
     const Context &x_;
     size_t m_;
     hzsdr_channelizer *c_ = nullptr;
+};
+// The channel bank (include/hzsdr_chanbank.h): the polyphase channelizer for the small channel counts, any `channels`
+// from 2 to 255.  Push consumes every sample it is given and returns the frames that complete as complex64, frames x
+// channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames (HZSDR_CHANNELIZER_CHANNEL_MAJOR, the pitch being the
+// frames of the push); HZSDR_ORDER_NEGATIVE_FIRST is ascending signed frequency, position 0 at -floor(channels / 2).
+class ChannelBank {
+public:
+    ChannelBank(const Context &x, int src_format, size_t channels, const std::vector<float> &taps, size_t hop,
+                int order = HZSDR_ORDER_NEGATIVE_FIRST, int layout = HZSDR_CHANNELIZER_FRAME_MAJOR)
+        : x_(x), m_(channels), l_(taps.size()) {
+        check(x_.raw(), hzsdr_chanbank_create(x_.raw(), src_format, channels, taps.empty() ? nullptr : taps.data(), taps.size(), hop, order,
+                                              layout, &c_));
+    }
+    ~ChannelBank() { if (c_) hzsdr_chanbank_free(c_); }
+    ChannelBank(const ChannelBank &) = delete;
+    ChannelBank &operator=(const ChannelBank &) = delete;
+    size_t FramesFor(size_t n_in) const {
+        size_t f = 0;
+        check(x_.raw(), hzsdr_chanbank_frames_for(c_, n_in, &f));
+        return f;
+    }
+    // (a HOST context's buffers: the frames come back in a vector)
+    std::vector<std::complex<float>> Push(Samples in) {
+        const size_t want = FramesFor(in.length);
+        std::vector<std::complex<float>> out(want * m_);
+        size_t frames = 0;
+        check(x_.raw(), hzsdr_chanbank_push(c_, in.data, in.length, out.empty() ? nullptr : out.data(), want, want, &frames));
+        return out;
+    }
+    // -> (samples held for the next frame, index of the next frame)
+    std::pair<size_t, uint64_t> Pending() const {
+        size_t h = 0;
+        uint64_t j = 0;
+        check(x_.raw(), hzsdr_chanbank_pending(c_, &h, &j));
+        return {h, j};
+    }
+    // -> (frames per workgroup, rows of the real matrix per workgroup, HZSDR_CHANBANK_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t t = 0, r = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_chanbank_plan(c_, &t, &r, &f));
+        return {t, r, f};
+    }
+    // row k of the DFT table: the channels rounded up to an even count of complex64 values
+    std::vector<std::complex<float>> Table(size_t k) const {
+        std::vector<std::complex<float>> out((m_ + 1) & ~(size_t)1);
+        check(x_.raw(), hzsdr_chanbank_readout(c_, HZSDR_CHANBANK_READ_DFT, k, out.data(), out.size()));
+        return out;
+    }
+    std::vector<float> Taps() const {
+        std::vector<float> out(l_);
+        check(x_.raw(), hzsdr_chanbank_readout(c_, HZSDR_CHANBANK_READ_TAPS, 0, out.data(), out.size()));
+        return out;
+    }
+    void Reset() { check(x_.raw(), hzsdr_chanbank_reset(c_)); }
+    size_t Channels() const { return m_; }
+
+private:
+    const Context &x_;
+    size_t m_, l_;
+    hzsdr_chanbank *c_ = nullptr;
 };
 // The polyphase synthesis bank (include/hzsdr_synthesizer.h), the channelizer's adjoint: Push consumes frames of
 // `channels` complex64 values, frames x channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames

@@ -858,6 +858,13 @@ def channelizer_frames(r, channelizer, block=READER_BLOCK):
             yield frames, channelizer.channel_rate(r.sample_rate()), channelizer.order
 
 
+def channel_bank_frames(r, bank, block=READER_BLOCK):
+    """Read `r` to its end in blocks of `block` samples, push them through `bank` (a chanbank.ChannelBank of the
+    reader's format on a HOST context) and yield (frames, channel_rate, order) for every block that completes frames:
+    `frames` in the bank's layout, channel_rate = r.sample_rate() / hop."""
+    return channelizer_frames(r, bank, block)
+
+
 # ---- channels back into one stream (include/hzsdr_synthesizer.h) -------------------------------
 
 def synthesizer_samples(frames_iterable, synthesizer):
