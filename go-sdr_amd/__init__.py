@@ -449,6 +449,19 @@ class Context:
         from .chanbank import ChannelBank, NegativeFirst
         return ChannelBank(self, src_fmt, channels, taps, hop, NegativeFirst if order is None else order, layout)
 
+    def covariance(self, src_fmt, channels, block):
+        """The covariance bank (include/hzsdr_covar.h, covar.Covariance): the spatial covariance R = sum x x^H of
+        `channels` coherent rows of src_fmt samples (2 ... 16), one unnormalised complex64 matrix per `block`
+        snapshots."""
+        from .covar import Covariance
+        return Covariance(self, src_fmt, channels, block)
+
+    def beam_scan(self, weights):
+        """The beam scan (include/hzsdr_covar.h, covar.Scan) over the rows of `weights`, (G, channels) complex64 as
+        steering_weights makes them: run(matrices) -> Re w Q w^H per matrix and row."""
+        from .covar import Scan
+        return Scan(self, weights)
+
     def tuner_bank(self, src_fmt, words, taps, down=1):
         """The tuner bank (include/hzsdr_tuner.h, tuner.TunerBank): one pass over a stream of src_fmt samples, a tuner
         per entry of `words` (uint32 frequency words, tuner_word(freq_hz, sample_rate)), the shared prototype filter
@@ -865,6 +878,8 @@ from ._capi import TUNER_FORM_CHUNKED, TUNER_FORM_TRANSPOSED, TUNER_READ_TAPS, T
 from .tuner import TunerBank, tuner_word  # noqa: E402
 from ._capi import CHANBANK_FORM_A_LDS, CHANBANK_READ_DFT, CHANBANK_READ_TAPS  # noqa: E402
 from .chanbank import ChannelBank  # noqa: E402
+from ._capi import COVAR_FORM_ONE_TILE, COVAR_FORM_THREE_TILES  # noqa: E402
+from .covar import Covariance, Scan, bartlett, capon, music, peaks, steering_weights  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

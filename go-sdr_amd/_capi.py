@@ -272,9 +272,26 @@ CHANBANK_SIGNATURES = {
 CHANBANK_FORM_A_LDS = 1
 CHANBANK_READ_DFT, CHANBANK_READ_TAPS = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_covar.h declares
+COVAR_SIGNATURES = {
+    "hzsdr_covar_create": (i32, [vp, i32, sz, sz, pvp]),
+    "hzsdr_covar_push": (i32, [vp, vp, sz, sz, vp, sz, sz, psz]),
+    "hzsdr_covar_push_channels": (i32, [vp, pvp, sz, vp, sz, sz, psz]),
+    "hzsdr_covar_flush": (i32, [vp, vp, sz, psz]),
+    "hzsdr_covar_blocks_for": (i32, [vp, sz, psz]),
+    "hzsdr_covar_pending": (i32, [vp, C.POINTER(u64), C.POINTER(u64), psz]),
+    "hzsdr_covar_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_covar_reset": (i32, [vp]),
+    "hzsdr_covar_free": (i32, [vp]),
+    "hzsdr_scan_create": (i32, [vp, sz, vp, sz, pvp]),
+    "hzsdr_scan_run": (i32, [vp, vp, sz, sz, vp, sz, sz]),
+    "hzsdr_scan_free": (i32, [vp]),
+}
+COVAR_FORM_ONE_TILE, COVAR_FORM_THREE_TILES = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
-                             *CHANBANK_SIGNATURES.items()):
+                             *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

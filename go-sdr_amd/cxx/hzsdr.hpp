@@ -30,6 +30,7 @@
 #include "../../include/hzsdr_demod.h"
 #include "../../include/hzsdr_tuner.h"
 #include "../../include/hzsdr_chanbank.h"
+#include "../../include/hzsdr_covar.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1266,4 +1267,105 @@ private:
     hzsdr_tuner *t_ = nullptr;
 };
 }  // namespace stream
+
+namespace array {
+
+// The covariance bank (include/hzsdr_covar.h): `channels` coherent rows (2 ... 16) of one format into their spatial
+// covariance, one unnormalised channels x channels complex64 matrix, row-major, per `block` snapshots.  Push consumes
+// every snapshot it is given -- one buffer per channel, as Context::Beamform takes them -- and returns the matrices of
+// the blocks that complete, one behind the other; Flush returns the open block's (or nothing) and starts over.
+class Covariance {
+public:
+    Covariance(const Context &x, int src_format, size_t channels, size_t block) : x_(x), n_(channels), b_(block) {
+        check(x_.raw(), hzsdr_covar_create(x_.raw(), src_format, channels, block, &c_));
+    }
+    ~Covariance() { if (c_) hzsdr_covar_free(c_); }
+    Covariance(const Covariance &) = delete;
+    Covariance &operator=(const Covariance &) = delete;
+    size_t BlocksFor(size_t n_in) const {
+        size_t b = 0;
+        check(x_.raw(), hzsdr_covar_blocks_for(c_, n_in, &b));
+        return b;
+    }
+    // (a HOST context's buffers: the matrices come back in a vector)
+    std::vector<std::complex<float>> Push(const std::vector<Samples> &channels) {
+        if (channels.size() != n_) throw Error(HZSDR_ERR_INVALID_ARGUMENT, "covariance: one buffer per channel");
+        std::vector<const void *> rows;
+        for (const Samples &s : channels) {
+            if (s.length != channels[0].length) throw Error(HZSDR_ERR_LENGTH_MISMATCH, "covariance: the channels' buffers have one length");
+            rows.push_back(s.data);
+        }
+        const size_t want = BlocksFor(channels[0].length);
+        std::vector<std::complex<float>> out(want * n_ * n_);
+        size_t got = 0;
+        check(x_.raw(), hzsdr_covar_push_channels(c_, rows.data(), channels[0].length, out.empty() ? nullptr : out.data(), want, n_ * n_, &got));
+        return out;
+    }
+    // one channel-major block: row i starts i * stride samples into `in`, `n` snapshots per row
+    std::vector<std::complex<float>> PushRows(const void *in, size_t n, size_t stride) {
+        const size_t want = BlocksFor(n);
+        std::vector<std::complex<float>> out(want * n_ * n_);
+        size_t got = 0;
+        check(x_.raw(), hzsdr_covar_push(c_, in, n, stride, out.empty() ? nullptr : out.data(), want, n_ * n_, &got));
+        return out;
+    }
+    std::vector<std::complex<float>> Flush() {
+        std::vector<std::complex<float>> out(n_ * n_);
+        size_t got = 0;
+        check(x_.raw(), hzsdr_covar_flush(c_, out.data(), 1, &got));
+        out.resize(got * n_ * n_);
+        return out;
+    }
+    // -> (snapshots consumed per row, index of the open block, snapshots it holds)
+    std::tuple<uint64_t, uint64_t, size_t> Pending() const {
+        uint64_t c = 0, b = 0;
+        size_t o = 0;
+        check(x_.raw(), hzsdr_covar_pending(c_, &c, &b, &o));
+        return {c, b, o};
+    }
+    // -> (segment length, segments of a workgroup's group, HZSDR_COVAR_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t s = 0, g = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_covar_plan(c_, &s, &g, &f));
+        return {s, g, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_covar_reset(c_)); }
+    size_t Channels() const { return n_; }
+    size_t Block() const { return b_; }
+
+private:
+    const Context &x_;
+    size_t n_, b_;
+    hzsdr_covar *c_ = nullptr;
+};
+
+// The beam scan (include/hzsdr_covar.h) over `weights`, vectors x channels complex64 as hzsdr_beamform_angles makes
+// them: Run maps channels x channels matrices Q, one behind the other, to p[b][g] = Re w_g Q_b w_g^H.
+class Scan {
+public:
+    Scan(const Context &x, size_t channels, const std::vector<std::complex<float>> &weights)
+        : x_(x), n_(channels), g_(channels ? weights.size() / channels : 0) {
+        if (channels == 0 || weights.size() % channels) throw Error(HZSDR_ERR_INVALID_ARGUMENT, "scan: the weights are vectors x channels");
+        check(x_.raw(), hzsdr_scan_create(x_.raw(), channels, weights.data(), g_, &s_));
+    }
+    ~Scan() { if (s_) hzsdr_scan_free(s_); }
+    Scan(const Scan &) = delete;
+    Scan &operator=(const Scan &) = delete;
+    std::vector<float> Run(const std::vector<std::complex<float>> &mats) {
+        const size_t count = mats.size() / (n_ * n_);
+        if (mats.size() != count * n_ * n_) throw Error(HZSDR_ERR_LENGTH_MISMATCH, "scan: matrices are channels x channels");
+        std::vector<float> out(count * g_);
+        check(x_.raw(), hzsdr_scan_run(s_, mats.data(), count, n_ * n_, out.data(), out.size(), g_));
+        return out;
+    }
+    size_t Vectors() const { return g_; }
+
+private:
+    const Context &x_;
+    size_t n_, g_;
+    hzsdr_scan *s_ = nullptr;
+};
+
+}  // namespace array
 }  // namespace hzsdr

@@ -973,3 +973,27 @@ def tuner_rows(r, bank, block=READER_BLOCK):
     tail = bank.flush()
     if tail.shape[-1]:
         yield tail
+
+
+# ---- coherent Readers through the covariance bank (include/hzsdr_covar.h) -----------------------
+
+def covariance_blocks(readers, cov, block=READER_BLOCK):
+    """Read the N `readers` in lockstep, as read_beamform does, in blocks of `block` samples, push them through `cov`
+    (a covar.Covariance of the readers' format on a HOST context) and yield each push's (blocks, N, N) matrices, then
+    the flush last: concatenated, one unnormalised covariance per cov.block snapshots and the open block's.  The
+    stream ends where the first reader ends."""
+    readers = list(readers)
+    if any(r.sample_format() != cov.src_fmt for r in readers):
+        raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+    bufs = [make_samples(cov.src_fmt, block) for _ in readers]
+    while True:
+        try:
+            k = min(r.read(b) for r, b in zip(readers, bufs))
+        except EOF:
+            break
+        out = cov.push([b[:k] for b in bufs])
+        if out.shape[0]:
+            yield out
+    tail = cov.flush()
+    if tail.shape[0]:
+        yield tail
