@@ -1,0 +1,87 @@
+"""What the bank classes share around a call: the source formats, rows of samples in, rows of results out.
+
+A bank of R streams takes (R, n) rows with unit stride along a row and any row pitch (a view of a wider buffer) and
+writes (R, count) rows likewise; one stream takes (n,) and writes (count,).  numpy in a HOST context, torch tensors on
+the context's device in a DEVICE context.  The errors carry the calling class's noun.
+"""
+import numpy as np
+
+from . import _is_torch, FMT_C64, FMT_I8, FMT_I16, FMT_U8, MEM_HOST
+
+# format -> (numpy dtype of an element, bytes of a sample)
+_NP_IN = {FMT_C64: (np.complex64, 8), FMT_U8: (np.uint8, 2), FMT_I8: (np.int8, 2), FMT_I16: (np.int16, 4)}
+
+
+def torch_dtype(dt):
+    import torch
+    return {np.complex64: torch.complex64, np.float32: torch.float32, np.uint8: torch.uint8, np.int8: torch.int8, np.int16: torch.int16}[dt]
+
+
+def device_like(ctx):
+    """What a result made without an input lives like: None (numpy) in a HOST context, else a tensor on its device."""
+    if ctx.memspace == MEM_HOST:
+        return None
+    import torch
+    return torch.empty(0, device=f"cuda:{ctx.device}")
+
+
+def rows_input(x, fmt, rows, noun):
+    """-> (pointer, samples per row, row pitch in samples) of a block of format `fmt`: (rows, n), or (n,) for one row;
+    a trailing (I, Q) axis of 2 for the byte and int16 formats.  rows = None: one row, given as (n,) only."""
+    dt, size = _NP_IN[fmt]
+    if x.dtype != (torch_dtype(dt) if _is_torch(x) else dt):
+        raise ValueError(f"{noun}: samples are not of the source format")
+    if _is_torch(x):
+        strides, ptr, item = tuple(x.stride()), x.data_ptr(), x.element_size()
+    else:
+        item = x.dtype.itemsize
+        strides, ptr = tuple(s // item for s in x.strides), x.ctypes.data
+    shape = tuple(x.shape)
+    per = size // item  # elements per sample: 1 for complex64, 2 (I, Q) otherwise
+    if per == 2:
+        if not shape or shape[-1] != 2 or (strides[-1] != 1 and shape[-1] > 1):
+            raise ValueError(f"{noun}: samples of this format are (..., n, 2)")
+        shape, strides = shape[:-1], strides[:-1]
+    if len(shape) == 1 and rows in (None, 1):
+        shape, strides = (1,) + shape, (0,) + strides
+    elif rows is None:
+        shape = ()
+    rows = rows or 1
+    if len(shape) != 2 or shape[0] != rows:
+        raise ValueError(f"{noun}: input is (n,) for one stream, (streams, n) otherwise")
+    n = int(shape[1])
+    if n == 0:
+        return None, 0, 0
+    if (n > 1 and strides[1] != per) or (rows > 1 and (strides[0] % per or strides[0] // per < n)):
+        raise ValueError(f"{noun}: rows are contiguous, their pitch at least the samples of a row")
+    return ptr, n, int(strides[0] // per) if rows > 1 else n
+
+
+def rows_output(out, count, like, rows, dtype, noun, unit="stream"):
+    """-> (out, pointer, capacity, pitch) of a destination of numpy type `dtype`: (cap,) for one row, (rows, cap) with
+    unit stride along a row and any pitch otherwise.  out = None: a new one of `count` per row, where `like` lives."""
+    if out is None:
+        shape = (count,) if rows == 1 else (rows, count)
+        if _is_torch(like):
+            import torch
+            out = torch.empty(shape, dtype=torch_dtype(dtype), device=like.device)
+        else:
+            out = np.empty(shape, dtype)
+    if _is_torch(out):
+        ok, strides, ptr = out.dtype == torch_dtype(dtype), tuple(out.stride()), out.data_ptr()
+    else:
+        ok, strides, ptr = out.dtype == dtype, tuple(s // np.dtype(dtype).itemsize for s in out.strides), out.ctypes.data
+    if not ok:
+        raise ValueError(f"{noun}: the destination is {np.dtype(dtype).name}")
+    if rows == 1:
+        if out.ndim != 1 or (out.shape[0] > 1 and strides[0] != 1):
+            raise ValueError(f"{noun}: the destination of one {unit} is a contiguous (cap,)")
+        return out, ptr, int(out.shape[0]), int(out.shape[0])
+    if out.ndim != 2 or out.shape[0] != rows or (out.shape[1] > 1 and strides[1] != 1) or strides[0] < out.shape[1]:
+        raise ValueError(f"{noun}: the destination is ({unit}s, cap) with contiguous rows")
+    return out, ptr, int(out.shape[1]), int(strides[0])
+
+
+def cut(out, rows, got):
+    """The written part of a destination of rows_output."""
+    return out[:got] if rows == 1 else out[:, :got]

@@ -26,6 +26,7 @@
 #include "../../include/hzsdr_chanbank.h"
 #include "hz_chanbank_math.h"
 #include "hz_chanbank_plan.h"
+#include "hz_polyphase.h"
 
 struct hzsdr_chanbank {
     hzsdr_ctx *ctx;
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(cp::kThreads) void chanbank_tile_kernel(CbArgs a, f
             for (uint32_t fl = wave * fold_frames + fsub; fl < T; fl += cp::kWaves * fold_frames) {
                 const uint64_t f = f0 + fl;
                 const bool live = f < a.F;
-                const uint32_t w = rot0 + fl * a.D, s = w - cp::chanbank_div(w, a.magic) * a.M;
+                const uint32_t w = rot0 + fl * a.D, s = w - div_by_magic(w, a.magic) * a.M;
                 const uint64_t base = f * a.D;  // the frame's first sample in held ++ in
                 for (uint32_t r = r0; r < a.Mp; r += fold_lanes) {
                     cb::c32 acc{0.0f, 0.0f};
@@ -166,16 +167,6 @@ __global__ __launch_bounds__(cp::kThreads) void chanbank_tile_kernel(CbArgs a, f
     }
 }
 
-// the samples held for the next frame: V[start .. start + cnt) converted
-template <int FMT>
-__global__ __launch_bounds__(kThreads) void chanbank_tail_kernel(CbArgs a, uint64_t start, uint64_t cnt, float2 *__restrict__ tail_out) {
-    using RT = typename Raw<FMT>::t;
-    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * kThreads) {
-        const uint64_t v = start + i;
-        tail_out[i] = v < a.held ? a.tail[v] : Raw<FMT>::cvt(((const RT *)a.in)[v - a.held]);
-    }
-}
-
 template <int FMT, int NC, bool A_LDS>
 static int cb_launch_form(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
     // (tile after tile in a workgroup once the chip is full many times over: A is staged once per workgroup)
@@ -197,29 +188,7 @@ static int cb_launch_fmt(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
 }
 
 static int cb_launch(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
-    switch (c->fmt) {
-    case HZSDR_FMT_C64: return cb_launch_fmt<HZSDR_FMT_C64>(c, a, out);
-    case HZSDR_FMT_U8: return cb_launch_fmt<HZSDR_FMT_U8>(c, a, out);
-    case HZSDR_FMT_I8: return cb_launch_fmt<HZSDR_FMT_I8>(c, a, out);
-    default: return cb_launch_fmt<HZSDR_FMT_I16>(c, a, out);
-    }
-}
-
-template <int FMT>
-static void cb_tail_fmt(hzsdr_chanbank *c, const CbArgs &a, uint64_t start, uint64_t cnt) {
-    hipLaunchKernelGGL(chanbank_tail_kernel<FMT>, dim3(blocks_for(c->ctx, (size_t)cnt)), dim3(kThreads), 0, c->ctx->stream, a, start, cnt,
-                       c->tail[c->tcur ^ 1]);
-}
-
-static int cb_tail(hzsdr_chanbank *c, const CbArgs &a, uint64_t start, uint64_t cnt) {
-    switch (c->fmt) {
-    case HZSDR_FMT_C64: cb_tail_fmt<HZSDR_FMT_C64>(c, a, start, cnt); break;
-    case HZSDR_FMT_U8: cb_tail_fmt<HZSDR_FMT_U8>(c, a, start, cnt); break;
-    case HZSDR_FMT_I8: cb_tail_fmt<HZSDR_FMT_I8>(c, a, start, cnt); break;
-    default: cb_tail_fmt<HZSDR_FMT_I16>(c, a, start, cnt); break;
-    }
-    HZ_HIP(c->ctx, hipGetLastError());
-    return HZSDR_OK;
+    return with_format(c->fmt, [&](auto f) { return cb_launch_fmt<decltype(f)::value>(c, a, out); });
 }
 
 }  // namespace hz
@@ -236,17 +205,12 @@ int hzsdr_chanbank_create(hzsdr_ctx *ctx, int src_format, size_t channels, const
     if (m < cp::kMinChannels || m > cp::kMaxChannels)
         return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the channel count is 2 ... 255 (hzsdr_channelizer.h from 256 on)");
     if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: null taps");
-    if (n_taps == 0 || n_taps % m != 0 || n_taps > cp::kMaxTapsPerChannel * m)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the prototype has P * channels taps, 1 <= P <= 32");
-    if (hop == 0 || hop > m) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the hop is 1 ... channels");
-    if (order != HZSDR_ORDER_ZERO_FIRST && order != HZSDR_ORDER_NEGATIVE_FIRST)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: unknown fft order");
-    if (layout != HZSDR_CHANNELIZER_FRAME_MAJOR && layout != HZSDR_CHANNELIZER_CHANNEL_MAJOR)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: unknown output layout");
+    static_assert(cp::kMaxTapsPerChannel == 32, "check_polyphase_args allows 32 taps per channel");
+    HZ_TRY(check_polyphase_args(ctx, "chanbank", m, n_taps, hop, order, layout));
     HZ_TRY(enter(ctx));
     hzsdr_chanbank *c = new hzsdr_chanbank{ctx, src_format, (uint32_t)m, (uint32_t)n_taps, (uint32_t)hop, order, layout};
     c->g = cp::chanbank_geom(c->M);
-    c->magic = cp::chanbank_magic(c->M);
+    c->magic = div_magic(c->M);
     c->taps_host.assign(taps, taps + n_taps);
     c->W = cp::chanbank_tables(c->M);
     const std::vector<float> A = cp::chanbank_fill_a(c->g, c->W);
@@ -284,42 +248,26 @@ int hzsdr_chanbank_push(hzsdr_chanbank *c, const void *in, size_t n_in, void *ou
     if (!p.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the push is too long");
     const bool chmajor = c->layout == HZSDR_CHANNELIZER_CHANNEL_MAJOR;
     const size_t F = (size_t)p.F, M = c->M;
-    if (out_frames_cap < F) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "chanbank: output buffer too small for the frames of the push");
-    if (chmajor && out_stride < F) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "chanbank: out_stride is below the frames of the push");
-    if (F && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: null output");
+    // (the rows of a push: M channels of F frames, out_stride apart, or -- frame-major -- one run of F * M values)
+    HZ_TRY(check_rows_out(ctx, "chanbank", chmajor ? M : 1, out, out_frames_cap, out_stride, F, 0));
     HZ_TRY(enter(ctx));
     if (n_in == 0) return HZSDR_OK;
     Stage st(ctx);
     const void *din;
-    void *dout = nullptr;
-    size_t dstride = out_stride;
-    bool back2d = false;  // a HOST context's channel-major rows: dense on the device, copied back row by row
+    void *dout;
+    size_t dstride;
     HZ_TRY(st.in(0, in, n_in * (size_t)format_size(c->fmt), &din));
-    if (F) {
-        if (!chmajor) {
-            HZ_TRY(st.out(1, out, F * M * sizeof(float2), &dout));
-        } else if (!st.host() || st.pinned_by_us(out, ((M - 1) * out_stride + F) * sizeof(float2))) {
-            dout = out;
-        } else {
-            HZ_TRY(ensure_slot(ctx, 1, M * F * sizeof(float2)));
-            dout = ctx->slots[1].ptr;
-            dstride = F;
-            back2d = true;
-        }
-    }
+    HZ_TRY(st.out_rows(1, out, chmajor ? M : 1, chmajor ? F : F * M, out_stride, sizeof(float2), &dout, &dstride, true));
     const cp::Geom &g = c->g;
     const CbArgs a{din, c->tail[c->tcur], c->taps, c->a_dev, c->st.held, p.F, (p.F + g.T - 1) / g.T, dstride, c->magic,
                    c->M, g.Mp, c->L / c->M, c->D, c->st.rot, g.steps, g.pitch, g.groups, g.fold_shift, g.b_floats, (uint32_t)g.a_floats,
                    (uint32_t)(c->order == HZSDR_ORDER_NEGATIVE_FIRST)};
     if (F) HZ_TRY(cb_launch(c, a, (float2 *)dout));
     if (p.next.held) {
-        HZ_TRY(cb_tail(c, a, p.V - p.next.held, p.next.held));
+        HZ_TRY(hold_samples(ctx, c->fmt, din, a.tail, a.held, p.V - p.next.held, p.next.held, c->tail[c->tcur ^ 1]));
         c->tcur ^= 1;
     }
     c->st = p.next;
-    if (back2d)
-        HZ_HIP(ctx, hipMemcpy2DAsync(out, out_stride * sizeof(float2), dout, F * sizeof(float2), F * sizeof(float2), M, hipMemcpyDeviceToHost,
-                                     ctx->stream));
     HZ_TRY(st.finish());
     if (frames_written) *frames_written = F;
     return HZSDR_OK;
@@ -367,10 +315,7 @@ int hzsdr_chanbank_reset(hzsdr_chanbank *c) {
 
 int hzsdr_chanbank_free(hzsdr_chanbank *c) {
     if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    for (void *p : {(void *)c->taps, (void *)c->a_dev, (void *)c->tail[0], (void *)c->tail[1]})
-        if (p) (void)hipFree(p);
+    hz::bank_release(c->ctx, {c->taps, c->a_dev, c->tail[0], c->tail[1]});
     delete c;
     return HZSDR_OK;
 }

@@ -9,11 +9,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define HZ_CB_HD __host__ __device__ inline
-#else
-#define HZ_CB_HD inline
-#endif
+#include "hz_plan.h"
 
 namespace hz {
 namespace cb {
@@ -23,14 +19,14 @@ struct c32 {
 };
 
 // one term of the fold: u += g * x, one fused multiply-add per component
-HZ_CB_HD c32 chanbank_fold(c32 acc, float g, c32 x) {
+HZ_HD c32 chanbank_fold(c32 acc, float g, c32 x) {
     acc.re = __builtin_fmaf(g, x.re, acc.re);
     acc.im = __builtin_fmaf(g, x.im, acc.im);
     return acc;
 }
 
 // one r of the product as a chain of four fused steps: THE expression the matrix product must reproduce
-HZ_CB_HD c32 chanbank_term(c32 acc, c32 w, c32 a) {
+HZ_HD c32 chanbank_term(c32 acc, c32 w, c32 a) {
     acc.re = __builtin_fmaf(w.re, a.re, acc.re);
     acc.re = __builtin_fmaf(-w.im, a.im, acc.re);
     acc.im = __builtin_fmaf(w.im, a.re, acc.im);

@@ -47,7 +47,7 @@ struct Step {
 };
 
 // (rot + f D) mod M without a product of the stream length: f is reduced first
-HZ_CB_HD uint32_t chanbank_rot(uint32_t rot, uint64_t f, uint32_t D, uint32_t M) {
+HZ_HD uint32_t chanbank_rot(uint32_t rot, uint64_t f, uint32_t D, uint32_t M) {
     return (uint32_t)((rot + (f % M) * D) % M);  // below 255 + 254 * 255
 }
 
@@ -65,7 +65,7 @@ inline Step chanbank_step(const State &s, uint32_t M, uint32_t L, uint32_t D, ui
 
 // ---- the position map ----------------------------------------------------------------------------------
 // ascending signed frequency for NegativeFirst: position 0 is channel ceil(M / 2), i.e. -floor(M / 2) fs / M
-HZ_CB_HD uint32_t chanbank_pos(uint32_t k, uint32_t M, bool negative_first) {
+HZ_HD uint32_t chanbank_pos(uint32_t k, uint32_t M, bool negative_first) {
     if (!negative_first) return k;
     const uint32_t p = k + M / 2;
     return p >= M ? p - M : p;
@@ -110,22 +110,20 @@ inline Geom chanbank_geom(uint32_t M) {
 // Element (row, j) of A, j = 2 r + c the inner index (c = 0: the factor of u.re, c = 1: of u.im).  Lane l of
 // v_mfma_f32_16x16x4_f32 holds A[l & 15][l >> 4] of a 16 x 4 block: for each 16-row tile and each k-step the 64 lanes'
 // values are contiguous (hz_tuner_plan.h's order).
-HZ_CB_HD size_t chanbank_a_index(uint32_t row, uint32_t j, uint32_t steps) {
+HZ_HD size_t chanbank_a_index(uint32_t row, uint32_t j, uint32_t steps) {
     return ((size_t)(row / 16) * steps + j / 4) * 64 + (j % 4) * 16 + row % 16;
 }
 // Element (j, f) of B, f the frame of the tile: (re, im) of one r side by side, the frames of one r consecutive.  Lane l
 // of a B-operand read holds B[4 s + (l >> 4)][l & 15]: lanes 0 .. 31 (k = 0, 1: re and im of one r) read 32 consecutive
 // floats, lanes 32 .. 63 the 32 of r + 1 -- ds_read_b32 serves the halves apart and its banks are the address modulo
 // 32 floats, so every read is free of conflicts whatever the pitch.
-HZ_CB_HD uint32_t chanbank_b_index(uint32_t j, uint32_t f, uint32_t pitch) { return ((j >> 1) * pitch + f) * 2 + (j & 1u); }
+HZ_HD uint32_t chanbank_b_index(uint32_t j, uint32_t f, uint32_t pitch) { return ((j >> 1) * pitch + f) * 2 + (j & 1u); }
 
-// floor(w / M) for w < 2^16 by multiplication (hz_tuner_plan.h's tuner_div): the fold's rotation of frame fl of a tile is
-// (rot0 + fl D) mod M with rot0 + fl D <= 254 + 63 * 255
-inline uint64_t chanbank_magic(uint32_t M) { return ((uint64_t)1 << 32) / M + 1; }
-HZ_CB_HD uint32_t chanbank_div(uint32_t w, uint64_t magic) { return (uint32_t)((w * magic) >> 32); }
+// floor(w / M) is div_by_magic(w, div_magic(M)) (hz_plan.h): the fold's rotation of frame fl of a tile is
+// (rot0 + fl D) mod M with rot0 + fl D <= 254 + 63 * 255, and M <= 255 keeps w M far below 2^32
 
 // frame offset of fold output r at tap row 0 for a frame whose rotation is s: (r - s) mod M
-HZ_CB_HD uint32_t chanbank_offset(uint32_t r, uint32_t s, uint32_t M) { return r >= s ? r - s : r + M - s; }
+HZ_HD uint32_t chanbank_offset(uint32_t r, uint32_t s, uint32_t M) { return r >= s ? r - s : r + M - s; }
 
 }  // namespace cp
 }  // namespace hz

@@ -144,14 +144,13 @@ __global__ __launch_bounds__(fv::block(M), chan_occupancy(M)) void channelizer_f
     }
 }
 
-// the samples held for the next frame: V[start .. start + cnt) converted
-template <int FMT>
-__global__ __launch_bounds__(kThreads) void channelizer_tail_kernel(ChanArgs a, size_t start, size_t cnt, float2 *__restrict__ tail_out) {
-    using R = typename Raw<FMT>::t;
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < cnt; i += (size_t)gridDim.x * kThreads) {
-        const size_t v = start + i;
-        tail_out[i] = v < a.held ? a.tail[v] : Raw<FMT>::cvt(((const R *)a.in)[v - a.held]);
-    }
+int hold_samples(hzsdr_ctx *ctx, int fmt, const void *in, const float2 *tail, size_t held, size_t start, size_t cnt, float2 *tail_out) {
+    with_format(fmt, [&](auto f) {
+        hipLaunchKernelGGL(held_samples_kernel<decltype(f)::value>, dim3(blocks_for(ctx, cnt)), dim3(kThreads), 0, ctx->stream, in, tail, held,
+                           start, cnt, tail_out);
+    });
+    HZ_HIP(ctx, hipGetLastError());
+    return HZSDR_OK;
 }
 
 template <int M, int FMT>
@@ -181,14 +180,6 @@ static int chan_launch_fmt(hzsdr_channelizer *c, const ChanArgs &a, float2 *out,
     }
 }
 
-template <int FMT>
-static int chan_tail(hzsdr_channelizer *c, const ChanArgs &a, size_t start, size_t cnt) {
-    hipLaunchKernelGGL(channelizer_tail_kernel<FMT>, dim3(blocks_for(c->ctx, cnt)), dim3(kThreads), 0, c->ctx->stream, a, start, cnt,
-                       c->tail[c->tcur ^ 1]);
-    HZ_HIP(c->ctx, hipGetLastError());
-    return HZSDR_OK;
-}
-
 }  // namespace hz
 
 extern "C" {
@@ -203,13 +194,7 @@ int hzsdr_channelizer_create(hzsdr_ctx *ctx, int src_format, size_t channels, co
     if (m < 256 || m > 8192 || (m & (m - 1)) != 0)
         return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: the channel count is a power of two, 256 ... 8192");
     if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: null taps");
-    if (n_taps == 0 || n_taps % m != 0 || n_taps > 32 * m)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: the prototype has P * channels taps, 1 <= P <= 32");
-    if (hop == 0 || hop > m) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: the hop is 1 ... channels");
-    if (order != HZSDR_ORDER_ZERO_FIRST && order != HZSDR_ORDER_NEGATIVE_FIRST)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: unknown fft order");
-    if (layout != HZSDR_CHANNELIZER_FRAME_MAJOR && layout != HZSDR_CHANNELIZER_CHANNEL_MAJOR)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: unknown output layout");
+    HZ_TRY(check_polyphase_args(ctx, "channelizer", m, n_taps, hop, order, layout));
     HZ_TRY(enter(ctx));
     hzsdr_channelizer *c = new hzsdr_channelizer{ctx, src_format, m, n_taps, hop, order, layout};
     auto undo = [&](int rc) {
@@ -242,55 +227,26 @@ int hzsdr_channelizer_push(hzsdr_channelizer *c, const void *in, size_t n_in, vo
     if (n_in && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: null input");
     const ChanStep p = chan_step(c, n_in);
     const bool chmajor = c->layout == HZSDR_CHANNELIZER_CHANNEL_MAJOR;
-    if (out_frames_cap < p.F) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "channelizer: output buffer too small for the frames of the push");
-    if (chmajor && out_stride < p.F) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "channelizer: out_stride is below the frames of the push");
-    if (p.F && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: null output");
+    const size_t M = c->m;
+    // (the rows of a push: M channels of F frames, out_stride apart, or -- frame-major -- one run of F * M values)
+    HZ_TRY(check_rows_out(ctx, "channelizer", chmajor ? M : 1, out, out_frames_cap, out_stride, p.F, 0));
     HZ_TRY(enter(ctx));
     if (n_in == 0) return HZSDR_OK;
-    const size_t fs = (size_t)format_size(c->fmt), M = c->m;
     Stage st(ctx);
     const void *din;
-    void *dout = nullptr;
-    size_t dstride = out_stride;
-    bool back2d = false;  // a HOST context's channel-major rows: dense on the device, copied back row by row
-    HZ_TRY(st.in(0, in, n_in * fs, &din));
-    if (p.F) {
-        if (!chmajor) {
-            HZ_TRY(st.out(1, out, p.F * M * sizeof(float2), &dout));
-        } else if (!st.host() || st.pinned_by_us(out, ((M - 1) * out_stride + p.F) * sizeof(float2))) {
-            dout = out;
-        } else {
-            HZ_TRY(ensure_slot(ctx, 1, M * p.F * sizeof(float2)));
-            dout = ctx->slots[1].ptr;
-            dstride = p.F;
-            back2d = true;
-        }
-    }
+    void *dout;
+    size_t dstride;
+    HZ_TRY(st.in(0, in, n_in * (size_t)format_size(c->fmt), &din));
+    HZ_TRY(st.out_rows(1, out, chmajor ? M : 1, chmajor ? p.F : p.F * M, out_stride, sizeof(float2), &dout, &dstride, true));
     const ChanArgs a{din, c->tail[c->tcur], c->held, c->hop, p.F, c->taps, c->tabs.fwd, (unsigned)c->rot, (unsigned)(c->ntaps / M)};
-    if (p.F) {
-        switch (c->fmt) {
-        case HZSDR_FMT_C64: HZ_TRY(chan_launch_fmt<HZSDR_FMT_C64>(c, a, (float2 *)dout, dstride)); break;
-        case HZSDR_FMT_U8: HZ_TRY(chan_launch_fmt<HZSDR_FMT_U8>(c, a, (float2 *)dout, dstride)); break;
-        case HZSDR_FMT_I8: HZ_TRY(chan_launch_fmt<HZSDR_FMT_I8>(c, a, (float2 *)dout, dstride)); break;
-        default: HZ_TRY(chan_launch_fmt<HZSDR_FMT_I16>(c, a, (float2 *)dout, dstride)); break;
-        }
-    }
+    if (p.F) HZ_TRY(with_format(c->fmt, [&](auto f) { return chan_launch_fmt<decltype(f)::value>(c, a, (float2 *)dout, dstride); }));
     if (p.new_held) {
-        const size_t start = p.V - p.new_held;
-        switch (c->fmt) {
-        case HZSDR_FMT_C64: HZ_TRY(chan_tail<HZSDR_FMT_C64>(c, a, start, p.new_held)); break;
-        case HZSDR_FMT_U8: HZ_TRY(chan_tail<HZSDR_FMT_U8>(c, a, start, p.new_held)); break;
-        case HZSDR_FMT_I8: HZ_TRY(chan_tail<HZSDR_FMT_I8>(c, a, start, p.new_held)); break;
-        default: HZ_TRY(chan_tail<HZSDR_FMT_I16>(c, a, start, p.new_held)); break;
-        }
+        HZ_TRY(hold_samples(ctx, c->fmt, din, a.tail, a.held, p.V - p.new_held, p.new_held, c->tail[c->tcur ^ 1]));
         c->tcur ^= 1;
     }
     c->held = p.new_held;
     c->rot = (c->rot + (p.F & (M - 1)) * c->hop) & (M - 1);  // (running value mod M: no product of stream length)
     c->frame += p.F;
-    if (back2d)
-        HZ_HIP(ctx, hipMemcpy2DAsync(out, out_stride * sizeof(float2), dout, p.F * sizeof(float2), p.F * sizeof(float2), M,
-                                     hipMemcpyDeviceToHost, ctx->stream));
     HZ_TRY(st.finish());
     if (frames_written) *frames_written = p.F;
     return HZSDR_OK;
@@ -313,10 +269,7 @@ int hzsdr_channelizer_reset(hzsdr_channelizer *c) {
 
 int hzsdr_channelizer_free(hzsdr_channelizer *c) {
     if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    for (void *p : {(void *)c->taps, (void *)c->tail[0], (void *)c->tail[1]})
-        if (p) (void)hipFree(p);
+    hz::bank_release(c->ctx, {c->taps, c->tail[0], c->tail[1]});
     delete c;
     return HZSDR_OK;
 }

@@ -7,8 +7,11 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
+#include <initializer_list>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hzsdr.h"
@@ -90,6 +93,18 @@ inline int format_size(int f) {
     }
 }
 
+// f(std::integral_constant<int, FMT>{}) for the sample format `fmt` (one that format_size accepts): where a format
+// known at run time picks a template instantiation, as in
+//     with_format(fmt, [&](auto f) { return launch<decltype(f)::value>(args); });
+template <class F> inline auto with_format(int fmt, F &&f) {
+    switch (fmt) {
+    case HZSDR_FMT_C64: return f(std::integral_constant<int, HZSDR_FMT_C64>{});
+    case HZSDR_FMT_U8: return f(std::integral_constant<int, HZSDR_FMT_U8>{});
+    case HZSDR_FMT_I8: return f(std::integral_constant<int, HZSDR_FMT_I8>{});
+    default: return f(std::integral_constant<int, HZSDR_FMT_I16>{});
+    }
+}
+
 // Select the context's device on the calling thread (cgo: goroutines migrate
 // between OS threads and HIP's current device is thread-local).
 inline int enter(hzsdr_ctx *ctx) {
@@ -135,6 +150,8 @@ struct Stage {
         const void *dev;
         size_t bytes;
         bool cpu;  // copy back with memcpy after the stream wait (staging area) instead of a DMA
+        // out_rows' 2-D copy: `rows` rows of `bytes` each, dense at dev, host_pitch bytes apart at host (rows == 0: one run)
+        size_t rows, host_pitch;
     };
     std::vector<Back> backs;
     size_t used = 0;  // bytes of the staging area handed out so far
@@ -150,8 +167,46 @@ struct Stage {
     int inout(int slot, void *p, size_t bytes, void **dev);
     // like out(), but uploads the current contents first (partial writers)
     int out_preserve(int slot, void *p, size_t bytes, void **dev) { return inout(slot, p, bytes, dev); }
+    // Rows: `rows` rows of `count` elements of `size` bytes, `pitch` elements from one row's start to the next.  *dev and
+    // *dev_pitch are what the kernel gets.  One row, or pitch == count: in() / out() over rows * count elements, with
+    // all three of their routes.  A DEVICE context, or a span inside a range the library pinned: the caller's pointer
+    // and pitch.  Otherwise (a HOST context's rows with gaps) a dense copy in the slot, brought in by one 2-D copy
+    // (in_rows) or recorded in `backs` for finish() to copy back (out_rows): the gaps are neither read nor written.
+    // No rows or count == 0: nothing.  The arithmetic is hz_rows.h; a span that does not fit size_t is refused.
+    int in_rows(int slot, const void *p, size_t rows, size_t count, size_t pitch, size_t size, const void **dev, size_t *dev_pitch);
+    // keep_rows: several rows with no gap between them travel as rows with a gap do, not through out() -- the channelizer's
+    // and the channel bank's channel-major rows, whose pushes over the staging limit measured faster that way
+    int out_rows(int slot, void *p, size_t rows, size_t count, size_t pitch, size_t size, void **dev, size_t *dev_pitch, bool keep_rows = false);
     // enqueue the copies back and, for HOST contexts, wait for them
     int finish();
 };
+
+// ---- what the bank objects (spectrum, channelizer, synthesizer, resampler, demodulator, tuner, channel bank,
+// covariance) share on the host ----
+
+// The checks of a call that writes `count` outputs into each of `rows` rows, before anything is launched; tile: outputs
+// per workgroup of the kernel whose grid the count sets (0: no such limit).
+inline int check_rows_out(hzsdr_ctx *ctx, const char *who, size_t rows, const void *out, size_t cap, size_t stride, uint64_t count, uint32_t tile) {
+    const std::string w = std::string(who) + ": ";
+    if (cap < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, w + "output buffer too small for the outputs of the call");
+    if (rows > 1 && stride < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, w + "out_stride is below the outputs of the call");
+    if (count && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, w + "null output");
+    if (tile && (count + tile - 1) / tile > 0x7fffffffull) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, w + "too many outputs for one call");
+    return HZSDR_OK;
+}
+
+inline int check_taps_finite(hzsdr_ctx *ctx, const char *who, const float *taps, size_t n) {
+    for (size_t k = 0; k < n; k++)
+        if (!std::isfinite(taps[k])) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string(who) + ": a tap is not finite");
+    return HZSDR_OK;
+}
+
+// the head of every *_free: behind whatever still runs on the context's stream, the object's device buffers go
+inline void bank_release(hzsdr_ctx *ctx, std::initializer_list<void *> ptrs) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+}
 
 }  // namespace hz

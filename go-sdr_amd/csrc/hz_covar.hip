@@ -279,12 +279,7 @@ static int cv_launch_fmt(hzsdr_covar *c, const CvArgs &a) {
 }
 
 static int cv_launch(hzsdr_covar *c, const CvArgs &a) {
-    switch (c->fmt) {
-    case HZSDR_FMT_C64: return cv_launch_fmt<HZSDR_FMT_C64>(c, a);
-    case HZSDR_FMT_U8: return cv_launch_fmt<HZSDR_FMT_U8>(c, a);
-    case HZSDR_FMT_I8: return cv_launch_fmt<HZSDR_FMT_I8>(c, a);
-    default: return cv_launch_fmt<HZSDR_FMT_I16>(c, a);
-    }
+    return with_format(c->fmt, [&](auto f) { return cv_launch_fmt<decltype(f)::value>(c, a); });
 }
 
 // the node scratch for `nodes` nodes, grow-only
@@ -494,10 +489,7 @@ int hzsdr_covar_reset(hzsdr_covar *c) {
 
 int hzsdr_covar_free(hzsdr_covar *c) {
     if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    for (void *p : {(void *)c->tail[0], (void *)c->tail[1], (void *)c->stack[0], (void *)c->stack[1], (void *)c->nodes})
-        if (p) (void)hipFree(p);
+    hz::bank_release(c->ctx, {c->tail[0], c->tail[1], c->stack[0], c->stack[1], c->nodes});
     delete c;
     return HZSDR_OK;
 }
@@ -553,9 +545,7 @@ int hzsdr_scan_run(hzsdr_scan *s, const void *mats, size_t n_mats, size_t mat_st
 
 int hzsdr_scan_free(hzsdr_scan *s) {
     if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    if (s->w) (void)hipFree(s->w);
+    hz::bank_release(s->ctx, {s->w});
     delete s;
     return HZSDR_OK;
 }

@@ -45,21 +45,21 @@ constexpr uint64_t kRoundSegments = 8192;
 
 // ---- the tile --------------------------------------------------------------------------------------------
 // rows of V: 2N rounded up to whole accumulator tiles
-HZ_CV_HD uint32_t covar_rows(uint32_t N) { return N <= 8 ? 16u : 32u; }
+HZ_HD uint32_t covar_rows(uint32_t N) { return N <= 8 ? 16u : 32u; }
 // accumulator tiles: (0,0) alone, or (0,0), (0,1), (1,1)
-HZ_CV_HD uint32_t covar_tiles(uint32_t N) { return N <= 8 ? 1u : 3u; }
-HZ_CV_HD uint32_t covar_node_floats(uint32_t N) { return covar_tiles(N) * kTile; }
-HZ_CV_HD uint32_t covar_lds_bytes(uint32_t N) { return covar_rows(N) * kPitch * 4u; }
+HZ_HD uint32_t covar_tiles(uint32_t N) { return N <= 8 ? 1u : 3u; }
+HZ_HD uint32_t covar_node_floats(uint32_t N) { return covar_tiles(N) * kTile; }
+HZ_HD uint32_t covar_lds_bytes(uint32_t N) { return covar_rows(N) * kPitch * 4u; }
 // Element (row, n) of the staged chunk.  Lane l of the matrix instruction's A operand holds V[l & 15][4 t + (l >> 4)],
 // and B = V^T wants the same element: one register serves both.  ds_read_b32 serves lanes 0 .. 31 and 32 .. 63 apart and
 // its banks are the address modulo 32 floats: with a pitch of 2 mod 32 the 16 rows x 2 k-slots of a half wave fall on 32
 // different banks.  The staging stores are consecutive floats of one row.
-HZ_CV_HD uint32_t covar_lds_index(uint32_t row, uint32_t n) { return row * kPitch + n; }
+HZ_HD uint32_t covar_lds_index(uint32_t row, uint32_t n) { return row * kPitch + n; }
 // Entry (p, q) of the Gram matrix inside a node.  An accumulator tile in D order is lane * 4 + reg with column lane & 15
 // and row (lane >> 4) * 4 + reg; tile 0 is rows and columns 0 .. 15, tile 1 rows 0 .. 15 of columns 16 .. 31, tile 2 rows
 // and columns 16 .. 31.  The lower tile is never computed: G is symmetric bit for bit (a product commutes), so (p, q)
 // there is read as (q, p).
-HZ_CV_HD uint32_t covar_node_index(uint32_t p, uint32_t q) {
+HZ_HD uint32_t covar_node_index(uint32_t p, uint32_t q) {
     if ((p >> 4) > (q >> 4)) {
         const uint32_t s = p;
         p = q, q = s;
@@ -69,8 +69,8 @@ HZ_CV_HD uint32_t covar_node_index(uint32_t p, uint32_t q) {
     return tile * kTile + lane * 4u + (p & 3u);
 }
 // the rows of V a tile's A and B operands come from: tile -> (first row of A, first row of B)
-HZ_CV_HD uint32_t covar_tile_a(uint32_t tile) { return tile == 2 ? 16u : 0u; }
-HZ_CV_HD uint32_t covar_tile_b(uint32_t tile) { return tile == 0 ? 0u : 16u; }
+HZ_HD uint32_t covar_tile_a(uint32_t tile) { return tile == 2 ? 16u : 0u; }
+HZ_HD uint32_t covar_tile_b(uint32_t tile) { return tile == 0 ? 0u : 16u; }
 
 // ---- the counts --------------------------------------------------------------------------------------------
 struct State {
@@ -108,7 +108,7 @@ struct Step {
     State next;
 };
 
-HZ_CV_HD uint32_t covar_block_segments(uint32_t B) { return (B + kSeg - 1) / kSeg; }
+HZ_HD uint32_t covar_block_segments(uint32_t B) { return (B + kSeg - 1) / kSeg; }
 
 inline void covar_deal(Region &r) {
     const uint32_t up = (r.seg0 + kGroup - 1) / kGroup * kGroup;
@@ -190,7 +190,7 @@ inline Step covar_flush(const State &s) {
 struct Item {
     uint32_t seg, count, level;
 };
-HZ_CV_HD Item covar_item(const Region &r, uint32_t it) {
+HZ_HD Item covar_item(const Region &r, uint32_t it) {
     if (it < r.head) return Item{r.seg0 + it, 1u, 0u};
     it -= r.head;
     if (it < r.groups) return Item{r.seg0 + r.head + it * kGroup, kGroup, kGroupLog};
@@ -198,13 +198,13 @@ HZ_CV_HD Item covar_item(const Region &r, uint32_t it) {
     return Item{r.seg0 + r.head + r.groups * kGroup + it, 1u, 0u};
 }
 // snapshots of segment `seg` that are present in a block of region r
-HZ_CV_HD uint32_t covar_seg_len(const Region &r, uint32_t seg) {
+HZ_HD uint32_t covar_seg_len(const Region &r, uint32_t seg) {
     const uint32_t at = seg * kSeg;
     if (at >= r.limit) return 0;
     return r.limit - at < kSeg ? r.limit - at : kSeg;
 }
 // position in held ++ in of the first snapshot of segment `seg` of block `blk` of region r
-HZ_CV_HD uint64_t covar_seg_start(const Region &r, uint64_t blk, uint32_t seg, uint32_t B) {
+HZ_HD uint64_t covar_seg_start(const Region &r, uint64_t blk, uint32_t seg, uint32_t B) {
     return r.v0 + blk * B + (uint64_t)(seg - r.seg0) * kSeg;
 }
 
@@ -213,7 +213,7 @@ HZ_CV_HD uint64_t covar_seg_start(const Region &r, uint64_t blk, uint32_t seg, u
 // where count is a multiple of 2^level.
 // (`stack` is anything indexed by level: an array, or a lane's column of LDS)
 template <class S, class T, class Add>
-HZ_CV_HD void covar_counter_push(S &&stack, uint32_t &count, T v, uint32_t level, Add add) {
+HZ_HD void covar_counter_push(S &&stack, uint32_t &count, T v, uint32_t level, Add add) {
     uint32_t c = count >> level, l = level;
     while (c & 1u) {
         v = add(stack[l], v);
@@ -224,7 +224,7 @@ HZ_CV_HD void covar_counter_push(S &&stack, uint32_t &count, T v, uint32_t level
 }
 // the remainder collapses from the smallest group upward; count > 0
 template <class S, class Add>
-HZ_CV_HD auto covar_counter_collapse(S &&stack, uint32_t count, Add add) {
+HZ_HD auto covar_counter_collapse(S &&stack, uint32_t count, Add add) {
     uint32_t l = 0;
     while (!((count >> l) & 1u)) l++;
     auto acc = stack[l];
@@ -233,7 +233,7 @@ HZ_CV_HD auto covar_counter_collapse(S &&stack, uint32_t count, Add add) {
     return acc;
 }
 // the walker may take kWalk group nodes at once where the counter is aligned to them
-HZ_CV_HD bool covar_walk_many(uint32_t count, uint32_t level, uint32_t left) {
+HZ_HD bool covar_walk_many(uint32_t count, uint32_t level, uint32_t left) {
     return level == kGroupLog && left >= kWalk && (count & ((kGroup * kWalk) - 1u)) == 0;
 }
 

@@ -1,5 +1,6 @@
 // hz_ctx.hip -- context lifecycle, memory, staging (C-ABI: library / context section).
 #include "hz_common.h"
+#include "hz_rows.h"
 
 #include <mutex>
 #include <set>
@@ -126,11 +127,50 @@ int Stage::inout(int slot, void *p, size_t bytes, void **dev) {
     return HZSDR_OK;
 }
 
+int Stage::in_rows(int slot, const void *p, size_t rows, size_t count, size_t pitch, size_t size, const void **dev, size_t *dev_pitch) {
+    const rows::Span sp = rows::span(rows, count, pitch, size);
+    if (!sp.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "rows: rows, pitch and count do not fit the address space");
+    *dev = p;
+    *dev_pitch = pitch;
+    switch (rows::route(host(), rows, count, pitch, host() && pinned_by_us(p, sp.bytes))) {
+    case rows::kDense: return in(slot, p, sp.dense_bytes, dev);
+    case rows::kCopy2D:
+        HZ_TRY(ensure_slot(ctx, slot, sp.dense_bytes));
+        HZ_HIP(ctx, hipMemcpy2DAsync(ctx->slots[slot].ptr, count * size, p, pitch * size, count * size, rows, hipMemcpyHostToDevice, ctx->stream));
+        *dev = ctx->slots[slot].ptr;
+        *dev_pitch = count;
+        return HZSDR_OK;
+    default: return HZSDR_OK;
+    }
+}
+
+int Stage::out_rows(int slot, void *p, size_t rows, size_t count, size_t pitch, size_t size, void **dev, size_t *dev_pitch, bool keep_rows) {
+    const rows::Span sp = rows::span(rows, count, pitch, size);
+    if (!sp.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "rows: rows, pitch and count do not fit the address space");
+    *dev = p;
+    *dev_pitch = pitch;
+    switch (rows::route(host(), rows, count, pitch, host() && pinned_by_us(p, sp.bytes), !keep_rows)) {
+    case rows::kDense: return out(slot, p, sp.dense_bytes, dev);
+    case rows::kCopy2D:
+        HZ_TRY(ensure_slot(ctx, slot, sp.dense_bytes));
+        *dev = ctx->slots[slot].ptr;
+        *dev_pitch = count;
+        backs.push_back({p, *dev, count * size, false, rows, pitch * size});
+        return HZSDR_OK;
+    default: return HZSDR_OK;
+    }
+}
+
 int Stage::finish() {
     HZ_HIP(ctx, hipGetLastError());
     if (!host()) return HZSDR_OK;
-    for (auto &b : backs)
-        if (!b.cpu) HZ_HIP(ctx, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    for (auto &b : backs) {
+        if (b.cpu) continue;
+        if (b.rows)
+            HZ_HIP(ctx, hipMemcpy2DAsync(b.host, b.host_pitch, b.dev, b.bytes, b.bytes, b.rows, hipMemcpyDeviceToHost, ctx->stream));
+        else
+            HZ_HIP(ctx, hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (auto &b : backs)
         if (b.cpu) memcpy(b.host, b.dev, b.bytes);

@@ -6,7 +6,7 @@
 // One kernel.  A workgroup of 256 lanes takes one tile of T consecutive outputs of one row (the row is the grid's second
 // dimension).  It computes the tile's (T - 1) D + Q detector values ONCE, from (T - 1) D + Q + 1 raw samples converted
 // in the loads -- from the held tail below the push's first sample, +0 at and past its last -- and stores each as one
-// float in LDS, transposed (dp::demod_slot: value w in row w mod D), so that the lanes of a read, D values apart, sit
+// float in LDS, transposed (transposed_slot: value w in row w mod D), so that the lanes of a read, D values apart, sit
 // on consecutive banks.  A lane then owns T / 256 outputs, 256 apart, as independent fma chains; from tap to tap the
 // slot moves by a step that is the same for every lane (scalar work), and the chains of a lane are a constant 256
 // floats apart (an immediate offset).  h[q] is read from a wave-uniform address: scalar registers, never lane by lane.
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(dp::kThreads) void demod_tile_kernel(DemArgs a, flo
             const dm::c32 x0 = a.mode == dm::kFm ? src.at(w) : dm::c32{0.0f, 0.0f};
             d = dm::demod_detect(a.mode, x1, x0);
         }
-        const uint32_t j = dp::demod_div(w, a.magic);
+        const uint32_t j = div_by_magic(w, a.magic);
         win[(w - j * a.D) * a.J + j] = d;
     }
     __syncthreads();
@@ -176,27 +176,14 @@ static int dem_launch_fmt(hzsdr_demod *d, const DemArgs &a, float *out) {
 }
 
 static int dem_launch(hzsdr_demod *d, const DemArgs &a, float *out) {
-    switch (d->fmt) {
-    case HZSDR_FMT_C64: return dem_launch_fmt<HZSDR_FMT_C64>(d, a, out);
-    case HZSDR_FMT_U8: return dem_launch_fmt<HZSDR_FMT_U8>(d, a, out);
-    case HZSDR_FMT_I8: return dem_launch_fmt<HZSDR_FMT_I8>(d, a, out);
-    default: return dem_launch_fmt<HZSDR_FMT_I16>(d, a, out);
-    }
-}
-
-template <int FMT>
-static void dem_tail_fmt(hzsdr_demod *d, const DemArgs &a) {
-    const dim3 grid((d->Q + dp::kThreads - 1) / dp::kThreads, d->R);
-    hipLaunchKernelGGL(demod_tail_kernel<FMT>, grid, dim3(dp::kThreads), 0, d->ctx->stream, a, d->tail[d->tcur ^ 1]);
+    return with_format(d->fmt, [&](auto f) { return dem_launch_fmt<decltype(f)::value>(d, a, out); });
 }
 
 static int dem_tail(hzsdr_demod *d, const DemArgs &a) {
-    switch (d->fmt) {
-    case HZSDR_FMT_C64: dem_tail_fmt<HZSDR_FMT_C64>(d, a); break;
-    case HZSDR_FMT_U8: dem_tail_fmt<HZSDR_FMT_U8>(d, a); break;
-    case HZSDR_FMT_I8: dem_tail_fmt<HZSDR_FMT_I8>(d, a); break;
-    default: dem_tail_fmt<HZSDR_FMT_I16>(d, a); break;
-    }
+    const dim3 grid((d->Q + dp::kThreads - 1) / dp::kThreads, d->R);
+    with_format(d->fmt, [&](auto f) {
+        hipLaunchKernelGGL(demod_tail_kernel<decltype(f)::value>, grid, dim3(dp::kThreads), 0, d->ctx->stream, a, d->tail[d->tcur ^ 1]);
+    });
     HZ_HIP(d->ctx, hipGetLastError());
     return HZSDR_OK;
 }
@@ -205,48 +192,6 @@ static size_t dem_tail_bytes(const hzsdr_demod *d) { return (size_t)d->R * d->Q 
 
 static DemArgs dem_args(const hzsdr_demod *d, const void *in, size_t in_stride, uint64_t n_in, uint64_t count, size_t out_stride) {
     return DemArgs{in, in_stride, d->tail[d->tcur], d->h, n_in, count, out_stride, d->magic, d->D, d->Q, d->g.J, d->st.rel, d->g.row0, d->g.slot0, d->mode};
-}
-
-// The destination of `count` outputs per row.  A DEVICE context, one row, dense rows or rows inside memory the library
-// pinned: the caller's buffer.  Otherwise a HOST context's pitched rows are written densely to a device slot and
-// copied back row by row (dem_back).
-struct DemOut {
-    void *dev = nullptr;
-    size_t stride = 0;
-    bool back2d = false;
-};
-
-static int dem_out(hzsdr_demod *d, Stage &st, void *out, size_t out_stride, size_t count, DemOut *o) {
-    const size_t R = d->R;
-    o->stride = out_stride;
-    if (count == 0) return HZSDR_OK;
-    if (R == 1 || out_stride == count) return st.out(1, out, R * count * sizeof(float), &o->dev);
-    if (!st.host() || st.pinned_by_us(out, ((R - 1) * out_stride + count) * sizeof(float))) {
-        o->dev = out;
-        return HZSDR_OK;
-    }
-    HZ_TRY(ensure_slot(d->ctx, 1, R * count * sizeof(float)));
-    o->dev = d->ctx->slots[1].ptr;
-    o->stride = count;
-    o->back2d = true;
-    return HZSDR_OK;
-}
-
-static int dem_back(hzsdr_demod *d, const DemOut &o, void *out, size_t out_stride, size_t count) {
-    if (o.back2d)
-        HZ_HIP(d->ctx, hipMemcpy2DAsync(out, out_stride * sizeof(float), o.dev, count * sizeof(float), count * sizeof(float), d->R,
-                                        hipMemcpyDeviceToHost, d->ctx->stream));
-    return HZSDR_OK;
-}
-
-// the checks of a push or flush that writes `count` outputs per row, before anything is launched
-static int dem_check_out(hzsdr_demod *d, const void *out, size_t out_cap, size_t out_stride, uint64_t count) {
-    hzsdr_ctx *ctx = d->ctx;
-    if (out_cap < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "demod: output buffer too small for the outputs of the call");
-    if (d->R > 1 && out_stride < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "demod: out_stride is below the outputs of the call");
-    if (count && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: null output");
-    if ((count + d->g.T - 1) / d->g.T > 0x7fffffffull) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: too many outputs for one call");
-    return HZSDR_OK;
 }
 
 }  // namespace hz
@@ -264,12 +209,11 @@ int hzsdr_demod_create(hzsdr_ctx *ctx, int src_format, int mode, size_t down, co
     if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: null taps");
     if (n_taps == 0 || n_taps > dp::kMaxTaps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: 1 ... 1024 taps");
     if (streams == 0 || streams > dp::kMaxStreams) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: 1 ... 8192 streams");
-    for (size_t k = 0; k < n_taps; k++)
-        if (!std::isfinite(taps[k])) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: a tap is not finite");
+    HZ_TRY(check_taps_finite(ctx, "demod", taps, n_taps));
     HZ_TRY(enter(ctx));
     hzsdr_demod *d = new hzsdr_demod{ctx, src_format, mode, (uint32_t)down, (uint32_t)n_taps, (uint32_t)streams};
     d->g = dp::demod_geom(d->D, d->Q);
-    d->magic = dp::demod_magic(d->D);
+    d->magic = div_magic(d->D);
     auto undo = [&](int rc) {
         hzsdr_demod_free(d);
         return rc;
@@ -305,30 +249,20 @@ int hzsdr_demod_push(hzsdr_demod *d, const void *in, size_t n_in, size_t in_stri
     if (R > 1 && in_stride < n_in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: in_stride is below the samples of the push");
     const dp::Step p = dp::demod_step(d->st, d->D, d->Q, n_in);
     if (!p.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "demod: the push is too long");
-    HZ_TRY(dem_check_out(d, out, out_cap, out_stride, p.count));
+    HZ_TRY(check_rows_out(ctx, "demod", R, out, out_cap, out_stride, p.count, d->g.T));
     HZ_TRY(enter(ctx));
     if (n_in == 0) return HZSDR_OK;
     Stage st(ctx);
     const void *din;
-    size_t dstride = in_stride;
-    if (R == 1 || in_stride == n_in) {
-        HZ_TRY(st.in(0, in, R * n_in * fs, &din));
-    } else if (!st.host() || st.pinned_by_us(in, ((R - 1) * in_stride + n_in) * fs)) {
-        din = in;
-    } else {  // a HOST context's rows with a pitch: dense on the device, copied in row by row
-        HZ_TRY(ensure_slot(ctx, 0, R * n_in * fs));
-        HZ_HIP(ctx, hipMemcpy2DAsync(ctx->slots[0].ptr, n_in * fs, in, in_stride * fs, n_in * fs, R, hipMemcpyHostToDevice, ctx->stream));
-        din = ctx->slots[0].ptr;
-        dstride = n_in;
-    }
-    DemOut o;
-    HZ_TRY(dem_out(d, st, out, out_stride, (size_t)p.count, &o));
-    const DemArgs a = dem_args(d, din, dstride, n_in, p.count, o.stride);
-    if (p.count) HZ_TRY(dem_launch(d, a, (float *)o.dev));
+    void *dout;
+    size_t dstride, ostride;
+    HZ_TRY(st.in_rows(0, in, R, n_in, in_stride, fs, &din, &dstride));
+    HZ_TRY(st.out_rows(1, out, R, (size_t)p.count, out_stride, sizeof(float), &dout, &ostride));
+    const DemArgs a = dem_args(d, din, dstride, n_in, p.count, ostride);
+    if (p.count) HZ_TRY(dem_launch(d, a, (float *)dout));
     HZ_TRY(dem_tail(d, a));
     d->tcur ^= 1;
     d->st = p.next;
-    HZ_TRY(dem_back(d, o, out, out_stride, (size_t)p.count));
     HZ_TRY(st.finish());
     if (written) *written = (size_t)p.count;
     return HZSDR_OK;
@@ -340,15 +274,15 @@ int hzsdr_demod_flush(hzsdr_demod *d, float *out, size_t out_cap, size_t out_str
     if (!d) return HZSDR_ERR_INVALID_ARGUMENT;
     hzsdr_ctx *ctx = d->ctx;
     const uint64_t count = dp::demod_flush_count(d->st, d->D, d->Q);
-    HZ_TRY(dem_check_out(d, out, out_cap, out_stride, count));
+    HZ_TRY(check_rows_out(ctx, "demod", d->R, out, out_cap, out_stride, count, d->g.T));
     HZ_TRY(enter(ctx));
     if (count) {
         Stage st(ctx);
-        DemOut o;
-        HZ_TRY(dem_out(d, st, out, out_stride, (size_t)count, &o));
+        void *dout;
+        size_t ostride;
+        HZ_TRY(st.out_rows(1, out, d->R, (size_t)count, out_stride, sizeof(float), &dout, &ostride));
         // (a push of no samples: every detector value at or past the push's first sample reads as zero)
-        HZ_TRY(dem_launch(d, dem_args(d, nullptr, 0, 0, count, o.stride), (float *)o.dev));
-        HZ_TRY(dem_back(d, o, out, out_stride, (size_t)count));
+        HZ_TRY(dem_launch(d, dem_args(d, nullptr, 0, 0, count, ostride), (float *)dout));
         HZ_TRY(st.finish());
     }
     HZ_TRY(hzsdr_demod_reset(d));
@@ -383,10 +317,7 @@ int hzsdr_demod_reset(hzsdr_demod *d) {
 
 int hzsdr_demod_free(hzsdr_demod *d) {
     if (!d) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(d->ctx->device);
-    (void)hipStreamSynchronize(d->ctx->stream);
-    for (void *p : {(void *)d->h, (void *)d->tail[0], (void *)d->tail[1]})
-        if (p) (void)hipFree(p);
+    hz::bank_release(d->ctx, {d->h, d->tail[0], d->tail[1]});
     delete d;
     return HZSDR_OK;
 }

@@ -26,11 +26,7 @@
 //       E = 2.673684e-7 rad  (the bound asserted by tests/test_demod_cpu.py is 2^-21 = 4.77e-7, two ulps of the largest result)
 #pragma once
 
-#if defined(__HIPCC__)
-#define HZ_DM_HD __host__ __device__ inline
-#else
-#define HZ_DM_HD inline
-#endif
+#include "hz_plan.h"
 
 #if defined(__clang__)
 #define HZ_DM_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -51,7 +47,7 @@ constexpr float kAtan[8] = {-3.333298564e-01f, 1.999039650e-01f,  -1.418597549e-
                             -7.366702706e-02f, 4.112181813e-02f, -1.513251010e-02f, 2.622237895e-03f};
 
 // a * conj(b), every operation rounded by itself
-HZ_DM_HD c32 demod_mul_conj(c32 a, c32 b) {
+HZ_HD c32 demod_mul_conj(c32 a, c32 b) {
     HZ_DM_NO_CONTRACT
     const float rr = a.re * b.re, ii = a.im * b.im, ir = a.im * b.re, ri = a.re * b.im;
     c32 p;
@@ -60,7 +56,7 @@ HZ_DM_HD c32 demod_mul_conj(c32 a, c32 b) {
     return p;
 }
 
-HZ_DM_HD float demod_angle(float y, float x) {
+HZ_HD float demod_angle(float y, float x) {
     HZ_DM_NO_CONTRACT
     const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
     const bool steep = ay > ax;
@@ -84,16 +80,16 @@ HZ_DM_HD float demod_angle(float y, float x) {
     return __builtin_copysignf(r, y);
 }
 
-HZ_DM_HD float demod_power(c32 a) {
+HZ_HD float demod_power(c32 a) {
     HZ_DM_NO_CONTRACT
     const float rr = a.re * a.re, ii = a.im * a.im;
     return rr + ii;
 }
 
-HZ_DM_HD float demod_envelope(c32 a) { return __builtin_sqrtf(demod_power(a)); }
-HZ_DM_HD float demod_phase(c32 a) { return demod_angle(a.im, a.re); }
+HZ_HD float demod_envelope(c32 a) { return __builtin_sqrtf(demod_power(a)); }
+HZ_HD float demod_phase(c32 a) { return demod_angle(a.im, a.re); }
 // a = c(x[n]), b = c(x[n - 1])
-HZ_DM_HD float demod_fm(c32 a, c32 b) {
+HZ_HD float demod_fm(c32 a, c32 b) {
     const c32 p = demod_mul_conj(a, b);
     return demod_angle(p.im, p.re);
 }
@@ -101,7 +97,7 @@ HZ_DM_HD float demod_fm(c32 a, c32 b) {
 constexpr int kFm = 1, kPhase = 2, kEnvelope = 3, kPower = 4;  // HZSDR_DEMOD_*
 
 // d[n] of `mode` from a = c(x[n]) and b = c(x[n - 1]) (read by FM alone)
-HZ_DM_HD float demod_detect(int mode, c32 a, c32 b) {
+HZ_HD float demod_detect(int mode, c32 a, c32 b) {
     switch (mode) {
     case kFm: return demod_fm(a, b);
     case kPhase: return demod_phase(a);
@@ -111,7 +107,7 @@ HZ_DM_HD float demod_detect(int mode, c32 a, c32 b) {
 }
 
 // one term of the post-filter: THE expression every path evaluates
-HZ_DM_HD float demod_term(float acc, float h, float d) { return __builtin_fmaf(h, d, acc); }
+HZ_HD float demod_term(float acc, float h, float d) { return __builtin_fmaf(h, d, acc); }
 
 }  // namespace dm
 }  // namespace hz

@@ -6,16 +6,12 @@
 // recomputed as a product with the stream length.
 //
 // The device sees a 64-bit scalar per workgroup, formed from the tile index (demod_tile), and 32-bit per-lane window
-// indices below (T - 1) D + Q < 2^17, divided by D with a reciprocal (demod_div) that is exact on that range.
+// indices below (T - 1) D + Q < 2^17, divided by D with a reciprocal (div_by_magic, hz_plan.h) that is exact on that range.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define HZ_DP_HD __host__ __device__
-#else
-#define HZ_DP_HD
-#endif
+#include "hz_plan.h"
 
 namespace hz {
 namespace dp {
@@ -66,26 +62,23 @@ struct Tile {
 };
 
 // tile `tile` of a push whose first output has `rel`: T outputs from output tile * T of the push
-HZ_DP_HD inline Tile demod_tile(uint32_t rel, uint32_t D, uint32_t Q, uint32_t T, uint64_t tile) {
+HZ_HD Tile demod_tile(uint32_t rel, uint32_t D, uint32_t Q, uint32_t T, uint64_t tile) {
     Tile t;
     t.i0 = rel + tile * ((uint64_t)T * D);  // below 2^63: Step.ok
     t.window = (T - 1) * D + Q;
     return t;
 }
 
-// floor(w / D) for w < 2^22 by multiplication: magic = floor(2^32 / D) + 1.  e = magic D - 2^32 lies in (0, D], and
-// floor(w magic / 2^32) = floor(w / D) as long as w e < 2^32, which D <= 64 and w < 2^22 give.
+// floor(w / D) for w < 2^22 is div_by_magic(w, div_magic(D)) (hz_plan.h): D <= 64 and w < 2^22 keep w D below 2^32.
 constexpr uint32_t kDivRange = 1u << 22;
-inline uint64_t demod_magic(uint32_t D) { return ((uint64_t)1 << 32) / D + 1; }
-HZ_DP_HD inline uint32_t demod_div(uint32_t w, uint64_t magic) { return (uint32_t)((w * magic) >> 32); }
 
 // Where window value w lives in LDS.  For a given tap, lane l of a wave reads value l D + c: 4 bytes each, serviced 32
 // lanes at a time over 32 banks.  The window is stored TRANSPOSED, D rows of J floats, value w in row w mod D at
 // column floor(w / D): the lanes of one read then sit in ONE row at consecutive columns, one lane per bank for every
 // D, odd or even, and every c.  Along the taps the slot is stepped, never divided: from w to w - 1 it goes one row up
 // (slot - J), and from row 0 to row D - 1 of the column before (slot + (D - 1) J - 1); the row is c mod D, the same for
-// every lane and every chain, so the stepping is scalar work common to a wave.
-HZ_DP_HD inline uint32_t demod_slot(uint32_t w, uint32_t D, uint32_t J) { return (w % D) * J + w / D; }
+// every lane and every chain, so the stepping is scalar work common to a wave.  The slot is transposed_slot(w, D, J)
+// (hz_plan.h).
 
 // the kernel's shape for (D, Q), chosen once at create
 struct Geom {
@@ -109,7 +102,7 @@ inline Geom demod_geom(uint32_t D, uint32_t Q) {
     }
     g.half = g.T < (uint32_t)kThreads;
     g.row0 = (Q - 1) % D;
-    g.slot0 = demod_slot(Q - 1, D, g.J);
+    g.slot0 = transposed_slot(Q - 1, D, g.J);
     g.lds_bytes = (size_t)D * g.J * 4;
     return g;
 }

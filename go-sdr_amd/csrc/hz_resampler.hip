@@ -94,7 +94,7 @@ __global__ __launch_bounds__(rs::kThreads) void resampler_tile_kernel(ResArgs a,
     uint32_t ci[R], cphi[R];
     {
         const uint32_t u = t.phi + tid * a.D;
-        uint32_t i = rs::resampler_div(u, a.magic), phi = u - i * a.U;
+        uint32_t i = div_by_magic(u, a.magic), phi = u - i * a.U;
 #pragma unroll
         for (int r = 0; r < R; r++) {
             ci[r] = i + (a.Q - 1);
@@ -186,27 +186,14 @@ static int res_launch_fmt(hzsdr_resampler *r, const ResArgs &a, float2 *out) {
 }
 
 static int res_launch(hzsdr_resampler *r, const ResArgs &a, float2 *out) {
-    switch (r->fmt) {
-    case HZSDR_FMT_C64: return res_launch_fmt<HZSDR_FMT_C64>(r, a, out);
-    case HZSDR_FMT_U8: return res_launch_fmt<HZSDR_FMT_U8>(r, a, out);
-    case HZSDR_FMT_I8: return res_launch_fmt<HZSDR_FMT_I8>(r, a, out);
-    default: return res_launch_fmt<HZSDR_FMT_I16>(r, a, out);
-    }
-}
-
-template <int FMT>
-static void res_tail_fmt(hzsdr_resampler *r, const ResArgs &a) {
-    const dim3 grid((r->Q - 1 + rs::kThreads - 1) / rs::kThreads, r->R);
-    hipLaunchKernelGGL(resampler_tail_kernel<FMT>, grid, dim3(rs::kThreads), 0, r->ctx->stream, a, r->tail[r->tcur ^ 1]);
+    return with_format(r->fmt, [&](auto f) { return res_launch_fmt<decltype(f)::value>(r, a, out); });
 }
 
 static int res_tail(hzsdr_resampler *r, const ResArgs &a) {
-    switch (r->fmt) {
-    case HZSDR_FMT_C64: res_tail_fmt<HZSDR_FMT_C64>(r, a); break;
-    case HZSDR_FMT_U8: res_tail_fmt<HZSDR_FMT_U8>(r, a); break;
-    case HZSDR_FMT_I8: res_tail_fmt<HZSDR_FMT_I8>(r, a); break;
-    default: res_tail_fmt<HZSDR_FMT_I16>(r, a); break;
-    }
+    const dim3 grid((r->Q - 1 + rs::kThreads - 1) / rs::kThreads, r->R);
+    with_format(r->fmt, [&](auto f) {
+        hipLaunchKernelGGL(resampler_tail_kernel<decltype(f)::value>, grid, dim3(rs::kThreads), 0, r->ctx->stream, a, r->tail[r->tcur ^ 1]);
+    });
     HZ_HIP(r->ctx, hipGetLastError());
     return HZSDR_OK;
 }
@@ -216,48 +203,6 @@ static size_t res_tail_bytes(const hzsdr_resampler *r) { return (size_t)r->R * s
 static ResArgs res_args(const hzsdr_resampler *r, const void *in, size_t in_stride, uint64_t n_in, uint64_t count, size_t out_stride) {
     return ResArgs{in, in_stride, r->tail[r->tcur], r->hp, n_in, count, out_stride, r->magic, r->U, r->D, r->Q, r->g.pitch,
                    r->st.rel, r->st.phi, r->g.step_i, r->g.step_phi};
-}
-
-// The destination of `count` outputs per row.  A DEVICE context, one row, dense rows or rows inside memory the library
-// pinned: the caller's buffer.  Otherwise a HOST context's pitched rows are written densely to a device slot and
-// copied back row by row (res_back).
-struct ResOut {
-    void *dev = nullptr;
-    size_t stride = 0;
-    bool back2d = false;
-};
-
-static int res_out(hzsdr_resampler *r, Stage &st, void *out, size_t out_stride, size_t count, ResOut *o) {
-    const size_t R = r->R;
-    o->stride = out_stride;
-    if (count == 0) return HZSDR_OK;
-    if (R == 1 || out_stride == count) return st.out(1, out, R * count * sizeof(float2), &o->dev);
-    if (!st.host() || st.pinned_by_us(out, ((R - 1) * out_stride + count) * sizeof(float2))) {
-        o->dev = out;
-        return HZSDR_OK;
-    }
-    HZ_TRY(ensure_slot(r->ctx, 1, R * count * sizeof(float2)));
-    o->dev = r->ctx->slots[1].ptr;
-    o->stride = count;
-    o->back2d = true;
-    return HZSDR_OK;
-}
-
-static int res_back(hzsdr_resampler *r, const ResOut &o, void *out, size_t out_stride, size_t count) {
-    if (o.back2d)
-        HZ_HIP(r->ctx, hipMemcpy2DAsync(out, out_stride * sizeof(float2), o.dev, count * sizeof(float2), count * sizeof(float2), r->R,
-                                        hipMemcpyDeviceToHost, r->ctx->stream));
-    return HZSDR_OK;
-}
-
-// the checks of a push or flush that writes `count` outputs per row, before anything is launched
-static int res_check_out(hzsdr_resampler *r, const void *out, size_t out_cap, size_t out_stride, uint64_t count) {
-    hzsdr_ctx *ctx = r->ctx;
-    if (out_cap < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "resampler: output buffer too small for the outputs of the call");
-    if (r->R > 1 && out_stride < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "resampler: out_stride is below the outputs of the call");
-    if (count && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "resampler: null output");
-    if ((count + r->g.T - 1) / r->g.T > 0x7fffffffull) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "resampler: too many outputs for one call");
-    return HZSDR_OK;
 }
 
 }  // namespace hz
@@ -277,12 +222,11 @@ int hzsdr_resampler_create(hzsdr_ctx *ctx, int src_format, size_t up, size_t dow
     const size_t q = (n_taps + up - 1) / up;
     if (q > rs::kMaxPhaseTaps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "resampler: at most 256 taps per phase (ceil(n_taps / up))");
     if (streams == 0 || streams > rs::kMaxStreams) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "resampler: 1 ... 8192 streams");
-    for (size_t k = 0; k < n_taps; k++)
-        if (!std::isfinite(taps[k])) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "resampler: a tap is not finite");
+    HZ_TRY(check_taps_finite(ctx, "resampler", taps, n_taps));
     HZ_TRY(enter(ctx));
     hzsdr_resampler *r = new hzsdr_resampler{ctx, src_format, (uint32_t)up, (uint32_t)down, (uint32_t)n_taps, (uint32_t)q, (uint32_t)streams};
     r->g = rs::resampler_geom(r->U, r->D, r->Q);
-    r->magic = rs::resampler_magic(r->U);
+    r->magic = div_magic(r->U);
     auto undo = [&](int rc) {
         hzsdr_resampler_free(r);
         return rc;
@@ -319,32 +263,22 @@ int hzsdr_resampler_push(hzsdr_resampler *r, const void *in, size_t n_in, size_t
     if (R > 1 && in_stride < n_in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "resampler: in_stride is below the samples of the push");
     const rs::Step p = rs::resampler_step(r->st, r->U, r->D, r->Q, n_in);
     if (!p.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "resampler: the push is too long");
-    HZ_TRY(res_check_out(r, out, out_cap, out_stride, p.count));
+    HZ_TRY(check_rows_out(ctx, "resampler", R, out, out_cap, out_stride, p.count, r->g.T));
     HZ_TRY(enter(ctx));
     if (n_in == 0) return HZSDR_OK;
     Stage st(ctx);
     const void *din;
-    size_t dstride = in_stride;
-    if (R == 1 || in_stride == n_in) {
-        HZ_TRY(st.in(0, in, R * n_in * fs, &din));
-    } else if (!st.host() || st.pinned_by_us(in, ((R - 1) * in_stride + n_in) * fs)) {
-        din = in;
-    } else {  // a HOST context's rows with a pitch: dense on the device, copied in row by row
-        HZ_TRY(ensure_slot(ctx, 0, R * n_in * fs));
-        HZ_HIP(ctx, hipMemcpy2DAsync(ctx->slots[0].ptr, n_in * fs, in, in_stride * fs, n_in * fs, R, hipMemcpyHostToDevice, ctx->stream));
-        din = ctx->slots[0].ptr;
-        dstride = n_in;
-    }
-    ResOut o;
-    HZ_TRY(res_out(r, st, out, out_stride, (size_t)p.count, &o));
-    const ResArgs a = res_args(r, din, dstride, n_in, p.count, o.stride);
-    if (p.count) HZ_TRY(res_launch(r, a, (float2 *)o.dev));
+    void *dout;
+    size_t dstride, ostride;
+    HZ_TRY(st.in_rows(0, in, R, n_in, in_stride, fs, &din, &dstride));
+    HZ_TRY(st.out_rows(1, out, R, (size_t)p.count, out_stride, sizeof(float2), &dout, &ostride));
+    const ResArgs a = res_args(r, din, dstride, n_in, p.count, ostride);
+    if (p.count) HZ_TRY(res_launch(r, a, (float2 *)dout));
     if (r->Q > 1) {
         HZ_TRY(res_tail(r, a));
         r->tcur ^= 1;
     }
     r->st = p.next;
-    HZ_TRY(res_back(r, o, out, out_stride, (size_t)p.count));
     HZ_TRY(st.finish());
     if (written) *written = (size_t)p.count;
     return HZSDR_OK;
@@ -356,15 +290,15 @@ int hzsdr_resampler_flush(hzsdr_resampler *r, void *out, size_t out_cap, size_t 
     if (!r) return HZSDR_ERR_INVALID_ARGUMENT;
     hzsdr_ctx *ctx = r->ctx;
     const uint64_t count = rs::resampler_flush_count(r->st, r->U, r->D, r->L);
-    HZ_TRY(res_check_out(r, out, out_cap, out_stride, count));
+    HZ_TRY(check_rows_out(ctx, "resampler", r->R, out, out_cap, out_stride, count, r->g.T));
     HZ_TRY(enter(ctx));
     if (count) {
         Stage st(ctx);
-        ResOut o;
-        HZ_TRY(res_out(r, st, out, out_stride, (size_t)count, &o));
+        void *dout;
+        size_t ostride;
+        HZ_TRY(st.out_rows(1, out, r->R, (size_t)count, out_stride, sizeof(float2), &dout, &ostride));
         // (a push of no samples: every index at or past the push's first reads as zero)
-        HZ_TRY(res_launch(r, res_args(r, nullptr, 0, 0, count, o.stride), (float2 *)o.dev));
-        HZ_TRY(res_back(r, o, out, out_stride, (size_t)count));
+        HZ_TRY(res_launch(r, res_args(r, nullptr, 0, 0, count, ostride), (float2 *)dout));
         HZ_TRY(st.finish());
     }
     HZ_TRY(hzsdr_resampler_reset(r));
@@ -401,10 +335,7 @@ int hzsdr_resampler_reset(hzsdr_resampler *r) {
 
 int hzsdr_resampler_free(hzsdr_resampler *r) {
     if (!r) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(r->ctx->device);
-    (void)hipStreamSynchronize(r->ctx->stream);
-    for (void *p : {(void *)r->hp, (void *)r->tail[0], (void *)r->tail[1]})
-        if (p) (void)hipFree(p);
+    hz::bank_release(r->ctx, {r->hp, r->tail[0], r->tail[1]});
     delete r;
     return HZSDR_OK;
 }

@@ -8,16 +8,12 @@
 // 128-bit integers; nothing is ever recomputed as a product with the stream length.
 //
 // The device sees a 64-bit scalar per workgroup, formed from the tile index (resampler_tile), and 32-bit per-lane
-// offsets below U + T D < 2^22, divided by U with a reciprocal (resampler_div) that is exact on that range.
+// offsets below U + T D < 2^22, divided by U with a reciprocal (div_by_magic, hz_plan.h) that is exact on that range.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define HZ_RS_HD __host__ __device__
-#else
-#define HZ_RS_HD
-#endif
+#include "hz_plan.h"
 
 namespace hz {
 namespace rs {
@@ -75,7 +71,7 @@ struct Tile {
 };
 
 // tile `tile` of a push whose first output has (rel, phi): T outputs from output tile * T of the push
-HZ_RS_HD inline Tile resampler_tile(uint32_t rel, uint32_t phi, uint32_t U, uint32_t D, uint32_t Q, uint32_t T, uint64_t tile) {
+HZ_HD Tile resampler_tile(uint32_t rel, uint32_t phi, uint32_t U, uint32_t D, uint32_t Q, uint32_t T, uint64_t tile) {
     const uint64_t tt = (uint64_t)rel * U + phi + tile * ((uint64_t)T * D);  // below 2^63: Step.ok
     Tile t;
     t.i0 = tt / U;
@@ -84,11 +80,8 @@ HZ_RS_HD inline Tile resampler_tile(uint32_t rel, uint32_t phi, uint32_t U, uint
     return t;
 }
 
-// floor(u / U) for u < 2^22 by multiplication: magic = floor(2^32 / U) + 1.  e = magic U - 2^32 lies in (0, U], and
-// floor(u magic / 2^32) = floor(u / U) as long as u e < 2^32, which U <= 1024 and u < 2^22 give.
+// floor(u / U) for u < 2^22 is div_by_magic(u, div_magic(U)) (hz_plan.h): U <= 1024 and u < 2^22 keep u U below 2^32.
 constexpr uint32_t kDivRange = 1u << 22;
-inline uint64_t resampler_magic(uint32_t U) { return ((uint64_t)1 << 32) / U + 1; }
-HZ_RS_HD inline uint32_t resampler_div(uint32_t u, uint64_t magic) { return (uint32_t)((u * magic) >> 32); }
 
 // the kernel's shape for (U, D, Q), chosen once at create
 struct Geom {
@@ -115,7 +108,7 @@ inline uint32_t resampler_pitch(uint32_t Q) {
 // four lanes per bank); one empty slot behind every 32 samples makes them differ for D/U = 2, 4, 8, 16, 32 and nearly
 // so between those.  Below 2 the plain layout has at most two lanes per bank, and the two operations per read that the
 // padded index costs are not worth paying.
-HZ_RS_HD inline uint32_t resampler_slot(uint32_t w, bool pad) { return pad ? w + (w >> 5) : w; }
+HZ_HD uint32_t resampler_slot(uint32_t w, bool pad) { return pad ? w + (w >> 5) : w; }
 
 inline Geom resampler_geom(uint32_t U, uint32_t D, uint32_t Q) {
     Geom g{};

@@ -12,6 +12,7 @@
 //     carry a partial row from chunk to chunk and from push to push.  For few rows of many frames.
 #include "hz_chain_host.h"
 #include "../../include/hzsdr_spectrum.h"
+#include "hz_polyphase.h"
 
 struct hzsdr_spectrum {
     hzsdr_ctx *ctx;
@@ -210,16 +211,6 @@ __global__ __launch_bounds__(kThreads) void spectrum_sum_kernel(const float *__r
     else acc_out[k] = acc;
 }
 
-// the samples held for the next frame: V[start .. start + cnt) converted
-template <int FMT>
-__global__ __launch_bounds__(kThreads) void spectrum_tail_kernel(SpecArgs a, size_t start, size_t cnt, float2 *__restrict__ tail_out) {
-    using R = typename Raw<FMT>::t;
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < cnt; i += (size_t)gridDim.x * kThreads) {
-        const size_t v = start + i;
-        tail_out[i] = v < a.held ? a.tail[v] : Raw<FMT>::cvt(((const R *)a.in)[v - a.held]);
-    }
-}
-
 // frame-parallel chunk: p_j of at most this many float32 values in scratch at once
 constexpr size_t kSpecChunkFloats = (size_t)1 << 23;
 
@@ -281,14 +272,6 @@ static int spec_launch_fmt(hzsdr_spectrum *s, const SpecArgs &a, float *out, int
     case 8192: return spec_launch_n<8192, FMT>(s, a, out, form);
     default: return HZSDR_ERR_INVALID_ARGUMENT;
     }
-}
-
-template <int FMT>
-static int spec_tail(hzsdr_spectrum *s, const SpecArgs &a, size_t start, size_t cnt) {
-    hipLaunchKernelGGL(spectrum_tail_kernel<FMT>, dim3(blocks_for(s->ctx, cnt)), dim3(kThreads), 0, s->ctx->stream, a, start, cnt,
-                       s->tail[s->tcur ^ 1]);
-    HZ_HIP(s->ctx, hipGetLastError());
-    return HZSDR_OK;
 }
 
 // Auto: the row walk as long as the rows give every SIMD of the chip a wave of their own (a row is TPT lanes), the
@@ -366,22 +349,11 @@ int hzsdr_spectrum_push(hzsdr_spectrum *s, const void *in, size_t n_in, float *o
     const SpecArgs a{din, s->tail[s->tcur], s->held, s->hop, p.F, s->win, s->tabs.fwd};
     if (p.F) {
         const int form = spec_pick_form(s, p.F);
-        switch (s->fmt) {
-        case HZSDR_FMT_C64: HZ_TRY(spec_launch_fmt<HZSDR_FMT_C64>(s, a, (float *)dout, form)); break;
-        case HZSDR_FMT_U8: HZ_TRY(spec_launch_fmt<HZSDR_FMT_U8>(s, a, (float *)dout, form)); break;
-        case HZSDR_FMT_I8: HZ_TRY(spec_launch_fmt<HZSDR_FMT_I8>(s, a, (float *)dout, form)); break;
-        default: HZ_TRY(spec_launch_fmt<HZSDR_FMT_I16>(s, a, (float *)dout, form)); break;
-        }
+        HZ_TRY(with_format(s->fmt, [&](auto f) { return spec_launch_fmt<decltype(f)::value>(s, a, (float *)dout, form); }));
         s->last_form = form;
     }
     if (p.new_held) {
-        const size_t start = p.L - p.new_held;
-        switch (s->fmt) {
-        case HZSDR_FMT_C64: HZ_TRY(spec_tail<HZSDR_FMT_C64>(s, a, start, p.new_held)); break;
-        case HZSDR_FMT_U8: HZ_TRY(spec_tail<HZSDR_FMT_U8>(s, a, start, p.new_held)); break;
-        case HZSDR_FMT_I8: HZ_TRY(spec_tail<HZSDR_FMT_I8>(s, a, start, p.new_held)); break;
-        default: HZ_TRY(spec_tail<HZSDR_FMT_I16>(s, a, start, p.new_held)); break;
-        }
+        HZ_TRY(hold_samples(ctx, s->fmt, din, a.tail, a.held, p.L - p.new_held, p.new_held, s->tail[s->tcur ^ 1]));
         s->tcur ^= 1;
     }
     s->held = p.new_held;
@@ -422,10 +394,7 @@ int hzsdr_spectrum_reset(hzsdr_spectrum *s) {
 
 int hzsdr_spectrum_free(hzsdr_spectrum *s) {
     if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    for (void *p : {(void *)s->win, (void *)s->tail[0], (void *)s->tail[1], (void *)s->acc[0], (void *)s->acc[1], (void *)s->scratch})
-        if (p) (void)hipFree(p);
+    hz::bank_release(s->ctx, {s->win, s->tail[0], s->tail[1], s->acc[0], s->acc[1], s->scratch});
     delete s;
     return HZSDR_OK;
 }

@@ -177,12 +177,10 @@ static int synth_frames(hzsdr_synthesizer *s, const float2 *in, size_t stride, s
 
 static int synth_ola(hzsdr_synthesizer *s, const SynthOla &a, void *out) {
     const dim3 grid((a.total + kThreads - 1) / kThreads), block(kThreads);
-    switch (s->fmt) {
-    case HZSDR_FMT_C64: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_C64>, grid, block, 0, s->ctx->stream, a, (float2 *)out); break;
-    case HZSDR_FMT_U8: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_U8>, grid, block, 0, s->ctx->stream, a, (uint16_t *)out); break;
-    case HZSDR_FMT_I8: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_I8>, grid, block, 0, s->ctx->stream, a, (uint16_t *)out); break;
-    default: hipLaunchKernelGGL(synthesizer_ola_kernel<HZSDR_FMT_I16>, grid, block, 0, s->ctx->stream, a, (uint32_t *)out); break;
-    }
+    with_format(s->fmt, [&](auto f) {
+        constexpr int FMT = decltype(f)::value;
+        hipLaunchKernelGGL(synthesizer_ola_kernel<FMT>, grid, block, 0, s->ctx->stream, a, (typename SynthDst<FMT>::t *)out);
+    });
     HZ_HIP(s->ctx, hipGetLastError());
     return HZSDR_OK;
 }
@@ -216,13 +214,7 @@ int hzsdr_synthesizer_create(hzsdr_ctx *ctx, int dst_format, size_t channels, co
     if (m < 256 || m > 8192 || (m & (m - 1)) != 0)
         return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: the channel count is a power of two, 256 ... 8192");
     if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null taps");
-    if (n_taps == 0 || n_taps % m != 0 || n_taps > 32 * m)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: the prototype has P * channels taps, 1 <= P <= 32");
-    if (hop == 0 || hop > m) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: the hop is 1 ... channels");
-    if (order != HZSDR_ORDER_ZERO_FIRST && order != HZSDR_ORDER_NEGATIVE_FIRST)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: unknown fft order");
-    if (layout != HZSDR_CHANNELIZER_FRAME_MAJOR && layout != HZSDR_CHANNELIZER_CHANNEL_MAJOR)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: unknown input layout");
+    HZ_TRY(check_polyphase_args(ctx, "synthesizer", m, n_taps, hop, order, layout));
     HZ_TRY(enter(ctx));
     hzsdr_synthesizer *s = new hzsdr_synthesizer{ctx, dst_format, m, n_taps, hop, order, layout};
     auto undo = [&](int rc) {
@@ -250,8 +242,7 @@ int hzsdr_synthesizer_push(hzsdr_synthesizer *s, const void *frames, size_t n_fr
     const size_t M = s->m, D = s->hop, L = s->ntaps, n_out = n_frames * D;
     if (n_frames && !frames) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null input");
     if (chmajor && in_stride < n_frames) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: in_stride is below the frames of the push");
-    if (out_cap < n_out) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "synthesizer: output buffer too small for the samples of the push");
-    if (n_out && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null output");
+    HZ_TRY(check_rows_out(ctx, "synthesizer", 1, out, out_cap, 0, n_out, 0));
     HZ_TRY(enter(ctx));
     if (n_frames == 0) return HZSDR_OK;
     HZ_TRY(synth_scratch(s, n_frames));
@@ -259,18 +250,9 @@ int hzsdr_synthesizer_push(hzsdr_synthesizer *s, const void *frames, size_t n_fr
     Stage st(ctx);
     const void *din;
     void *dout;
-    size_t dstride = in_stride;
-    if (!chmajor || in_stride == n_frames) {
-        HZ_TRY(st.in(0, frames, n_frames * M * sizeof(float2), &din));
-    } else if (!st.host() || st.pinned_by_us(frames, ((M - 1) * in_stride + n_frames) * sizeof(float2))) {
-        din = frames;
-    } else {  // a HOST context's channel-major rows with a pitch: dense on the device, copied in row by row
-        HZ_TRY(ensure_slot(ctx, 0, M * n_frames * sizeof(float2)));
-        HZ_HIP(ctx, hipMemcpy2DAsync(ctx->slots[0].ptr, n_frames * sizeof(float2), frames, in_stride * sizeof(float2),
-                                     n_frames * sizeof(float2), M, hipMemcpyHostToDevice, ctx->stream));
-        din = ctx->slots[0].ptr;
-        dstride = n_frames;
-    }
+    size_t dstride;
+    // (M channels of n_frames frames, in_stride apart, or -- frame-major -- one run of n_frames * M values)
+    HZ_TRY(st.in_rows(0, frames, chmajor ? M : 1, chmajor ? n_frames : n_frames * M, in_stride, sizeof(float2), &din, &dstride));
     HZ_TRY(st.out(1, out, n_out * fs, &dout));
     const size_t group = synth_group_frames(s);
     for (size_t f0 = 0; f0 < n_frames; f0 += group) {
@@ -295,8 +277,7 @@ int hzsdr_synthesizer_flush(hzsdr_synthesizer *s, void *out, size_t out_cap, siz
     if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
     hzsdr_ctx *ctx = s->ctx;
     const size_t n = s->held;
-    if (out_cap < n) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "synthesizer: output buffer too small for the held samples");
-    if (n && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null output");
+    HZ_TRY(check_rows_out(ctx, "synthesizer", 1, out, out_cap, 0, n, 0));
     HZ_TRY(enter(ctx));
     if (n) {
         Stage st(ctx);
@@ -336,10 +317,7 @@ int hzsdr_synthesizer_reset(hzsdr_synthesizer *s) {
 
 int hzsdr_synthesizer_free(hzsdr_synthesizer *s) {
     if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    for (void *p : {(void *)s->taps, (void *)s->hold[0], (void *)s->hold[1], (void *)s->w})
-        if (p) (void)hipFree(p);
+    hz::bank_release(s->ctx, {s->taps, s->hold[0], s->hold[1], s->w});
     delete s;
     return HZSDR_OK;
 }

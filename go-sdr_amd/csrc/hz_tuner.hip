@@ -6,7 +6,7 @@
 //
 // One kernel.  A workgroup of four waves takes T outputs times tile_rows rows of A.  It stages the tile's window of
 // (T - 1) D + cq samples, converted in the loads -- from the held samples below the push's first one, +0 at and past
-// its last -- into LDS as two planes, each transposed by D (tp::tuner_slot), so that the 16 lanes of one k of a
+// its last -- into LDS as two planes, each transposed by D (transposed_slot), so that the 16 lanes of one k of a
 // B-operand read, samples D apart, are 16 consecutive floats, and the re and im halves of a 32-lane group fall on
 // disjoint banks (plane pitch 16 mod 32).  A wave holds 2 x 2 accumulators (32 rows x 32 outputs): per k-step two
 // coalesced loads of A, two LDS reads of B and four MFMAs.  Where the window of the whole filter is past the LDS budget
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(tp::kThreads) void tuner_tile_kernel(TunArgs a, flo
 
     // the lane's first B sample of a chunk: w = ml D + (cq - 1) - (kk >> 1), then two samples down per k-step
     const uint32_t w0 = ml * a.D + (a.cq - 1u) - (kk >> 1);
-    [[maybe_unused]] const uint32_t col0 = tp::tuner_div(w0, a.magic), row0 = w0 - col0 * a.D;
+    [[maybe_unused]] const uint32_t col0 = div_by_magic(w0, a.magic), row0 = w0 - col0 * a.D;
     const uint32_t dec = 2u % a.D, cdec = 2u / a.D;
     [[maybe_unused]] const uint32_t down = dec * a.J + cdec, wrap = a.D * a.J - 1u;
     [[maybe_unused]] const float *bp = win + (kk & 1u) * a.plane;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(tp::kThreads) void tuner_tile_kernel(TunArgs a, flo
             const TunSrc<FMT> src(a, tp::tuner_window_base(a.rel, a.D, T, a.cq, blockIdx.x, c));
             for (uint32_t w = tid; w < a.window; w += tp::kThreads) {
                 const float2 v = src.at(w);
-                const uint32_t j = tp::tuner_div(w, a.magic);
+                const uint32_t j = div_by_magic(w, a.magic);
                 const uint32_t s = (w - j * a.D) * a.J + j;
                 win[s] = v.x;
                 win[a.plane + s] = v.y;
@@ -194,27 +194,14 @@ static int tun_launch_fmt(hzsdr_tuner *t, const TunArgs &a, float2 *out) {
 }
 
 static int tun_launch(hzsdr_tuner *t, const TunArgs &a, float2 *out) {
-    switch (t->fmt) {
-    case HZSDR_FMT_C64: return tun_launch_fmt<HZSDR_FMT_C64>(t, a, out);
-    case HZSDR_FMT_U8: return tun_launch_fmt<HZSDR_FMT_U8>(t, a, out);
-    case HZSDR_FMT_I8: return tun_launch_fmt<HZSDR_FMT_I8>(t, a, out);
-    default: return tun_launch_fmt<HZSDR_FMT_I16>(t, a, out);
-    }
-}
-
-template <int FMT>
-static void tun_tail_fmt(hzsdr_tuner *t, const TunArgs &a) {
-    const dim3 grid((a.H + tp::kThreads - 1) / tp::kThreads + (a.H == 0));
-    hipLaunchKernelGGL(tuner_tail_kernel<FMT>, grid, dim3(tp::kThreads), 0, t->ctx->stream, a, t->tail[t->tcur ^ 1], t->phase_dev);
+    return with_format(t->fmt, [&](auto f) { return tun_launch_fmt<decltype(f)::value>(t, a, out); });
 }
 
 static int tun_tail(hzsdr_tuner *t, const TunArgs &a) {
-    switch (t->fmt) {
-    case HZSDR_FMT_C64: tun_tail_fmt<HZSDR_FMT_C64>(t, a); break;
-    case HZSDR_FMT_U8: tun_tail_fmt<HZSDR_FMT_U8>(t, a); break;
-    case HZSDR_FMT_I8: tun_tail_fmt<HZSDR_FMT_I8>(t, a); break;
-    default: tun_tail_fmt<HZSDR_FMT_I16>(t, a); break;
-    }
+    const dim3 grid((a.H + tp::kThreads - 1) / tp::kThreads + (a.H == 0));
+    with_format(t->fmt, [&](auto f) {
+        hipLaunchKernelGGL(tuner_tail_kernel<decltype(f)::value>, grid, dim3(tp::kThreads), 0, t->ctx->stream, a, t->tail[t->tcur ^ 1], t->phase_dev);
+    });
     HZ_HIP(t->ctx, hipGetLastError());
     return HZSDR_OK;
 }
@@ -224,48 +211,6 @@ static size_t tun_tail_bytes(const hzsdr_tuner *t) { return (size_t)(t->Q > 1 ? 
 static TunArgs tun_args(const hzsdr_tuner *t, const void *in, uint64_t n_in, uint64_t count, size_t out_stride) {
     return TunArgs{in, t->tail[t->tcur], t->a_dev, t->phase_dev, t->step_dev, t->tab_dev, n_in, count, out_stride, t->magic,
                    t->D, tp::tuner_held(t->Q), t->K, t->st.rel, t->g.steps, t->g.cq, t->g.chunks, t->g.J, t->g.plane, t->g.window};
-}
-
-// The destination of `count` outputs per row, as hz_demod.hip's: the caller's buffer in a DEVICE context, for one row,
-// for dense rows or for rows inside memory the library pinned; otherwise a HOST context's pitched rows are written
-// densely to a device slot and copied back row by row (tun_back).
-struct TunOut {
-    void *dev = nullptr;
-    size_t stride = 0;
-    bool back2d = false;
-};
-
-static int tun_out(hzsdr_tuner *t, Stage &st, void *out, size_t out_stride, size_t count, TunOut *o) {
-    const size_t K = t->K;
-    o->stride = out_stride;
-    if (count == 0) return HZSDR_OK;
-    if (K == 1 || out_stride == count) return st.out(1, out, K * count * sizeof(float2), &o->dev);
-    if (!st.host() || st.pinned_by_us(out, ((K - 1) * out_stride + count) * sizeof(float2))) {
-        o->dev = out;
-        return HZSDR_OK;
-    }
-    HZ_TRY(ensure_slot(t->ctx, 1, K * count * sizeof(float2)));
-    o->dev = t->ctx->slots[1].ptr;
-    o->stride = count;
-    o->back2d = true;
-    return HZSDR_OK;
-}
-
-static int tun_back(hzsdr_tuner *t, const TunOut &o, void *out, size_t out_stride, size_t count) {
-    if (o.back2d)
-        HZ_HIP(t->ctx, hipMemcpy2DAsync(out, out_stride * sizeof(float2), o.dev, count * sizeof(float2), count * sizeof(float2), t->K,
-                                        hipMemcpyDeviceToHost, t->ctx->stream));
-    return HZSDR_OK;
-}
-
-// the checks of a push or flush that writes `count` outputs per row, before anything is launched
-static int tun_check_out(hzsdr_tuner *t, const void *out, size_t out_cap, size_t out_stride, uint64_t count) {
-    hzsdr_ctx *ctx = t->ctx;
-    if (out_cap < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "tuner: output buffer too small for the outputs of the call");
-    if (t->K > 1 && out_stride < count) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "tuner: out_stride is below the outputs of the call");
-    if (count && !out) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: null output");
-    if ((count + t->g.T - 1) / t->g.T > 0x7fffffffull) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: too many outputs for one call");
-    return HZSDR_OK;
 }
 
 // step 1 for tuner k, and its two rows of A
@@ -310,12 +255,11 @@ int hzsdr_tuner_create(hzsdr_ctx *ctx, int src_format, const uint32_t *words, si
     if (!words) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: null words");
     if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: null taps");
     if (n_taps == 0 || n_taps > tp::kMaxTaps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: 1 ... 1024 taps");
-    for (size_t k = 0; k < n_taps; k++)
-        if (!std::isfinite(taps[k])) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: a tap is not finite");
+    HZ_TRY(check_taps_finite(ctx, "tuner", taps, n_taps));
     HZ_TRY(enter(ctx));
     hzsdr_tuner *t = new hzsdr_tuner{ctx, src_format, (uint32_t)tuners, (uint32_t)down, (uint32_t)n_taps};
     t->g = tp::tuner_geom(t->K, t->D, t->Q);
-    t->magic = tp::tuner_magic(t->D);
+    t->magic = div_magic(t->D);
     t->h.assign(t->g.Qp, 0.0f);
     for (size_t q = 0; q < n_taps; q++) t->h[q] = taps[q];
     t->words.assign(words, words + tuners);
@@ -362,21 +306,21 @@ int hzsdr_tuner_push(hzsdr_tuner *t, const void *in, size_t n_in, void *out, siz
     if (n_in && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: null input");
     const tp::Step p = dp::demod_step(t->st, t->D, t->Q, n_in);
     if (!p.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "tuner: the push is too long");
-    HZ_TRY(tun_check_out(t, out, out_cap, out_stride, p.count));
+    HZ_TRY(check_rows_out(ctx, "tuner", t->K, out, out_cap, out_stride, p.count, t->g.T));
     HZ_TRY(enter(ctx));
     if (n_in == 0) return HZSDR_OK;
     Stage st(ctx);
     const void *din;
+    void *dout;
+    size_t ostride;
     HZ_TRY(st.in(0, in, n_in * (size_t)format_size(t->fmt), &din));
-    TunOut o;
-    HZ_TRY(tun_out(t, st, out, out_stride, (size_t)p.count, &o));
-    const TunArgs a = tun_args(t, din, n_in, p.count, o.stride);
-    if (p.count) HZ_TRY(tun_launch(t, a, (float2 *)o.dev));
+    HZ_TRY(st.out_rows(1, out, t->K, (size_t)p.count, out_stride, sizeof(float2), &dout, &ostride));
+    const TunArgs a = tun_args(t, din, n_in, p.count, ostride);
+    if (p.count) HZ_TRY(tun_launch(t, a, (float2 *)dout));
     HZ_TRY(tun_tail(t, a));
     t->tcur ^= 1;
     t->st = p.next;
     for (uint32_t k = 0; k < t->K; k++) t->phase[k] = tp::phase_advance(t->phase[k], t->step[k], p.count);
-    HZ_TRY(tun_back(t, o, out, out_stride, (size_t)p.count));
     HZ_TRY(st.finish());
     if (written) *written = (size_t)p.count;
     return HZSDR_OK;
@@ -388,15 +332,15 @@ int hzsdr_tuner_flush(hzsdr_tuner *t, void *out, size_t out_cap, size_t out_stri
     if (!t) return HZSDR_ERR_INVALID_ARGUMENT;
     hzsdr_ctx *ctx = t->ctx;
     const uint64_t count = dp::demod_flush_count(t->st, t->D, t->Q);
-    HZ_TRY(tun_check_out(t, out, out_cap, out_stride, count));
+    HZ_TRY(check_rows_out(ctx, "tuner", t->K, out, out_cap, out_stride, count, t->g.T));
     HZ_TRY(enter(ctx));
     if (count) {
         Stage st(ctx);
-        TunOut o;
-        HZ_TRY(tun_out(t, st, out, out_stride, (size_t)count, &o));
+        void *dout;
+        size_t ostride;
+        HZ_TRY(st.out_rows(1, out, t->K, (size_t)count, out_stride, sizeof(float2), &dout, &ostride));
         // (a push of no samples: every sample at or past the push's first reads as zero)
-        HZ_TRY(tun_launch(t, tun_args(t, nullptr, 0, count, o.stride), (float2 *)o.dev));
-        HZ_TRY(tun_back(t, o, out, out_stride, (size_t)count));
+        HZ_TRY(tun_launch(t, tun_args(t, nullptr, 0, count, ostride), (float2 *)dout));
         HZ_TRY(st.finish());
     }
     HZ_TRY(hzsdr_tuner_reset(t));
@@ -470,10 +414,7 @@ int hzsdr_tuner_reset(hzsdr_tuner *t) {
 
 int hzsdr_tuner_free(hzsdr_tuner *t) {
     if (!t) return HZSDR_ERR_INVALID_ARGUMENT;
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    for (void *p : {(void *)t->a_dev, (void *)t->tab_dev, (void *)t->step_dev, (void *)t->phase_dev, (void *)t->tail[0], (void *)t->tail[1]})
-        if (p) (void)hipFree(p);
+    hz::bank_release(t->ctx, {t->a_dev, t->tab_dev, t->step_dev, t->phase_dev, t->tail[0], t->tail[1]});
     delete t;
     return HZSDR_OK;
 }

@@ -10,11 +10,7 @@
 #include <stdint.h>
 #include <math.h>
 
-#if defined(__HIPCC__)
-#define HZ_TM_HD __host__ __device__ inline
-#else
-#define HZ_TM_HD inline
-#endif
+#include "hz_plan.h"
 
 #if defined(__clang__)
 #define HZ_TM_NO_CONTRACT _Pragma("clang fp contract(off)")
@@ -32,12 +28,12 @@ struct c32 {
 // p = a 2^21 + b 2^10 + c: 11, 11 and 10 bits
 constexpr uint32_t kT2 = 2048, kT1 = 2048, kT0 = 1024;
 constexpr uint32_t kTables = kT2 + kT1 + kT0;  // T2 at 0, T1 at kT2, T0 at kT2 + kT1 of one array
-HZ_TM_HD uint32_t tuner_a(uint32_t p) { return p >> 21; }
-HZ_TM_HD uint32_t tuner_b(uint32_t p) { return (p >> 10) & 2047u; }
-HZ_TM_HD uint32_t tuner_c(uint32_t p) { return p & 1023u; }
+HZ_HD uint32_t tuner_a(uint32_t p) { return p >> 21; }
+HZ_HD uint32_t tuner_b(uint32_t p) { return (p >> 10) & 2047u; }
+HZ_HD uint32_t tuner_c(uint32_t p) { return p & 1023u; }
 
 // cmul(u, v): the inner products rounded by themselves, the outer step fused
-HZ_TM_HD c32 tuner_cmul(c32 u, c32 v) {
+HZ_HD c32 tuner_cmul(c32 u, c32 v) {
     HZ_TM_NO_CONTRACT
     const float ii = u.im * v.im, ir = u.im * v.re;
     c32 r;
@@ -47,13 +43,13 @@ HZ_TM_HD c32 tuner_cmul(c32 u, c32 v) {
 }
 
 // y = cmul(s, cmul(cmul(T2[a], T1[b]), T0[c])) of the phase word p; tab: the three tables in one array
-HZ_TM_HD c32 tuner_rotate(c32 s, uint32_t p, const c32 *tab) {
+HZ_HD c32 tuner_rotate(c32 s, uint32_t p, const c32 *tab) {
     const c32 r = tuner_cmul(tuner_cmul(tab[tuner_a(p)], tab[kT2 + tuner_b(p)]), tab[kT2 + kT1 + tuner_c(p)]);
     return tuner_cmul(s, r);
 }
 
 // one q of step 2 as a chain of four fused steps: THE expression the matrix product must reproduce
-HZ_TM_HD c32 tuner_term(c32 acc, c32 g, c32 a) {
+HZ_HD c32 tuner_term(c32 acc, c32 g, c32 a) {
     acc.re = __builtin_fmaf(g.re, a.re, acc.re);
     acc.re = __builtin_fmaf(-g.im, a.im, acc.re);
     acc.im = __builtin_fmaf(g.im, a.re, acc.im);

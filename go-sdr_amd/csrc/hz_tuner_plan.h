@@ -9,7 +9,7 @@
 // The product is A (2K x 2Qp) times B (2Qp x outputs) on v_mfma_f32_16x16x4_f32.  A workgroup of four waves takes T
 // outputs times `tile_rows` rows of A; a wave holds 2 x 2 accumulators of 16 x 16, i.e. 32 rows times 32 outputs, and
 // the waves lie along the outputs first (T = 128: 4 x 1, T = 64: 2 x 2, T = 32: 1 x 4).  The tile's window of
-// (T - 1) D + cq converted samples is staged in LDS as two planes (re, im), each transposed by D (tuner_slot); cq is
+// (T - 1) D + cq converted samples is staged in LDS as two planes (re, im), each transposed by D (transposed_slot, hz_plan.h); cq is
 // the chunk of q staged at once, Qp wherever the window then fits the budget, otherwise the largest even count that
 // does at T = 32, the accumulators carried from chunk to chunk.
 #pragma once
@@ -35,25 +35,21 @@ inline uint32_t tuner_held(uint32_t Q) { return Q - 1; }
 
 // ---- the running phase words -------------------------------------------------------------------------
 // the phase step from one output to the next, (w D) mod 2^32
-HZ_DP_HD inline uint32_t phase_step(uint32_t w, uint32_t D) { return w * D; }
+HZ_HD uint32_t phase_step(uint32_t w, uint32_t D) { return w * D; }
 // the word of output m, (w D m) mod 2^32 = step * (m mod 2^32) mod 2^32: at create, reset and retune
 inline uint32_t phase_at(uint32_t step, uint64_t m) { return step * (uint32_t)m; }
 // behind a push of `count` outputs
-HZ_DP_HD inline uint32_t phase_advance(uint32_t p, uint32_t step, uint64_t count) { return p + step * (uint32_t)count; }
+HZ_HD uint32_t phase_advance(uint32_t p, uint32_t step, uint64_t count) { return p + step * (uint32_t)count; }
 
 // ---- the window's layout ------------------------------------------------------------------------------
-// floor(w / D) for w < 2^16 by multiplication: magic = floor(2^32 / D) + 1; exact while w (magic D - 2^32) < 2^32, which
-// D <= 256 and w < 2^16 give.
+// floor(w / D) for w < 2^16 is div_by_magic(w, div_magic(D)) (hz_plan.h): D <= 256 and w < 2^16 keep w D below 2^32.
 constexpr uint32_t kDivRange = 1u << 16;
-inline uint64_t tuner_magic(uint32_t D) { return ((uint64_t)1 << 32) / D + 1; }
-HZ_DP_HD inline uint32_t tuner_div(uint32_t w, uint64_t magic) { return (uint32_t)((w * magic) >> 32); }
 
 // Where window sample w lives in a plane.  Lane l of a B-operand read holds output (l & 15) of a 16-column tile: the
 // 16 lanes of one k are samples D apart.  Stored transposed, D rows of J floats, sample w in row w mod D at column
 // floor(w / D), they are 16 consecutive floats for every D.  The two halves of a 32-lane service group read the SAME
 // slots of the re plane and of the im plane (k = 0, 1: the re and im term of one q), so the plane pitch is 16 modulo
-// 32: distinct banks for every D.
-HZ_DP_HD inline uint32_t tuner_slot(uint32_t w, uint32_t D, uint32_t J) { return (w % D) * J + w / D; }
+// 32: distinct banks for every D.  The slot is transposed_slot(w, D, J) (hz_plan.h).
 inline uint32_t tuner_plane(uint32_t D, uint32_t J) {
     const uint32_t p = D * J;
     return p + (48u - p % 32u) % 32u;
@@ -110,13 +106,13 @@ inline Geom tuner_geom(uint32_t K, uint32_t D, uint32_t Q) {
 // Element (row, j) of A, j = 2 q + c the inner index (c = 0: the factor of a.re, c = 1: of a.im).  Lane l of
 // v_mfma_f32_16x16x4_f32 holds A[l & 15][l >> 4] of a 16 x 4 block: for each 16-row tile and each k-step the 64 lanes'
 // values are contiguous.
-HZ_DP_HD inline size_t tuner_a_index(uint32_t row, uint32_t j, uint32_t steps) {
+HZ_HD size_t tuner_a_index(uint32_t row, uint32_t j, uint32_t steps) {
     return ((size_t)(row / 16) * steps + j / 4) * 64 + (j % 4) * 16 + row % 16;
 }
 
 // tile `tile` of a push whose first output has `rel`, chunk `chunk`: the relative index (from the push's first sample)
 // of window sample 0, which is the sample of the tile's first output at the chunk's LAST q, qa + cq - 1
-HZ_DP_HD inline int64_t tuner_window_base(uint32_t rel, uint32_t D, uint32_t T, uint32_t cq, uint64_t tile, uint32_t chunk) {
+HZ_HD int64_t tuner_window_base(uint32_t rel, uint32_t D, uint32_t T, uint32_t cq, uint64_t tile, uint32_t chunk) {
     return (int64_t)(rel + tile * ((uint64_t)T * D)) - (int64_t)((uint64_t)chunk * cq + cq - 1);  // below 2^63: Step.ok
 }
 

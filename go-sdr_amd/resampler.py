@@ -15,10 +15,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import _is_torch, ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib, MEM_HOST  # noqa: F401
+from . import ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib  # noqa: F401
+from ._rows import cut, device_like, rows_input, rows_output
 from ._capi import RESAMPLER_FORM_DIRECT, RESAMPLER_FORM_TAPS_GLOBAL, RESAMPLER_FORM_TAPS_UNIFORM, RESAMPLER_FORM_WINDOW_PADDED
 
-_NP_IN = {FMT_C64: (np.complex64, 8), FMT_U8: (np.uint8, 2), FMT_I8: (np.int8, 2), FMT_I16: (np.int16, 4)}
 
 
 def resampler_taps(up, down, taps_per_phase=16, beta=8.0):
@@ -73,94 +73,23 @@ class Resampler:
         self.ctx._ck(lib.hzsdr_resampler_plan(self._h, C.byref(t), C.byref(f)))
         return t.value, f.value
 
-    def _input(self, x):
-        """-> (pointer, samples per row, row pitch in samples) of a block of the source format."""
-        dt, size = _NP_IN[self.src_fmt]
-        torch_in = _is_torch(x)
-        if torch_in:
-            import torch
-            tdt = {np.complex64: torch.complex64, np.uint8: torch.uint8, np.int8: torch.int8, np.int16: torch.int16}[dt]
-            if x.dtype != tdt:
-                raise ValueError("resampler: samples are not of the source format")
-            strides, ptr, item = tuple(x.stride()), x.data_ptr(), x.element_size()
-        else:
-            if x.dtype != dt:
-                raise ValueError("resampler: samples are not of the source format")
-            item = x.dtype.itemsize
-            strides, ptr = tuple(s // item for s in x.strides), x.ctypes.data
-        shape = tuple(x.shape)
-        per = size // item  # elements per sample: 1 for complex64, 2 (I, Q) otherwise
-        if per == 2:
-            if not shape or shape[-1] != 2 or (strides[-1] != 1 and shape[-1] > 1):
-                raise ValueError("resampler: samples of this format are (..., n, 2)")
-            shape, strides = shape[:-1], strides[:-1]
-        if self.streams == 1 and len(shape) == 1:
-            shape, strides = (1,) + shape, (0,) + strides
-        if len(shape) != 2 or shape[0] != self.streams:
-            raise ValueError("resampler: input is (n,) for one stream, (streams, n) otherwise")
-        n = int(shape[1])
-        if n == 0:
-            return None, 0, 0
-        if (n > 1 and strides[1] != per) or (self.streams > 1 and (strides[0] % per or strides[0] // per < n)):
-            raise ValueError("resampler: rows are contiguous, their pitch at least the samples of a row")
-        return ptr, n, int(strides[0] // per) if self.streams > 1 else n
-
-    def _empty(self, count, like):
-        shape = (count,) if self.streams == 1 else (self.streams, count)
-        if _is_torch(like):
-            import torch
-            return torch.empty(shape, dtype=torch.complex64, device=like.device)
-        return np.empty(shape, np.complex64)
-
-    def _output(self, out, count, like):
-        """-> (out, pointer, capacity, pitch) of a complex64 destination: (cap,) for one stream, (streams, cap) rows
-        with unit stride along a row and any pitch otherwise."""
-        if out is None:
-            out = self._empty(count, like)
-        torch_out = _is_torch(out)
-        if torch_out:
-            import torch
-            ok = out.dtype == torch.complex64
-            strides, ptr = tuple(out.stride()), out.data_ptr()
-        else:
-            ok = out.dtype == np.complex64
-            strides, ptr = tuple(s // 8 for s in out.strides), out.ctypes.data
-        if not ok:
-            raise ValueError("resampler: the destination is complex64")
-        if self.streams == 1:
-            if out.ndim != 1 or (out.shape[0] > 1 and strides[0] != 1):
-                raise ValueError("resampler: the destination of one stream is a contiguous (cap,)")
-            return out, ptr, int(out.shape[0]), int(out.shape[0])
-        if out.ndim != 2 or out.shape[0] != self.streams or (out.shape[1] > 1 and strides[1] != 1) or strides[0] < out.shape[1]:
-            raise ValueError("resampler: the destination is (streams, cap) with contiguous rows")
-        return out, ptr, int(out.shape[1]), int(strides[0])
-
-    def _like(self):
-        if self.ctx.memspace == MEM_HOST:
-            return None
-        import torch
-        return torch.empty(0, device=f"cuda:{self.ctx.device}")
-
-    def _cut(self, out, got):
-        return out[:got] if self.streams == 1 else out[:, :got]
-
     def push(self, samples, out=None):
         """Consume every sample of every row of `samples`; return the outputs they complete.  `out`, when given, is a
         complex64 buffer ((cap,), or (streams, cap) with any row pitch; columns past the outputs written are left as
         they are); the result is its written part."""
-        ptr, n, pitch = self._input(samples)
-        out, optr, cap, opitch = self._output(out, self.outputs_for(n), samples)
+        ptr, n, pitch = rows_input(samples, self.src_fmt, self.streams, "resampler")
+        out, optr, cap, opitch = rows_output(out, self.outputs_for(n), samples, self.streams, np.complex64, "resampler")
         got = C.c_size_t(0)
         self.ctx._ck(lib.hzsdr_resampler_push(self._h, ptr, n, pitch, optr if cap else None, cap, opitch, C.byref(got)))
-        return self._cut(out, got.value)
+        return cut(out, self.streams, got.value)
 
     def flush(self, out=None):
         """The outputs that still depend on samples pushed, the samples behind the last one taken as zero; the
         resampler starts over.  Pushes and flush together have scipy.signal.upfirdn's length."""
-        out, optr, cap, opitch = self._output(out, self.pending()[2], self._like())
+        out, optr, cap, opitch = rows_output(out, self.pending()[2], device_like(self.ctx), self.streams, np.complex64, "resampler")
         got = C.c_size_t(0)
         self.ctx._ck(lib.hzsdr_resampler_flush(self._h, optr if cap else None, cap, opitch, C.byref(got)))
-        return self._cut(out, got.value)
+        return cut(out, self.streams, got.value)
 
     def reset(self):
         self.ctx._ck(lib.hzsdr_resampler_reset(self._h))

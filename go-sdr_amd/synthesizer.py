@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _is_torch, _ptr, ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib, MEM_HOST  # noqa: F401
 from ._capi import CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR
+from ._rows import device_like, torch_dtype
 from .channelizer import _LAYOUTS
 from .spectrum import NegativeFirst, ZeroFirst, _order
 
@@ -71,8 +72,7 @@ class Synthesizer:
         dt, tail = _NP_OUT[self.dst_fmt]
         if _is_torch(like):
             import torch
-            tdt = {np.complex64: torch.complex64, np.uint8: torch.uint8, np.int8: torch.int8, np.int16: torch.int16}[dt]
-            return torch.empty((n,) + tail, dtype=tdt, device=like.device)
+            return torch.empty((n,) + tail, dtype=torch_dtype(dt), device=like.device)
         return np.empty((n,) + tail, dt)
 
     def _input(self, frames):
@@ -120,11 +120,7 @@ class Synthesizer:
         `out` the result is a numpy array in a HOST context and a torch tensor on the context's device otherwise."""
         held = self.pending()[0]
         if out is None:
-            like = None
-            if self.ctx.memspace != MEM_HOST:
-                import torch
-                like = torch.empty(0, device=f"cuda:{self.ctx.device}")
-            out = self._empty(held, like)
+            out = self._empty(held, device_like(self.ctx))
         cap = int(out.shape[0])
         got = C.c_size_t(0)
         self.ctx._ck(lib.hzsdr_synthesizer_flush(self._h, _ptr(out) if cap else None, cap, C.byref(got)))

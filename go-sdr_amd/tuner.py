@@ -18,10 +18,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import _is_torch, ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib, MEM_HOST  # noqa: F401
+from . import ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib  # noqa: F401
+from ._rows import cut, device_like, rows_input, rows_output
 from ._capi import TUNER_FORM_CHUNKED, TUNER_FORM_TRANSPOSED, TUNER_READ_T0, TUNER_READ_T1, TUNER_READ_T2, TUNER_READ_TAPS
 
-_NP_IN = {FMT_C64: (np.complex64, 8), FMT_U8: (np.uint8, 2), FMT_I8: (np.int8, 2), FMT_I16: (np.int16, 4)}
 _READ_LEN = {TUNER_READ_T2: 2048, TUNER_READ_T1: 2048, TUNER_READ_T0: 1024}
 
 
@@ -92,79 +92,23 @@ class TunerBank:
         self.ctx._ck(lib.hzsdr_tuner_readout(self._h, int(what), int(index), out.ctypes.data, n))
         return out
 
-    def _input(self, x):
-        """-> (pointer, samples) of a block of the source format."""
-        dt, size = _NP_IN[self.src_fmt]
-        if _is_torch(x):
-            import torch
-            tdt = {np.complex64: torch.complex64, np.uint8: torch.uint8, np.int8: torch.int8, np.int16: torch.int16}[dt]
-            ok, contiguous, ptr = x.dtype == tdt, x.is_contiguous(), x.data_ptr()
-        else:
-            ok, contiguous, ptr = x.dtype == dt, x.flags.c_contiguous, x.ctypes.data
-        if not ok:
-            raise ValueError("tuner bank: samples are not of the source format")
-        shape = tuple(x.shape)
-        if size == 8 and len(shape) != 1 or size != 8 and (len(shape) != 2 or shape[1] != 2):
-            raise ValueError("tuner bank: samples are (n,) complex64 or (n, 2) of the byte and int16 formats")
-        if shape[0] and not contiguous:
-            raise ValueError("tuner bank: samples are contiguous")
-        return (ptr if shape[0] else None), int(shape[0])
-
-    def _empty(self, count, like):
-        shape = (count,) if self.tuners == 1 else (self.tuners, count)
-        if _is_torch(like):
-            import torch
-            return torch.empty(shape, dtype=torch.complex64, device=like.device)
-        return np.empty(shape, np.complex64)
-
-    def _output(self, out, count, like):
-        """-> (out, pointer, capacity, pitch) of a complex64 destination: (cap,) for one tuner, (tuners, cap) rows with
-        unit stride along a row and any pitch otherwise."""
-        if out is None:
-            out = self._empty(count, like)
-        if _is_torch(out):
-            import torch
-            ok = out.dtype == torch.complex64
-            strides, ptr = tuple(out.stride()), out.data_ptr()
-        else:
-            ok = out.dtype == np.complex64
-            strides, ptr = tuple(s // 8 for s in out.strides), out.ctypes.data
-        if not ok:
-            raise ValueError("tuner bank: the destination is complex64")
-        if self.tuners == 1:
-            if out.ndim != 1 or (out.shape[0] > 1 and strides[0] != 1):
-                raise ValueError("tuner bank: the destination of one tuner is a contiguous (cap,)")
-            return out, ptr, int(out.shape[0]), int(out.shape[0])
-        if out.ndim != 2 or out.shape[0] != self.tuners or (out.shape[1] > 1 and strides[1] != 1) or strides[0] < out.shape[1]:
-            raise ValueError("tuner bank: the destination is (tuners, cap) with contiguous rows")
-        return out, ptr, int(out.shape[1]), int(strides[0])
-
-    def _like(self):
-        if self.ctx.memspace == MEM_HOST:
-            return None
-        import torch
-        return torch.empty(0, device=f"cuda:{self.ctx.device}")
-
-    def _cut(self, out, got):
-        return out[:got] if self.tuners == 1 else out[:, :got]
-
     def push(self, samples, out=None):
         """Consume every sample; return the outputs they complete.  `out`, when given, is a complex64 buffer ((cap,), or
         (tuners, cap) with any row pitch; columns past the outputs written are left as they are); the result is its
         written part."""
-        ptr, n = self._input(samples)
-        out, optr, cap, opitch = self._output(out, self.outputs_for(n), samples)
+        ptr, n, _ = rows_input(samples, self.src_fmt, None, "tuner bank")
+        out, optr, cap, opitch = rows_output(out, self.outputs_for(n), samples, self.tuners, np.complex64, "tuner bank", "tuner")
         got = C.c_size_t(0)
         self.ctx._ck(lib.hzsdr_tuner_push(self._h, ptr, n, optr if cap else None, cap, opitch, C.byref(got)))
-        return self._cut(out, got.value)
+        return cut(out, self.tuners, got.value)
 
     def flush(self, out=None):
         """The outputs that still depend on samples pushed, the samples behind the last one taken as zero; the bank
         starts over.  Pushes and flush together have scipy.signal.upfirdn(taps, z, 1, down)'s length."""
-        out, optr, cap, opitch = self._output(out, self.pending()[2], self._like())
+        out, optr, cap, opitch = rows_output(out, self.pending()[2], device_like(self.ctx), self.tuners, np.complex64, "tuner bank", "tuner")
         got = C.c_size_t(0)
         self.ctx._ck(lib.hzsdr_tuner_flush(self._h, optr if cap else None, cap, opitch, C.byref(got)))
-        return self._cut(out, got.value)
+        return cut(out, self.tuners, got.value)
 
     def reset(self):
         self.ctx._ck(lib.hzsdr_tuner_reset(self._h))

@@ -142,8 +142,8 @@ static void check_geometry(uint32_t M, size_t *largest, uint32_t *largest_m, int
     for (uint32_t k = 0; k < M; k++) CHECK(pseen[k] == 1, "M=%u", M);
 
     // the division by multiplication, the rotation of a tile's frames and the load offsets
-    const uint64_t magic = cp::chanbank_magic(M);
-    for (uint32_t w = 0; w <= 254 + 63 * 255; w++) CHECK(cp::chanbank_div(w, magic) == w / M, "M=%u w=%u", M, w);
+    const uint64_t magic = div_magic(M);
+    for (uint32_t w = 0; w <= 254 + 63 * 255; w++) CHECK(div_by_magic(w, magic) == w / M, "M=%u w=%u", M, w);
     for (uint32_t s = 0; s < M; s++)
         for (uint32_t r = 0; r < M; r++) {
             const uint32_t o = cp::chanbank_offset(r, s, M);

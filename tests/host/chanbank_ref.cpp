@@ -73,7 +73,7 @@ static std::vector<c32> tiled(uint32_t M, uint32_t P, uint32_t D, const std::vec
     const cp::Geom geo = cp::chanbank_geom(M);
     const uint32_t L = P * M;
     const std::vector<float> A = cp::chanbank_fill_a(geo, W);
-    const uint64_t magic = cp::chanbank_magic(M);
+    const uint64_t magic = div_magic(M);
     std::vector<c32> y, tail;
     std::vector<float> B(geo.b_floats);
     cp::State st{};
@@ -92,7 +92,7 @@ static std::vector<c32> tiled(uint32_t M, uint32_t P, uint32_t D, const std::vec
             const uint32_t rot0 = cp::chanbank_rot(st.rot, f0, D, M);
             for (uint32_t fl = 0; fl < geo.T; fl++) {
                 const uint64_t f = f0 + fl;
-                const uint32_t w = rot0 + fl * D, s = w - cp::chanbank_div(w, magic) * M;
+                const uint32_t w = rot0 + fl * D, s = w - div_by_magic(w, magic) * M;
                 for (uint32_t r = 0; r < geo.Mp; r++) {
                     c32 acc{0.0f, 0.0f};
                     if (f < p.F && r < M) {

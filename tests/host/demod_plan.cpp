@@ -12,7 +12,7 @@
 //     into it;
 //   - the reciprocal of D is exact on the window's range;
 //   - the kernel's stepped slot (from tap to tap: one row up, or from row 0 to the last row of the column before) is
-//     demod_slot of the window index, for every tap, the first and the last lane and chain;
+//     transposed_slot of the window index, for every tap, the first and the last lane and chain;
 //   - the lanes per bank of each 32-lane half of a read, for EVERY window base (every tap of every chain): the table
 //     "banks: D worst" is printed, one line per D, and the condition is 1 for odd D and at most 2 for even D.
 // Prints "demod_plan ok".
@@ -45,7 +45,7 @@ static int worst_bank(const Geom &g, uint32_t D, uint32_t c, uint32_t lanes) {
     for (uint32_t half = 0; half < 64; half += 32) {
         int n[32] = {0};
         for (uint32_t l = half; l < half + 32 && l < lanes; l++) {
-            const int v = ++n[demod_slot(l * D + c, D, g.J) % 32];
+            const int v = ++n[hz::transposed_slot(l * D + c, D, g.J) % 32];
             if (v > worst) worst = v;
         }
     }
@@ -57,10 +57,10 @@ int main(int argc, char **argv) {
     size_t largest = 0;
     uint32_t ld = 0, lq = 0;
     for (uint32_t D = 1; D <= kMaxDown; D++) {
-        const uint64_t magic = demod_magic(D);
+        const uint64_t magic = hz::div_magic(D);
         for (uint32_t w = 0; w < kDivRange; w += D) {
-            CHECK(demod_div(w, magic) == w / D, "D=%u w=%u", D, w);
-            if (w) CHECK(demod_div(w - 1, magic) == (w - 1) / D, "D=%u w=%u", D, w - 1);
+            CHECK(hz::div_by_magic(w, magic) == w / D, "D=%u w=%u", D, w);
+            if (w) CHECK(hz::div_by_magic(w - 1, magic) == (w - 1) / D, "D=%u w=%u", D, w - 1);
         }
         int banks = 0;
         for (uint32_t Q = 1; Q <= kMaxTaps; Q++) {
@@ -75,16 +75,16 @@ int main(int argc, char **argv) {
                 const uint32_t w2 = (2 * g.T - 1) * D + Q, j2 = ((w2 + D - 1) / D) | 1u;
                 CHECK(D * j2 > kWindowMax, "D=%u Q=%u: T %u though %u fits", D, Q, g.T, 2 * g.T);
             }
-            CHECK(g.row0 == (Q - 1) % D && g.slot0 == demod_slot(Q - 1, D, g.J), "slot0");
+            CHECK(g.row0 == (Q - 1) % D && g.slot0 == hz::transposed_slot(Q - 1, D, g.J), "slot0");
             if (g.lds_bytes > largest) largest = g.lds_bytes, ld = D, lq = Q;
             if (!(Q <= 9 || Q % 97 == 0 || Q == kMaxTaps || Q == 129 || Q == 513 || Q == 757)) continue;
             // a bijection into the request
             std::vector<unsigned char> seen((size_t)D * g.J, 0);
             for (uint32_t w = 0; w < g.window; w++) {
-                const uint32_t s = demod_slot(w, D, g.J);
+                const uint32_t s = hz::transposed_slot(w, D, g.J);
                 CHECK(s < D * g.J && !seen[s], "D=%u Q=%u w=%u slot %u", D, Q, w, s);
                 if (s < D * g.J) seen[s] = 1;
-                const uint32_t j = demod_div(w, magic);  // the kernel's store
+                const uint32_t j = hz::div_by_magic(w, magic);  // the kernel's store
                 CHECK((w - j * D) * g.J + j == s, "store w=%u", w);
             }
             // the stepped slot, and the banks of every read
@@ -95,7 +95,7 @@ int main(int argc, char **argv) {
                 for (uint32_t r = 0; r < chains; r++)
                     for (uint32_t tid : {0u, 31u, 32u, lanes - 1}) {
                         const uint32_t w = (tid + r * kThreads) * D + (Q - 1 - q);
-                        CHECK(w < g.window && off + tid + r * kThreads == demod_slot(w, D, g.J), "D=%u Q=%u q=%u tid=%u r=%u", D, Q, q, tid, r);
+                        CHECK(w < g.window && off + tid + r * kThreads == hz::transposed_slot(w, D, g.J), "D=%u Q=%u q=%u tid=%u r=%u", D, Q, q, tid, r);
                     }
                 // (a wave's 64 lanes from any wave of any chain: the base c = wave's first output * D + Q - 1 - q)
                 for (uint32_t first = 0; first < g.T; first += 64) {

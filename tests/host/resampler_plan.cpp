@@ -37,12 +37,12 @@ static int failures = 0;
 // the kernel's lane arithmetic for every output of a tile against plain 64-bit division
 static void lanes(long lineno, const State &s, uint32_t U, uint32_t D, uint32_t Q, const Geom &g, uint64_t tile) {
     const Tile t = resampler_tile(s.rel, s.phi, U, D, Q, g.T, tile);
-    const uint64_t magic = resampler_magic(U);
+    const uint64_t magic = hz::div_magic(U);
     const uint64_t base = (uint64_t)s.rel * U + s.phi + tile * ((uint64_t)g.T * D);
     for (uint32_t tid = 0; tid < (uint32_t)kThreads; tid++) {
         const uint32_t u = t.phi + tid * D;
         CHECK(u < kDivRange, "u=%u", u);
-        uint32_t i = resampler_div(u, magic), phi = u - i * U;
+        uint32_t i = hz::div_by_magic(u, magic), phi = u - i * U;
         for (uint32_t r = 0; r < g.T / kThreads; r++) {
             const uint64_t tt = base + (uint64_t)(tid + r * kThreads) * D;
             CHECK(phi < U && tt / U == t.i0 + i && tt % U == phi, "U=%u D=%u tid=%u r=%u", U, D, tid, r);
@@ -61,12 +61,12 @@ int main(int argc, char **argv) {
     long lineno = 0;
     // the reciprocal: floor(u / U) can only first go wrong just below or at a multiple of U
     for (uint32_t U = 1; U <= kMaxRate; U++) {
-        const uint64_t magic = resampler_magic(U);
+        const uint64_t magic = hz::div_magic(U);
         for (uint32_t u = 0; u < kDivRange; u += U) {
-            CHECK(resampler_div(u, magic) == u / U, "U=%u u=%u", U, u);
-            if (u) CHECK(resampler_div(u - 1, magic) == (u - 1) / U, "U=%u u=%u", U, u - 1);
+            CHECK(hz::div_by_magic(u, magic) == u / U, "U=%u u=%u", U, u);
+            if (u) CHECK(hz::div_by_magic(u - 1, magic) == (u - 1) / U, "U=%u u=%u", U, u - 1);
         }
-        CHECK(resampler_div(kDivRange - 1, magic) == (kDivRange - 1) / U, "U=%u", U);
+        CHECK(hz::div_by_magic(kDivRange - 1, magic) == (kDivRange - 1) / U, "U=%u", U);
         // every shape's offsets stay inside that range, its LDS inside the budget
         for (uint32_t D = 1; D <= kMaxRate; D += (U % 7 == 0 ? 1 : 61))
             for (uint32_t Q : {1u, 2u, 7u, 64u, 256u}) {

@@ -11,7 +11,7 @@
 //   - for every D <= 256 and every Q <= 1024: the geometry's identities, the LDS request inside the budget, the tile the
 //     largest that is, the chunk the largest that is, chunks * cq covering Qp; the plane pitch 16 modulo 32;
 //   - for every D and a spread of Q: the reciprocal of D exact on the window's range; the layout a bijection of the
-//     window into a plane; the kernel's stepped slot (two samples down per k-step) equal to tuner_slot for every lane
+//     window into a plane; the kernel's stepped slot (two samples down per k-step) equal to transposed_slot for every lane
 //     and both column tiles; the banks of every B-operand read (32 lanes: 16 of the re plane, 16 of the im plane) all
 //     distinct;
 //   - for a spread of K and Q: tuner_a_index a bijection of (row, j) onto [0, a_floats), and the 64 values of one row
@@ -43,13 +43,13 @@ static long lineno = 0;
 
 static void check_layout(uint32_t D, uint32_t Q) {
     const Geom g = tuner_geom(1, D, Q);
-    const uint64_t magic = tuner_magic(D);
+    const uint64_t magic = hz::div_magic(D);
     std::vector<unsigned char> seen((size_t)D * g.J, 0);
     for (uint32_t w = 0; w < g.window; w++) {
-        const uint32_t s = tuner_slot(w, D, g.J);
+        const uint32_t s = hz::transposed_slot(w, D, g.J);
         CHECK(s < D * g.J && s < g.plane && !seen[s], "D=%u Q=%u w=%u slot %u", D, Q, w, s);
         if (s < D * g.J) seen[s] = 1;
-        const uint32_t j = tuner_div(w, magic);  // the kernel's store
+        const uint32_t j = hz::div_by_magic(w, magic);  // the kernel's store
         CHECK(j == w / D && (w - j * D) * g.J + j == s, "store w=%u", w);
     }
     // the kernel's walk: lane (n, kk) of the wave at outputs wo * 32, both column tiles, every k-step of a chunk
@@ -58,7 +58,7 @@ static void check_layout(uint32_t D, uint32_t Q) {
         uint32_t row[64], off[64];
         for (uint32_t l = 0; l < 64; l++) {
             const uint32_t w0 = (wo * 32 + (l & 15)) * D + (g.cq - 1) - (l >> 5);
-            const uint32_t col = tuner_div(w0, magic);
+            const uint32_t col = hz::div_by_magic(w0, magic);
             row[l] = w0 - col * D;
             off[l] = row[l] * g.J + col;
         }
@@ -69,7 +69,7 @@ static void check_layout(uint32_t D, uint32_t Q) {
                     for (uint32_t l = half; l < half + 32; l++) {
                         const uint32_t ml = wo * 32 + ct * 16 + (l & 15), q = 2 * s + (l >> 5);
                         const uint32_t w = ml * D + (g.cq - 1 - q);
-                        CHECK(w < g.window && off[l] + 16 * ct == tuner_slot(w, D, g.J), "D=%u Q=%u s=%u lane %u", D, Q, s, l);
+                        CHECK(w < g.window && off[l] + 16 * ct == hz::transposed_slot(w, D, g.J), "D=%u Q=%u s=%u lane %u", D, Q, s, l);
                         const uint32_t addr = ((l >> 4) & 1u) * g.plane + off[l] + 16 * ct;
                         CHECK(addr < 2 * g.plane, "address %u", addr);
                         CHECK(++banks[addr % 32] == 1, "D=%u Q=%u s=%u: two lanes of a read on bank %u", D, Q, s, addr % 32);
@@ -106,10 +106,10 @@ int main(int argc, char **argv) {
     uint32_t ld = 0, lq = 0;
     long chunked = 0;
     for (uint32_t D = 1; D <= kMaxDown; D++) {
-        const uint64_t magic = tuner_magic(D);
+        const uint64_t magic = hz::div_magic(D);
         for (uint32_t w = 0; w < kDivRange; w += D) {
-            CHECK(tuner_div(w, magic) == w / D, "D=%u w=%u", D, w);
-            if (w) CHECK(tuner_div(w - 1, magic) == (w - 1) / D, "D=%u w=%u", D, w - 1);
+            CHECK(hz::div_by_magic(w, magic) == w / D, "D=%u w=%u", D, w);
+            if (w) CHECK(hz::div_by_magic(w - 1, magic) == (w - 1) / D, "D=%u w=%u", D, w - 1);
         }
         for (uint32_t Q = 1; Q <= kMaxTaps; Q++) {
             const Geom g = tuner_geom(7, D, Q);

@@ -211,6 +211,51 @@ def test_host_context_and_pitch(hz, ctx, hctx, m, p, d, fmt):
         assert same(run(hbank, raw, [n // 3]), run(bank, dev(raw)))
 
 
+ZERO_COPY_MAX = 2 << 20  # Stage's kZeroCopyMax: up to this many bytes in total, a HOST call's dense buffers go through the pinned staging area
+
+
+def test_host_channel_major_routes(hz, ctx, hctx):
+    """HOST context, channel-major, M = 12, P = 3, D = 11, u8, every result bit for bit the DEVICE context's dense one:
+    a dense destination (stride == frames) under and over the staging limit in total bytes; a pitched destination in
+    ordinary memory and inside pinned_samples memory, the pitch gap and the values behind the last row intact; a push
+    too short to complete a frame into either, which writes nothing and keeps its samples for the next."""
+    m, p, d, fmt = 12, 3, 11, "u8"
+    g = ref.taps_of(m, p)
+    mark = np.complex64(-7.5 + 3.25j)
+    with make(hz, ctx, fmt, m, g, d, "neg", "channels") as bank, make(hz, hctx, fmt, m, g, d, "neg", "channels") as hbank:
+        for frames, over in ((None, False), (22000, True)):
+            n = stream_length(bank, frames)
+            raw = white(fmt, n, 77 + n)
+            bank.reset()
+            dense = run(bank, dev(raw))
+            f = dense.shape[1]
+            assert (m * f * 8 > ZERO_COPY_MAX) if over else (m * f * 8 + raw.nbytes + 512 <= ZERO_COPY_MAX)
+            hbuf = np.full(m * f + 8, mark, np.complex64)
+            hbank.reset()
+            rows = hbank.push(raw, out=hbuf[:m * f].reshape(m, f))
+            assert rows.shape == (m, f) and rows.strides[0] == 8 * f
+            assert same(rows, dense), f"dense rows of {f} frames differ from the DEVICE context's"
+            assert bool((hbuf[m * f:] == mark).all()), "values behind the last row were touched"
+        # (raw, dense, f: the short stream from here on)
+        n = stream_length(bank)
+        raw = white(fmt, n, 77 + n)
+        bank.reset()
+        dense = run(bank, dev(raw))
+        f, w, short = dense.shape[1], dense.shape[1] + 9, m * p - 1
+        pinned = hctx.pinned_samples(hz.FMT_C64, m * w + 8)
+        for flat in (np.empty(m * w + 8, np.complex64), pinned):
+            flat[:] = mark
+            buf = flat[:m * w].reshape(m, w)
+            hbank.reset()
+            none = hbank.push(raw[:short], out=buf)
+            assert none.shape == (m, 0) and hbank.pending()[0] == short
+            assert bool((flat == mark).all()), "a push that completes no frame wrote"
+            rows = hbank.push(raw[short:], out=buf)
+            assert rows.shape == (m, f) and rows.strides[0] == 8 * w
+            assert same(rows, dense), "pitched rows differ from the DEVICE context's dense ones"
+            assert bool((buf[:, f:] == mark).all()) and bool((flat[m * w:] == mark).all()), "the pitch gap or the values behind the rows were touched"
+
+
 # ---- 5. against the tuner bank --------------------------------------------------------------------------
 
 def test_against_the_tuner_bank(hz, ctx):

@@ -340,6 +340,50 @@ def test_channel_major_pitch_leaves_the_rest(hz, ctx, hctx):
         ch.close()
 
 
+ZERO_COPY_MAX = 2 << 20  # Stage's kZeroCopyMax: up to this many bytes in total, a HOST call's dense buffers go through the pinned staging area
+
+
+def test_host_channel_major_routes(hz, ctx, hctx):
+    """HOST context, channel-major, M = 256, P = 2, hop 192, i16, every result bit for bit the DEVICE context's dense
+    one: a dense destination (stride == frames) under and over the staging limit in total bytes; a pitched destination
+    in ordinary memory and inside pinned_samples memory, the pitch gap and the values behind the last row intact; a
+    push too short to complete a frame into either, which writes nothing and keeps its samples for the next."""
+    m, p, d = 256, 2, 192
+    g = hz.channelizer_taps(m, p)
+    sentinel = np.complex64(complex(-7.0, 9.0))
+    dch = ctx.channelizer(hz.FMT_I16, m, g, hop=d, order=hz.NEGATIVE_FIRST, layout="channels")
+    hch = hctx.channelizer(hz.FMT_I16, m, g, hop=d, order=hz.NEGATIVE_FIRST, layout="channels")
+    for frames, over in ((11, False), (1030, True)):
+        xh = raw("i16", (frames - 1) * d + p * m + 100, seed=frames)
+        dch.reset()
+        want = bits(push_all(dch, dev(xh)))
+        assert (m * frames * 8 > ZERO_COPY_MAX) if over else (m * frames * 8 + xh.nbytes + 512 <= ZERO_COPY_MAX)
+        flat = np.full(m * frames + 8, sentinel, np.complex64)
+        hch.reset()
+        got = hch.push(xh, out=flat[:m * frames].reshape(m, frames))
+        assert tuple(got.shape) == (m, frames)
+        assert torch.equal(bits(got), want), f"dense rows of {frames} frames differ from the DEVICE context's"
+        assert (flat[m * frames:] == sentinel).all(), "values behind the last row were touched"
+    frames, w, short = 11, 16, p * m - 1
+    xh = raw("i16", (frames - 1) * d + p * m + 100, seed=frames)
+    dch.reset()
+    want = bits(push_all(dch, dev(xh)))
+    pinned = hctx.pinned_samples(hz.FMT_C64, m * w + 8)
+    for flat in (np.empty(m * w + 8, np.complex64), pinned):
+        flat[:] = sentinel
+        out = flat[:m * w].reshape(m, w)
+        hch.reset()
+        none = hch.push(xh[:short], out=out)
+        assert tuple(none.shape) == (m, 0) and hch.pending()[0] == short
+        assert (flat == sentinel).all(), "a push that completes no frame wrote"
+        got = hch.push(xh[short:], out=out)
+        assert tuple(got.shape) == (m, frames)
+        assert torch.equal(bits(got), want), "pitched rows differ from the DEVICE context's dense ones"
+        assert (out[:, frames:] == sentinel).all() and (flat[m * w:] == sentinel).all(), "the pitch gap or the values behind the rows were touched"
+    dch.close()
+    hch.close()
+
+
 # ---- 6. host logic and state -----------------------------------------------------------------------
 
 @pytest.mark.parametrize("fmt", ["u8", "i8", "i16", "c64"])

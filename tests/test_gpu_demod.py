@@ -318,6 +318,37 @@ def test_streams_and_pitch(hz, ctx, hctx, streams, fmt, mode, q, down):
         o.close()
 
 
+def test_host_pitched_rows_both_ways(hz, ctx, hctx):
+    """3 streams, HOST context, input AND output with a pitch in one call: both from ordinary memory (each takes the 2-D
+    copy), then both inside pinned_samples memory (the kernel reads and writes the caller's rows).  Bit for bit the
+    DEVICE context's dense result; the output's pitch gap and the values behind its last row intact."""
+    streams, fmt, q, down, pad = 3, "c64", 33, 5, 7
+    h = taps_of(q)
+    dm = ctx.demodulator(FMT[fmt], hz.DEMOD_FM, h, down, streams=streams)
+    hdm = hctx.demodulator(FMT[fmt], hz.DEMOD_FM, h, down, streams=streams)
+    n = (dm.plan()[0] + 37) * down + 1
+    x = white(fmt, streams * n, seed=91).reshape(streams, n)
+    want = run(dm, dev(x), [0, n // 3, n])
+    total = want.shape[1]
+    wi, wo = n + pad, total + pad
+    srcs = (np.empty(streams * wi, np.complex64), hctx.pinned_samples(hz.FMT_C64, streams * wi))
+    dsts = (np.empty(streams * wo + 8, np.float32), hctx.pinned_samples(hz.FMT_C64, streams * wo + 8).view(np.float32)[:streams * wo + 8])
+    for src, dst in zip(srcs, dsts):
+        wide = src.reshape(streams, wi)
+        wide[:] = np.complex64(complex(5.0, -5.0))
+        wide[:, :n] = x
+        dst[:] = np.float32(np.nan)
+        out = dst[:streams * wo].reshape(streams, wo)
+        done = 0
+        for part in (wide[:, :n // 3], wide[:, n // 3:n], None):
+            w = hdm.push(part, out=out[:, done:]) if part is not None else hdm.flush(out=out[:, done:])
+            done += w.shape[1]
+        assert done == total and same(out[:, :total], want), "pitched rows differ from the DEVICE context's dense ones"
+        assert np.isnan(out[:, total:]).all() and np.isnan(dst[streams * wo:]).all(), "the pitch gap or the values behind the rows were touched"
+    dm.close()
+    hdm.close()
+
+
 # ---- 5. sub-slices ---------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("fmt,start", [("u8", 1), ("u8", 3), ("i16", 1), ("i16", 3), ("c64", 1)])

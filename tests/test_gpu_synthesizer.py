@@ -233,6 +233,28 @@ def test_cuts_spaces_layouts_orders_runs_bit_identical(hz, ctx, hctx, m, p, d):
     ng.close()
 
 
+def test_host_channel_major_pitched_input(hz, ctx, hctx):
+    """HOST context, M = 256, P = 2, channel-major input with a pitch above the frame count, from ordinary and from
+    pinned_samples memory: the samples are the DEVICE context's, bit for bit, and the input is left as it was."""
+    m, p, d = 256, 2, 192
+    f = 2 * xpb(m) + 11
+    g = hz.channelizer_taps(m, p)
+    yh = frames_of(f, m, seed=41)
+    z = ctx.synthesizer(hz.FMT_C64, m, g, hop=d, order=hz.ZERO_FIRST, layout="channels")
+    whole = run(z, dev(np.ascontiguousarray(yh.T)))
+    z.close()
+    assert whole.shape[0] == (f - 1) * d + p * m
+    h = hctx.synthesizer(hz.FMT_C64, m, g, hop=d, order=hz.ZERO_FIRST, layout="channels")
+    for flat in (np.empty(m * (f + 5), np.complex64), hctx.pinned_samples(hz.FMT_C64, m * (f + 5))):
+        wide = flat.reshape(m, f + 5)
+        wide[:] = np.complex64(complex(3.0, -2.0))
+        wide[:, :f] = yh.T
+        before = wide.copy()
+        assert torch.equal(bits(run(h, wide[:, :f])), bits(whole)), "pitched channel-major input differs from the DEVICE context's"
+        assert wide.tobytes() == before.tobytes()
+    h.close()
+
+
 def test_internal_groups_bit_identical(hz, ctx):
     """A push longer than two internal groups against the same frames in pushes of 1000."""
     m, p, d = 256, 2, 64
