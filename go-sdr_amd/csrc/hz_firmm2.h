@@ -198,12 +198,20 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     constexpr bool kPlane = STRAIGHT && D == 8 && (EXP & (1 << 29)) != 0;
     static_assert(!kPlane || (EXP & (256 | 524288 | (1 << 23) | (1 << 27) | (1 << 28))) == 0, "not with the pair loop's experiments");
     static_assert(!kPlane || plane_form(D, NG * GS, 0), "the host sizes the LDS by plane_form");
+    // (1 << 30, with 1 << 29: the per-plane loop with the tiles interleaved over the column blocks -- a pair's B fragments
+    // are the fragments of two pairs earlier, one column block on, in the same lane: ONE tile-window read per pair instead
+    // of four; the slots in their own layout and the epilogue's exchange through LDS -- hz_firmm2_plan.h, reuse_form)
+    constexpr bool kReuse = kPlane && (EXP & (1 << 30)) != 0;
+    static_assert((EXP & (1 << 30)) == 0 || kPlane, "the re-using loop is a per-plane loop");
+    static_assert(!kReuse || ((EXP & 32768) == 0 && kXchgBytes == 2 * 64 * 16), "the landing by plain writes; two quads per lane and half in the exchange area");
     // (the per-plane loop's slots: tiles 160 bytes apart, its reads are conflict-free there -- hz_firmm2_plan.h)
     constexpr int TS = tile_stride(D, kPlane);
+    // (a tile's row in the slot)
+    auto row_at = [](int r) { return kReuse ? reuse_row_offset(r) : TS * r; };
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63;
     const int wb = blockIdx.x;
     const int n = l & 31, h = l >> 5;
-    const size_t tab_lds = table_lds(G.ne), slot_sz = slot_bytes(D, G.ks, kPlane);
+    const size_t tab_lds = table_lds(G.ne), slot_sz = form_slot_bytes(D, G.ks, kPlane, kReuse);
     uint8_t *const tabp = mm_lds;
     unsigned *const ctr = reinterpret_cast<unsigned *>(mm_lds + 2 * tab_lds);
     uint8_t *const slot = mm_lds + 2 * tab_lds + kCtlBytes + (size_t)wave * slot_sz;
@@ -234,11 +242,11 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // scratch is, and the scratch moves onto the slots of waves 0 and 1, retired by then -- behind a barrier that the
     // shipped kernel does not need; the harness asks for no LDS beyond the kernel's own)
     constexpr bool kStampShare = kPlane && (EXP & 64) != 0;
-    static_assert(!kStampShare || (8 * 16 * 8 * kWaves <= 8192 && 2 * slot_bytes(D, NG * GS, true) >= task_bytes(D, 1025)), "the shared areas fit");
+    static_assert(!kStampShare || (8 * 16 * 8 * kWaves <= 8192 && 2 * form_slot_bytes(D, NG * GS, true, kReuse) >= task_bytes(D, 1025)), "the shared areas fit");
     constexpr int kStampRows = (EXP & (1 << 24)) != 0 ? 16 : 4;
     int stamp_pass = 0;
     [[maybe_unused]] unsigned long long *const lstamp =
-        reinterpret_cast<unsigned long long *>(mm_lds + lds_bytes(D, G.ks, G.ne, G.ntaps, kPlane) - (kStampShare ? task_bytes(D, G.ntaps) : 0)) +
+        reinterpret_cast<unsigned long long *>(mm_lds + form_lds_bytes(D, G.ks, G.ne, G.ntaps, kPlane, kReuse) - (kStampShare ? task_bytes(D, G.ntaps) : 0)) +
         (size_t)wave * (8 * kStampRows);
     if constexpr ((EXP & 64) != 0) {
         for (int i = l; i < 8 * kStampRows; i += 64) lstamp[i] = 0;
@@ -320,7 +328,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     int fix_cnt = 0;
     // (the tasks' scratch in LDS behind the slots: the window's samples, the taps beside them)
     auto task_xs = [&](const Geom &G) {
-        return reinterpret_cast<float2 *>(mm_lds + 2 * table_lds(G.ne) + kCtlBytes + (kStampShare ? 0 : (size_t)kWaves * slot_bytes(D, G.ks, kPlane)));
+        return reinterpret_cast<float2 *>(mm_lds + 2 * table_lds(G.ne) + kCtlBytes + (kStampShare ? 0 : (size_t)kWaves * form_slot_bytes(D, G.ks, kPlane, kReuse)));
     };
     auto tasks_front_cold = [&](int round, const void *in, const float2 *hist, float2 *new_hist, const uint8_t *rhist, uint8_t *new_rhist,
                                 const float2 *taps, size_t n_in, const Geom &G, const Plan &L, const EwProgram &P, const Fix &F, const Batch &B) {
@@ -457,7 +465,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     stamp(9);
     auto put = [&](int q, v4i v) {
         if constexpr (FMT == HZSDR_FMT_U8) v ^= (int)0x80808080;  // b - 128 as int8
-        *reinterpret_cast<v4i *>(slot + TS * (q / PPT) + 16 * (q % PPT)) = v;
+        *reinterpret_cast<v4i *>(slot + row_at(q / PPT) + 16 * (q % PPT)) = v;
     };
     // The compiler's s_waitcnt pass keeps a load "pending" on every path it cannot prove a wait on (a conditional
     // consumer is enough), right around the pass loop; with stores in flight as well -- loads and stores return out of
@@ -472,7 +480,10 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // bytes were in flight under, EXP & 262144)
     auto land = [&](v4i(&x)[KU], bool flipped = false) {
         // piece l + 64 u is piece l % PPT of tile l / PPT + (64 / PPT) u: one address and constants
-        uint8_t *lp = slot + TS * (l / PPT) + 16 * (l % PPT);
+        // (the re-using loop's rows: 64 / PPT = 8 rows on is two whole groups of four rows on, a constant all the same)
+        uint8_t *lp = slot + row_at(l / PPT) + 16 * (l % PPT);
+        constexpr int kLandStep = kReuse ? reuse_row_offset(64 / PPT) : (64 / PPT) * TS;
+        static_assert(!kReuse || (64 / PPT) % 4 == 0, "whole groups of four rows");
         // (1 << 25: the rare un-flipped landing -- a wave's first pass, a pass behind an inactive one -- as a BRANCH.  The
         // condition is uniform, and the compiler turned `if (!flipped) x ^= c` into 40 v_xor + 40 v_cndmask executed
         // by EVERY landing: 80 of a pass's ~490 vector instructions, each of which costs the SIMD partner's matrix loop
@@ -498,7 +509,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                         x[u] ^= (int)0x80808080;  // b - 128 as int8
                     }
                 }
-                *reinterpret_cast<v4i *>(lp + u * (64 / PPT) * TS) = x[u];
+                *reinterpret_cast<v4i *>(lp + u * kLandStep) = x[u];
             }
         if constexpr (FMT == HZSDR_FMT_U8 && (EXP & 32768) != 0) {
             // the sign flip by the LDS itself: two ds_xor_b64 per piece behind its write (a wave's LDS operations
@@ -506,7 +517,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
             for (int u = 0; u < KU; u++)
                 if (kWhole || l + u * 64 < pieces) {
-                    unsigned long long *q8 = reinterpret_cast<unsigned long long *>(lp + u * (64 / PPT) * TS);
+                    unsigned long long *q8 = reinterpret_cast<unsigned long long *>(lp + u * kLandStep);
                     (void)__hip_atomic_fetch_xor(q8, 0x8080808080808080ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                     (void)__hip_atomic_fetch_xor(q8 + 1, 0x8080808080808080ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 }
@@ -584,7 +595,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
         int a_off = plane_a_offset(NE, G.e0, 0, KP - 1, r16, kq) + tab_off;
         asm volatile("" : "+v"(a_off));
         const uint8_t *ap = tabp + a_off;
-        const uint8_t *bp = slot + TS * r16 + 16 * kq;
+        // (the re-using loop: column r16 of block j is tile 4 r16 + j -- the lane's rows start at row 4 r16)
+        const uint8_t *bp = slot + row_at(kReuse ? 4 * r16 : r16) + 16 * kq;
         // (plane 0's pairs as a bit mask in scalar registers, made opaque at every pair: left to itself the compiler
         // hoists the 34 comparisons to the kernel's head and keeps them as lane masks in a VGPR, two v_readlane each)
         uint64_t p0_mask = (G.p0_hi >= 64 ? ~0ull : (1ull << G.p0_hi) - 1) & ~((1ull << G.p0_lo) - 1);
@@ -595,9 +607,14 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             for (int u = 0; u < 8; u++) {
                 const int p = u == 0 ? 1 : u < 5 ? -1 : u == 7 ? 0 : u - 3, j = u - 1;
                 if (p >= 0) a[r][p] = *reinterpret_cast<const v4i *>(ap + 32 * NE * p + 128 * (KP - 1 - t));
-                else b[r][j] = *reinterpret_cast<const v4i *>(bp + TS * (16 * j + t / 2) + 64 * (t & 1));
+                else if constexpr (!kReuse) b[r][j] = *reinterpret_cast<const v4i *>(bp + TS * (16 * j + t / 2) + 64 * (t & 1));
+                // (rows j + t / 2 past the lane's first; from pair 2 on the last block's alone, into the register of
+                // the fragment that died two pairs earlier -- the other three are there already)
+                else if (reuse_b_read(j, t)) b[r][reuse_b_reg(j, t)] = *reinterpret_cast<const v4i *>(bp + reuse_row_offset(j + t / 2) + 64 * (t & 1));
             }
         };
+        // the B registers of pair t: block j's fragment
+        auto bsel = [](int j, int t) { return kReuse ? reuse_b_reg(j, t) : j; };
         constexpr bool kFirstC0 = (EXP & 65536) != 0;  // (planes 1 .. 3: the first pair's MFMAs with the constant 0 as C)
         if constexpr (!kFirstC0) {
 #pragma unroll
@@ -617,9 +634,9 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         if constexpr (kFirstC0 && t == 0)
-                            asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(pa[p][j]) : "v"(a[r][p]), "v"(b[r][j]));
+                            asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(pa[p][j]) : "v"(a[r][p]), "v"(b[r][bsel(j, t)]));
                         else
-                            pa[p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[r][p], b[r][j], pa[p][j], 0, 0, 0);
+                            pa[p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[r][p], b[r][bsel(j, t)], pa[p][j], 0, 0, 0);
                     }
                 // (u8: the next pass's bytes get their sign flip here, in the shadow of the wave's own MFMAs -- EXP 262144
                 // of the pair loop, four registers per pair, done a pair before the end)
@@ -634,17 +651,19 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                         }
                     }
                 }
+                // (the next pair's reads, one behind each of the pair's first MFMAs: eight, or the re-using loop's five)
+                constexpr int kReads = kReuse && t + 1 >= 2 ? 5 : 8;
 #pragma unroll
-                for (int q = 0; q < 8; q++) {
+                for (int q = 0; q < kReads; q++) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
                     if constexpr (t + 1 < KP) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // LDS read
                 }
-                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 12 - kReads, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 asm volatile("" : "+s"(p0_mask));
                 if ((p0_mask >> t) & 1) {  // (uniform)
 #pragma unroll
-                    for (int j = 0; j < 4; j++) pa[0][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[r][0], b[r][j], pa[0][j], 0, 0, 0);
+                    for (int j = 0; j < 4; j++) pa[0][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[r][0], b[r][bsel(j, t)], pa[0][j], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 self(self, std::integral_constant<int, t + 1>{});
@@ -729,6 +748,60 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                 y[b][a2] = make_float2(w[0][0], w[0][1]);
                 y[b][2 + a2] = make_float2(w[1][0], w[1][1]);
             }
+    };
+    // ... and over the re-using loop's (kReuse): lane 16 g + c, block j, register k holds output 2 g + (k >> 1), part k & 1
+    // of tile 4 c + j.  The same combination per element, then the sixteen floats go to the lanes the pair loop has them in
+    // through the 2 KB behind the wave's image (hz_firmm2_plan.h, xchg_*), one column-block half b at a time: the lanes that
+    // hold tiles of half b (c >> 3 == b) write their four quads, every lane reads its two -- y[b][0 .. 3].  The wave's LDS
+    // operations execute in order: no barrier, the reads' s_waitcnt alone.  Called BEHIND the landing, as planes16 is: in
+    // front of it the next image's forty registers are still live beside the accumulators (measured: 236 VGPRs against
+    // 224).
+    [[maybe_unused]] auto planes_xchg = [&](const v4i(&pa)[4][4], float2(&y)[NB][4], double dcr, double dci) {
+        typedef float v4f_ __attribute__((ext_vector_type(4)));
+        static_assert(!kReuse || NB == 2, "two halves of 32 tiles");
+        v4f_ z[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int pt = k & 1;
+                double v = __fma_rn((double)pa[3][j][k], k3, pt ? dci : dcr);
+                v = __fma_rn((double)pa[2][j][k], k2, v);
+                if constexpr ((EXP & 16384) != 0) {
+                    const int hi = (int)(((unsigned)pa[0][j][k] << 8) + (unsigned)pa[1][j][k]);
+                    v = __fma_rn((double)hi, k1, v);
+                } else {
+                    v = __fma_rn((double)pa[1][j][k], k1, v);
+                    v = __fma_rn((double)pa[0][j][k], k0, v);
+                }
+                z[j][k] = (float)v;
+            }
+        // (the lane's three addresses formed HERE, a dozen integer instructions per pass: left to the compiler they are
+        // loop-invariant, hoisted to the kernel's head and held in registers through every matrix loop)
+        int lx = l;
+        asm volatile("" : "+v"(lx));
+        uint8_t *const xb = slot + reuse_image_bytes(D, NG * GS);
+        // (xchg_write_offset(l, j) = xchg_write_offset(l, j & 1) + 128 (j >> 1): sigma's bit 3 is the destination's bit 1)
+        uint8_t *const we = xb + xchg_write_offset(lx, 0), *const wo = xb + xchg_write_offset(lx, 1);
+        const uint8_t *const rp = xb + xchg_read_offset(lx, 0);
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            if (xchg_half(lx) == b) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) *reinterpret_cast<v4f_ *>(((j & 1) ? wo : we) + 128 * (j >> 1)) = z[j];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                const v4f_ w = *reinterpret_cast<const v4f_ *>(rp + 1024 * q);
+                y[b][2 * q] = make_float2(w.x, w.y);
+                y[b][2 * q + 1] = make_float2(w.z, w.w);
+            }
+            // (the other half's writes, and the next landing's, stay behind these reads: the same wave, in order)
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
     };
     // the elementwise program over a lane's outputs m = mb + 256 b + a of a pass in the run with phase line
     // (phi_r, dphi) / clock-table entry seg: equally spaced in two directions inside one exactly-linear clock run
@@ -1257,7 +1330,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             if (active) {
                 const double *dc = reinterpret_cast<const double *>(tabp + tab_off + (size_t)G.ne * 128);
                 float2 y[NB][4];
-                if constexpr (kPlane) planes16(pacc, y, dc[0] * k3, dc[1] * k3);
+                if constexpr (kReuse) planes_xchg(pacc, y, dc[0] * k3, dc[1] * k3);
+                else if constexpr (kPlane) planes16(pacc, y, dc[0] * k3, dc[1] * k3);
                 else planes(acc, y, dc[0] * k3, dc[1] * k3);
                 if constexpr ((EXP & 64) != 0) {  // (the stamp behind the combination, not in the middle of it)
 #pragma unroll

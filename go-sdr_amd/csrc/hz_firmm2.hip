@@ -28,6 +28,9 @@ constexpr int kLibExp = 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 
 // (1 << 29: the per-plane v_mfma_i32_16x16x64_i8 loop of the 1024-tap window at D = 8, plane 0 on its window of step
 // pairs; hzsdr_chain_fir_options' loop_form 8 keeps the pair loop of two planes per 32x32x32 fragment, for A/B)
 constexpr int kPairExp = kLibExp & ~(1 << 29);
+// (1 << 30: the per-plane loop that re-uses its tile windows, one B read per pair -- loop_form 10, and what loop_form 0
+// means by hz_firmm2_plan.h's kLoopDefault; loop_form 9 keeps the per-plane loop of four B reads per pair)
+constexpr int kReuseExp = kLibExp | (1 << 30);
 
 template <int FMT>
 static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *in, float2 *out, const float2 *hist,
@@ -35,8 +38,8 @@ static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *i
                       Plan L, const EwProgram &P, const Fix &F, const Batch &B, int rolled) {
     if (!factor_ok(D)) return HZSDR_ERR_INVALID_ARGUMENT;
     // (the per-plane instantiation's slots are wider: the same flag picks the kernel below and sizes its LDS)
-    const bool plane = plane_form((int)D, g.ks, rolled);
-    const size_t lds = lds_bytes((int)D, g.ks, g.ne, g.ntaps, plane);
+    const bool plane = plane_form((int)D, g.ks, rolled), reuse = reuse_form((int)D, g.ks, rolled);
+    const size_t lds = form_lds_bytes((int)D, g.ks, g.ne, g.ntaps, plane, reuse);
     if (D == 16) {  // (256 outputs per pass, one column block; the straight-line loop for the 1024-tap window: 9 groups of 8 steps)
         const int grid16 = std::max(1, L.grid);
         unsigned long long *no_stamps16 = nullptr;
@@ -51,6 +54,8 @@ static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *i
     // (the straight-line matrix loop exists for the 1024-tap window: 17 groups; `rolled`: hzsdr_chain_fir_options'
     // loop form -- 8 the straight-line pair loop, 1, 2, 4 groups per trip, anything else the instantiation for any
     // window -- for A/B measurements)
+    if (reuse)
+        return launch(fir_mm2_kernel<FMT, 8, 17, kReuseExp>, dim3(grid), lds, stream, in, out, hist, new_hist, rhist, new_rhist, taps, n, g, L, P, F, B, no_stamps);
     if (plane)
         return launch(fir_mm2_kernel<FMT, 8, 17, kLibExp>, dim3(grid), lds, stream, in, out, hist, new_hist, rhist, new_rhist, taps, n, g, L, P, F, B, no_stamps);
     if (g.ks == 17 * 4 && rolled == 8)

@@ -49,11 +49,58 @@ constexpr size_t image_bytes(int D, int ks) { return (size_t)(pass_tiles(D) - 1)
 constexpr int tile_stride(int D, bool plane = false) { return tile_bytes(D) + (plane ? 32 : 16); }
 // The instantiation a launch takes (hz_firmm2.hip: launch_fmt) runs the per-plane loop: factor 8, the 1024-tap window's
 // 17 groups of 4 steps, the default loop form.  Host and kernel size the LDS by this one flag.
-constexpr bool plane_form(int D, int ks, int loop_form) { return D == 8 && ks == 17 * 4 && loop_form == 0; }
+// (loop forms of hzsdr_chain_fir_options: 8 the pair loop, 9 the per-plane loop that reads four tile windows per pair, 10
+// the per-plane loop that re-uses them -- reuse_form below; 0, the default, is one of the last two)
+constexpr int kLoopPair = 8, kLoopPlane = 9, kLoopReuse = 10;
+constexpr int kLoopDefault = kLoopReuse;
+constexpr bool plane_form(int D, int ks, int loop_form) {
+    return D == 8 && ks == 17 * 4 && (loop_form == 0 || loop_form == kLoopPlane || loop_form == kLoopReuse);
+}
+// The per-plane loop with the tiles INTERLEAVED over the column blocks: column c of block j is tile 4 c + j (not 16 j + c),
+// so lane (c, kq) reads row 4 c + j + t / 2 of the image on pair t, and the fragment of block j on pair t + 2 is the
+// fragment of block j + 1 on pair t IN THE SAME LANE: it stays in its register, and a pair reads one new B fragment
+// (row 4 c + 3 + t / 2) where the loop above reads four.
+constexpr bool reuse_form(int D, int ks, int loop_form) {
+    return plane_form(D, ks, loop_form) && (loop_form == 0 ? kLoopDefault : loop_form) == kLoopReuse;
+}
 // (the loop's look-ahead reads two steps past the last window: one tile behind the image)
 constexpr size_t slot_bytes(int D, int ks, bool plane = false) {
     return ((image_bytes(D, ks) / tile_bytes(D) + 1) * tile_stride(D, plane) + 255) / 256 * 256;
 }
+// The re-using loop's slot: a lane's rows are FOUR rows apart, and at 160 bytes per row that is a lane stride of 640 = 16 *
+// 40, 40 = 0 mod 8 -- every lane of a kq on one 16-byte bank group.  Rows 128 bytes apart and 32 bytes of padding behind
+// every fourth row: the lane stride is 544 = 16 * 34, 34 = 2 mod 8, the class tile_stride's comment found conflict-free,
+// a row's 128 bytes stay contiguous (the landing's writes), and row 4 c + r is at 544 c + reuse_row_offset(r): one
+// per-lane base and constants, as before.  tests/host/window_reuse_layout.cpp counts the cycles.
+constexpr int reuse_row_offset(int row) { return 128 * row + 32 * (row >> 2); }
+// ... what lane (c, kq) reads as column block j's B operand on pair t: piece kq + 4 (t & 1) of row 4 c + j + t / 2
+constexpr int reuse_b_offset(int j, int t, int c, int kq) { return reuse_row_offset(4 * c + j + t / 2) + 64 * (t & 1) + 16 * kq; }
+// ... the register b[r][s] that holds that fragment, and whether pair t's own load reads it (else it is in the register
+// since pair t - 2, as block j + 1's)
+constexpr int reuse_b_reg(int j, int t) { return (j + t / 2) & 3; }
+constexpr bool reuse_b_read(int j, int t) { return t < 2 || j == 3; }
+// (no look-ahead behind the last window: the image's rows, and behind them the epilogue's exchange area, xchg_* below)
+constexpr int kXchgBytes = 2048;
+constexpr size_t reuse_image_bytes(int D, int ks) {
+    return ((size_t)reuse_row_offset((int)(image_bytes(D, ks) / tile_bytes(D))) + 255) / 256 * 256;
+}
+constexpr size_t reuse_slot_bytes(int D, int ks) { return reuse_image_bytes(D, ks) + kXchgBytes; }
+// The re-using loop's accumulators leave lane 16 g + c, block j, register k with output i = 2 g + (k >> 1), part k & 1 of
+// tile T = 4 c + j, and the mixer wants lane 32 h + n to hold y[b][a] with h = i >> 2, a = i & 3, n = T & 31, b = T >> 5: a
+// lane bit below 4 becomes a register bit, which no permlane swap does.  The sixteen floats per lane go through the 2 KB
+// behind the wave's image, one half b of the column blocks' tiles at a time: the four floats k = 0 .. 3 of (lane, j) are
+// quad 2 b + (a >> 1) = 2 (c >> 3) + (g & 1) of destination lane d = 32 (g >> 1) + 4 (c & 7) + j -- one ds_write_b128,
+// by the lanes with c >> 3 == b -- and lane d reads its two quads of the half back, one ds_read_b128 each.  Quad (a >> 1)
+// of lane d lies at 1024 (a >> 1) + 16 sigma(d): sigma spreads the eight lanes of a write group (d = 4 c' + j, c' =
+// 0 .. 7) over the eight 16-byte bank groups of 128 bytes and the sixteen lanes of a read group (d >> 2 in {0, 3, 5, 6}
+// or {1, 2, 4, 7}, every j) over the sixteen of 256.
+constexpr int xchg_sigma(int d) {
+    return 32 * (d >> 5) + 16 * (d & 1) + 8 * ((d >> 1) & 1) + ((((d >> 2) & 7)) ^ (d & 1));
+}
+constexpr int xchg_dst_lane(int lane, int j) { return 32 * (lane >> 5) + 4 * (lane & 7) + j; }
+constexpr int xchg_half(int lane) { return (lane >> 3) & 1; }  // b: the round in which the lane writes
+constexpr int xchg_write_offset(int lane, int j) { return 1024 * ((lane >> 4) & 1) + 16 * xchg_sigma(xchg_dst_lane(lane, j)); }
+constexpr int xchg_read_offset(int lane, int q) { return 1024 * q + 16 * xchg_sigma(lane); }  // q = a >> 1
 // table: T[f][E][part][pl] of 16 bytes (digit plane 2 f + pl, most significant first), then (dc_re, dc_im), then the
 // mixer's eight step factors of the run (step_factors below)
 constexpr size_t table_bytes(int ne) { return (size_t)ne * 128 + 16 + 128; }
@@ -64,6 +111,11 @@ constexpr size_t task_bytes(int D, int ntaps) { return ((size_t)(2 * ntaps + D *
 // two tables, the queue's counter, a slot per wave, the fix-up task's scratch
 constexpr size_t lds_bytes(int D, int ks, int ne, int ntaps, bool plane = false) {
     return 2 * table_lds(ne) + kCtlBytes + kWaves * slot_bytes(D, ks, plane) + task_bytes(D, ntaps);
+}
+// ... by the loop form: the re-using loop's slots are its own (reuse_slot_bytes)
+constexpr size_t form_slot_bytes(int D, int ks, bool plane, bool reuse) { return reuse ? reuse_slot_bytes(D, ks) : slot_bytes(D, ks, plane); }
+constexpr size_t form_lds_bytes(int D, int ks, int ne, int ntaps, bool plane, bool reuse) {
+    return 2 * table_lds(ne) + kCtlBytes + kWaves * form_slot_bytes(D, ks, plane, reuse) + task_bytes(D, ntaps);
 }
 
 // The per-plane loop's tap table in LDS is PLANE-MAJOR: P[plane][E][part] of 16 bytes, permuted while it is staged (the

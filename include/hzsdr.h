@@ -395,7 +395,8 @@ int hzsdr_chain_mix_in_order(hzsdr_chain *c, int in_order);
  * format, factor and tap count and is what every ordinary caller wants.  nfft_min (0: the default):
  * the smallest overlap-save block (a power of two in 256 ... 8192); loop_form (0: the default): the
  * persistent-pass matrix kernel's loop form (1, 2, 4 groups per trip, 8 the straight-line loop of two digit planes
- * per 32x32x32 fragment that the per-plane 16x16x64 loop replaced, 99 the any-window instantiation).
+ * per 32x32x32 fragment that the per-plane 16x16x64 loop replaced, 9 the per-plane loop that reads four tile windows
+ * per step pair, 10 the per-plane loop that reads one and keeps the rest in registers, 99 the any-window instantiation).
  * Replaces the round-2/3 environment switches HZ_FIR_FFT / HZ_MM_V1 / HZ_FIR_NFFT_MIN / HZ_MM_ROLLED,
  * which a library built with -DHZSDR_DIAG still reads, once, as the process-wide default. */
 #define HZSDR_FIR_IMPL_AUTO 0

@@ -14,7 +14,9 @@
 // rows "kernel's lanes" read with the addresses of the kernel's lanes (r16 = lane & 15, kq = lane >> 4: A row r16 of
 // entry i - kq - 4 t + e0, B piece kq of tile r16), plane 0's A on every pair as the kernel does, in the layout the
 // kernel had first (the table in its memory order T[f][E][part][pl], tiles 144 bytes apart: every read 2-way
-// conflicted) and in the one it has now (plane-major table, tiles 160 bytes apart: hz_firmm2_plan.h).
+// conflicted), in the one it had next (plane-major table, tiles 160 bytes apart: hz_firmm2_plan.h), and as the loop that
+// re-uses its tile windows reads them (column r16 of block j = tile 4 r16 + j, rows by reuse_row_offset, ONE B read per
+// pair from pair 2 on into the register of the fragment that died two pairs earlier: 176 reads a pass instead of 272).
 //
 // Reads run AH pairs (PLANE) or 2 steps (PAIR) ahead of their MFMAs, rings of AH + 1, placed one read behind each
 // MFMA (sched_group_barrier) as the kernel places them.  Reports per form: ns per pass per SIMD (two waves, each
@@ -42,9 +44,10 @@ constexpr int kR = 0, kZ = 24576, kH = kZ + 1024, kB = kH + 1024, kBW = 13056, k
 constexpr int kPairs = 34, kSteps = 68;
 // the kernel's geometry at 1024 taps (hz_firmm2_plan.h: make_geom)
 constexpr int kNe = 152, kE0 = 144;
-enum { LAY_FLAT = 0, LAY_FIRST = 1, LAY_NOW = 2 };
+enum { LAY_FLAT = 0, LAY_FIRST = 1, LAY_NOW = 2, LAY_REUSE = 3 };
 static_assert(hz::mm2::plane_a_offset(kNe, kE0, 3, 0, 15, 0) + 16 <= kZ && 64 * (7 + kE0) + 32 + 64 * kNe + 32 <= kZ, "A addresses inside the random area");
 static_assert(hz::mm2::plane_b_offset(160, 3, kPairs - 1, 15, 3) + 16 <= kBW, "B addresses inside the wave's slot");
+static_assert(hz::mm2::reuse_b_offset(3, kPairs - 1, 15, 3) + 16 <= kBW, "... the re-using loop's too");
 
 enum { FILL_SKIP = 0, FILL_ZERO = 1, FILL_RANDOM = 2 };
 
@@ -131,16 +134,20 @@ __global__ __launch_bounds__(512) void plane_pass(unsigned long long *out, int t
     const uint8_t *ab = lds + 16 * l, *bb = lds + kB + kBW * wave + 16 * l;
     // (the kernel's lanes: per-lane bases, the pair and the plane / block at constant offsets)
     const int r16 = l & 15, kq = l >> 4;
-    int a_lane = LAY == LAY_NOW ? hz::mm2::plane_a_offset(kNe, kE0, 0, kPairs - 1, r16, kq) : 64 * ((r16 >> 1) - kq - 4 * (kPairs - 1) + kE0) + 32 * (r16 & 1);
+    constexpr bool kTabNow = LAY == LAY_NOW || LAY == LAY_REUSE;  // (the plane-major table)
+    static_assert(LAY != LAY_REUSE || AH == 1, "the rotation is written for reads one pair ahead");
+    int a_lane = kTabNow ? hz::mm2::plane_a_offset(kNe, kE0, 0, kPairs - 1, r16, kq) : 64 * ((r16 >> 1) - kq - 4 * (kPairs - 1) + kE0) + 32 * (r16 & 1);
     asm volatile("" : "+v"(a_lane));  // (the last pair's entry as the base: unsigned offsets, as the kernel)
-    const uint8_t *al = lds + kR + a_lane, *bl = lds + kB + kBW * wave + (LAY == LAY_NOW ? 160 : 144) * r16 + 16 * kq;
+    const uint8_t *al = lds + kR + a_lane;
+    const uint8_t *bl = lds + kB + kBW * wave + (LAY == LAY_REUSE ? hz::mm2::reuse_row_offset(4 * r16) : (LAY == LAY_NOW ? 160 : 144) * r16) + 16 * kq;
     auto a_addr = [&](int t, int p) -> const v4i * {
-        if constexpr (LAY == LAY_NOW) return reinterpret_cast<const v4i *>(al + 32 * kNe * p + 128 * (kPairs - 1 - t));
+        if constexpr (kTabNow) return reinterpret_cast<const v4i *>(al + 32 * kNe * p + 128 * (kPairs - 1 - t));
         if constexpr (LAY == LAY_FIRST) return reinterpret_cast<const v4i *>(al + (p >> 1) * 64 * kNe + 16 * (p & 1) + 256 * (kPairs - 1 - t));
         if (p == 0 && FILL == FILL_ZERO && (t < LO || t >= HI)) return reinterpret_cast<const v4i *>(ab + kZ);
         return reinterpret_cast<const v4i *>(ab + kR + ((4 * t + p) % 24) * 1024);
     };
     auto b_addr = [&](int t, int j) {
+        if constexpr (LAY == LAY_REUSE) return reinterpret_cast<const v4i *>(bl + hz::mm2::reuse_row_offset(j + t / 2) + 64 * (t & 1));
         if constexpr (LAY != LAY_FLAT) return reinterpret_cast<const v4i *>(bl + (LAY == LAY_NOW ? 160 : 144) * (16 * j + t / 2) + 64 * (t & 1));
         return reinterpret_cast<const v4i *>(bb + ((4 * t + j) % 6) * 1024);
     };
@@ -159,7 +166,10 @@ __global__ __launch_bounds__(512) void plane_pass(unsigned long long *out, int t
             for (int p = 0; p < 4; p++)
                 if (p > 0 || has0(t)) a[r][p] = *a_addr(t, p);
 #pragma unroll
-            for (int j = 0; j < 4; j++) b[r][j] = *b_addr(t, j);
+            for (int j = 0; j < 4; j++) {
+                if constexpr (LAY != LAY_REUSE) b[r][j] = *b_addr(t, j);
+                else if (hz::mm2::reuse_b_read(j, t)) b[r][hz::mm2::reuse_b_reg(j, t)] = *b_addr(t, j);
+            }
         };
         for (int t = 0; t < AH; t++) load(t, t);
         unroll<kPairs>([&](auto tc) {
@@ -169,9 +179,9 @@ __global__ __launch_bounds__(512) void plane_pass(unsigned long long *out, int t
 #pragma unroll
             for (int p = h0 ? 0 : 1; p < 4; p++)
 #pragma unroll
-                for (int j = 0; j < 4; j++) c[p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t % RG][p], b[t % RG][j], c[p][j], 0, 0, 0);
+                for (int j = 0; j < 4; j++) c[p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[t % RG][p], b[t % RG][LAY == LAY_REUSE ? hz::mm2::reuse_b_reg(j, t) : j], c[p][j], 0, 0, 0);
             constexpr int nm = h0 ? 16 : 12;
-            constexpr int nr = t + AH < kPairs ? (LAY != LAY_FLAT || FILL != FILL_SKIP || (t + AH >= LO && t + AH < HI) ? 8 : 7) : 0;
+            constexpr int nr = t + AH >= kPairs ? 0 : LAY == LAY_REUSE && t + AH >= 2 ? 5 : (LAY != LAY_FLAT || FILL != FILL_SKIP || (t + AH >= LO && t + AH < HI) ? 8 : 7);
 #pragma unroll
             for (int i = 0; i < nm; i++) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -242,6 +252,8 @@ int main(int argc, char **argv) {
         run("... kernel's lanes, plane-major table, tiles 160 B apart", plane_pass<LO, HI, FILL_SKIP, 1, LAY_NOW>, kSkip, 16, dout, sink, us);
         run("PLANE all random, skip 0 (1 ahead), kernel's lanes, 144 B", plane_pass<LO, HI, FILL_RANDOM, 1, LAY_FIRST>, 544, 16, dout, sink, us);
         run("PLANE all random, skip 0 (1 ahead), kernel's lanes, 160 B", plane_pass<LO, HI, FILL_RANDOM, 1, LAY_NOW>, 544, 16, dout, sink, us);
+        run("... kernel's lanes, windows re-used: 1 B read per pair", plane_pass<LO, HI, FILL_SKIP, 1, LAY_REUSE>, kSkip, 16, dout, sink, us);
+        run("PLANE all random, skip 0 (1 ahead), windows re-used", plane_pass<LO, HI, FILL_RANDOM, 1, LAY_REUSE>, 544, 16, dout, sink, us);
     }
     return 0;
 }
