@@ -441,6 +441,14 @@ class Context:
         from .demod import Demodulator
         return Demodulator(self, src_fmt, mode, taps, down, streams)
 
+    def iir_bank(self, kind, sections, rows=1):
+        """The IIR bank (include/hzsdr_iir.h, iir.IirBank): the cascade of biquads `sections` -- float32 (S, 5) rows of
+        (b0, b1, b2, a1, a2) shared by all rows, or (rows, S, 5) -- over `rows` rows of real float32 samples
+        (IIR_REAL_F32; float32 out) or of a source format (complex64 out): iir.deemphasis, dc_block, notch, one_pole,
+        lowpass, highpass, butterworth design them."""
+        from .iir import IirBank
+        return IirBank(self, kind, sections, rows)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -880,6 +888,8 @@ from ._capi import CHANBANK_FORM_A_LDS, CHANBANK_READ_DFT, CHANBANK_READ_TAPS  #
 from .chanbank import ChannelBank  # noqa: E402
 from ._capi import COVAR_FORM_ONE_TILE, COVAR_FORM_THREE_TILES  # noqa: E402
 from .covar import Covariance, Scan, bartlett, capon, music, peaks, steering_weights  # noqa: E402
+from ._capi import IIR_FORM_COMPLEX, IIR_FORM_PER_ROW, IIR_MAX_ROWS, IIR_MAX_SECTIONS, IIR_REAL_F32  # noqa: E402
+from .iir import IirBank, butterworth, dc_block, deemphasis, highpass, lowpass, notch, one_pole  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

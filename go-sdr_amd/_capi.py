@@ -289,9 +289,25 @@ COVAR_SIGNATURES = {
 }
 COVAR_FORM_ONE_TILE, COVAR_FORM_THREE_TILES = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_iir.h declares
+IIR_SIGNATURES = {
+    "hzsdr_iir_create": (i32, [vp, i32, C.POINTER(f32), sz, i32, sz, pvp]),
+    "hzsdr_iir_push": (i32, [vp, vp, sz, sz, vp, sz, sz, psz]),
+    "hzsdr_iir_set_sections": (i32, [vp, C.POINTER(f32), sz]),
+    "hzsdr_iir_get_state": (i32, [vp, C.POINTER(f32), sz]),
+    "hzsdr_iir_set_state": (i32, [vp, C.POINTER(f32), sz, u64]),
+    "hzsdr_iir_position": (i32, [vp, C.POINTER(u64)]),
+    "hzsdr_iir_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_iir_reset": (i32, [vp]),
+    "hzsdr_iir_free": (i32, [vp]),
+}
+IIR_REAL_F32 = 32
+IIR_MAX_SECTIONS, IIR_MAX_ROWS = 8, 8192
+IIR_FORM_PER_ROW, IIR_FORM_COMPLEX = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
-                             *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items()):
+                             *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -7,9 +7,10 @@ the context's device in a DEVICE context.  The errors carry the calling class's 
 import numpy as np
 
 from . import _is_torch, FMT_C64, FMT_I8, FMT_I16, FMT_U8, MEM_HOST
+from ._capi import IIR_REAL_F32
 
-# format -> (numpy dtype of an element, bytes of a sample)
-_NP_IN = {FMT_C64: (np.complex64, 8), FMT_U8: (np.uint8, 2), FMT_I8: (np.int8, 2), FMT_I16: (np.int16, 4)}
+# format -> (numpy dtype of an element, bytes of a sample); beside the four source formats, the IIR bank's real float32 rows
+_NP_IN = {FMT_C64: (np.complex64, 8), FMT_U8: (np.uint8, 2), FMT_I8: (np.int8, 2), FMT_I16: (np.int16, 4), IIR_REAL_F32: (np.float32, 4)}
 
 
 def torch_dtype(dt):

@@ -31,6 +31,7 @@
 #include "../../include/hzsdr_tuner.h"
 #include "../../include/hzsdr_chanbank.h"
 #include "../../include/hzsdr_covar.h"
+#include "../../include/hzsdr_iir.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1202,6 +1203,72 @@ private:
     const Context &x_;
     size_t streams_;
     hzsdr_demod *d_ = nullptr;
+};
+
+// The IIR bank (include/hzsdr_iir.h): the cascade `sections` -- (b0, b1, b2, a1, a2) per section, one cascade shared by
+// all rows, or rows of them when per_row -- over `rows` rows of HZSDR_IIR_REAL_F32 samples (float32 out: Push) or of a
+// source format (complex64 out: PushComplex).  Push filters `n` samples of every row (row r starts r * in_stride
+// samples into `in`; dense rows when in_stride is 0) and returns dense rows of n; one output per input, no flush.
+class IirBank {
+public:
+    IirBank(const Context &x, int kind_or_format, const std::vector<float> &sections, size_t rows = 1, bool per_row = false)
+        : x_(x), rows_(rows), complex_(kind_or_format != HZSDR_IIR_REAL_F32) {
+        const size_t per = 5 * (per_row && rows ? rows : 1);
+        sections_ = sections.size() / per;
+        if (sections_ * per != sections.size()) throw std::invalid_argument("IirBank: sections are S * 5, or rows * S * 5 values");
+        check(x_.raw(), hzsdr_iir_create(x_.raw(), kind_or_format, sections.data(), sections_, per_row ? 1 : 0, rows, &f_));
+    }
+    ~IirBank() { if (f_) hzsdr_iir_free(f_); }
+    IirBank(const IirBank &) = delete;
+    IirBank &operator=(const IirBank &) = delete;
+    // real rows (row r of the result is [r * n, (r + 1) * n))
+    std::vector<float> Push(const void *in, size_t n, size_t in_stride = 0) {
+        if (complex_) throw std::invalid_argument("IirBank: complex rows go through PushComplex");
+        std::vector<float> out(rows_ * n);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_iir_push(f_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n, n, &w));
+        return out;
+    }
+    std::vector<std::complex<float>> PushComplex(const void *in, size_t n, size_t in_stride = 0) {
+        if (!complex_) throw std::invalid_argument("IirBank: real rows go through Push");
+        std::vector<std::complex<float>> out(rows_ * n);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_iir_push(f_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n, n, &w));
+        return out;
+    }
+    // the same count and form; the state and the position stay
+    void SetSections(const std::vector<float> &sections) {
+        if (sections.size() % 5) throw std::invalid_argument("IirBank: sections are S * 5, or rows * S * 5 values");
+        check(x_.raw(), hzsdr_iir_set_sections(f_, sections.data(), sections_));
+    }
+    // row, section, z1 / z2, re / im (hzsdr_iir.h)
+    std::vector<float> State() const {
+        std::vector<float> z(rows_ * sections_ * 2 * (complex_ ? 2 : 1));
+        check(x_.raw(), hzsdr_iir_get_state(f_, z.data(), z.size()));
+        return z;
+    }
+    void SetState(const std::vector<float> &z, uint64_t position = 0) { check(x_.raw(), hzsdr_iir_set_state(f_, z.data(), z.size(), position)); }
+    uint64_t Position() const {
+        uint64_t p = 0;
+        check(x_.raw(), hzsdr_iir_position(f_, &p));
+        return p;
+    }
+    // -> (rows per wave, samples per tile, HZSDR_IIR_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_iir_plan(f_, &g, &t, &f));
+        return {g, t, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_iir_reset(f_)); }
+    size_t Rows() const { return rows_; }
+    size_t Sections() const { return sections_; }
+
+private:
+    const Context &x_;
+    size_t rows_, sections_ = 0;
+    bool complex_;
+    hzsdr_iir *f_ = nullptr;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

@@ -953,6 +953,31 @@ def demodulator_blocks(r, demodulator, block=READER_BLOCK):
         yield tail
 
 
+# ---- a Reader, or a demodulator's blocks, through the IIR bank (include/hzsdr_iir.h) ------------
+
+def iir_rows(src, bank, block=READER_BLOCK):
+    """Push `src` through `bank` (an iir.IirBank on a HOST context) and yield each push's rows.  `src` is a Reader of
+    the bank's source format, read to its end in blocks of `block` samples (a one-row bank: a DC blocker in front of a
+    detector), or any iterable of blocks the bank takes as they are -- demodulator_blocks(...) into a bank of
+    IIR_REAL_F32 rows (de-emphasis, a squelch smoother).  One output per input and nothing to flush: concatenated
+    along the last axis, the whole filtered stream at the input's rate."""
+    if isinstance(src, Reader):
+        if bank.kind != src.sample_format():
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield bank.push(buf[:k])
+        return
+    for b in src:
+        if b.shape[-1]:
+            yield bank.push(b)
+
+
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
 
 def tuner_rows(r, bank, block=READER_BLOCK):
