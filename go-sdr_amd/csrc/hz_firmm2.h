@@ -123,59 +123,25 @@ __device__ __attribute__((noinline)) void other_shift_stage(float2 *y, double ta
     }
 }
 
-// The mixer's complex products as the packed float32 pipe takes them WITHOUT moves: a complex value is a register
-// pair (re, im); a broadcast of one half (op_sel / op_sel_hi), the exchange of the halves and a negated half (neg_lo)
-// are operand modifiers of v_pk_mul_f32 / v_pk_fma_f32 and cost nothing.  The compiler does not use them for this
-// code -- it builds (-s, c) from (c, s) with a v_xor and two v_mov per product and pads every packed instruction with
-// an s_nop: ~13 vector instructions per output where 6 do (round 5; every vector instruction of an epilogue costs
-// the SIMD partner's matrix loop ~2.5 cycles).  Same operations in the same order as the float expressions they
-// replace: bit-identical results.  None of the forms below is the gfx950 hazard's (op_sel:[0,1] with src0 straight,
-// hz_firmm.h); tools/fix_pk_opsel.py checks the built library all the same.
 typedef float v2f __attribute__((ext_vector_type(2)));
-// (cs, sn) = (c0, s0) turned by w = (cos hi, sin hi, cos lo, sin lo):
-//   cs = fma(c0, w.x, fma(-s0, w.y, fma(c0, w.z, -(s0 w.w)))),  sn = fma(c0, w.y, fma(s0, w.x, fma(c0, w.w, s0 w.z)))
-__device__ __forceinline__ v2f pk_turn(v2f cs0, v2f wxy, v2f wzw) {
-    v2f t;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(t) : "v"(cs0), "v"(wzw));      // (-s0 w.w, s0 w.z)
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(t) : "v"(cs0), "v"(wzw));                           // + (c0 w.z, c0 w.w)
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "+v"(t) : "v"(cs0), "v"(wxy));  // + (-s0 w.y, s0 w.x)
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(t) : "v"(cs0), "v"(wxy));                           // + (c0 w.x, c0 w.y)
-    return t;
-}
-// y (cs, sn):  re = fma(y.x, cs, -(y.y sn)),  im = fma(y.x, sn, y.y cs)
-__device__ __forceinline__ v2f pk_cmul(v2f y, v2f f) {
-    v2f u, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(u) : "v"(y), "v"(f));           // (-y.y sn, y.y cs)
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(r) : "v"(y), "v"(f), "v"(u));                       // + (y.x cs, y.x sn)
-    return r;
-}
 
-// EXP (tools/mfma_fir2.hip; kLibExp in the library): 1 = no input loads, 2 = no matrix loop, 4 = no mixer,
-// 8 = no stores, 16 = no stagger, 32 = wave priorities (see the pass loop's end), 64 = stamps, 128 = no explicit vmcnt(0),
-// 256 = accumulator checksums per pass and lane, taken right behind the matrix loop and again behind the landing,
-// stored (first launch) or compared with the stored ones (tools/mm2_glitch.hip: which register, which lanes,
-// which compute unit, stale read or wrong sum), 512 = the mixer's step factors read from LDS in one batch, waited for
-// (lgkmcnt(0) and eight wait states) and pinned before their first use, 1024 = the first step factor formed a second
-// time from a second, fully waited read and compared with the one the mixer used (records as for 256), 2048 = the
-// constant 0 as the first step's C operand instead of cleared accumulator registers, 4096 = the rare paths read the
-// kernel arguments as the common path does (HZ_COLD_ARGS below switched off: round 3's code shape, for A/B).
-// Round 5, fewer vector instructions per pass (each switchable for A/B; kLibExp = what the library ships):
-// 8192 = the mixer in hand-packed form (pk_turn / pk_cmul above), 16384 = the two top digit planes combined in int32
-// in front of the float64 step (the host bounds the sums: hz_firmm_plan.h, digit_shift), 32768 = a u8 pass image's
-// sign flip by the LDS (ds_xor_b64 behind the landing's writes) instead of 40 v_xor per lane, 65536 = the first
-// step's MFMAs with the constant 0 as C through inline assembly (early-clobber destinations: no clears, no overlap of
-// destinations and sources), 131072 = the cold multi-Shift path waits for its own scratch reloads and is marked
-// unlikely (the compiler otherwise leaves a vmcnt(0) for them at the pass loop's top, behind the prefetch's issue, and
-// eight register moves on the hot path where the two meet), 262144 = a u8 pass image's sign flip among the wave's OWN
-// MFMAs, near the matrix loop's end (straight-line form).  Measured one by one and together, tools/mfma_fir2.hip AB=1:
-// 32768 is 0.8 us SLOWER (LDS atomics), 131072 alone -1.0 us, the rest -0.3 together.
-// 524288 = a pass's stores among the MFMAs of the wave's NEXT matrix loop (a global store does not issue beside a
-// partner that streams MFMAs, tools/epi_cost.hip: it waits for the partner's loop to end) -- and yet 1 us per buffer
-// SLOWER in a call over four buffers, even single: not shipped.  1 << 22 = the mixer's products as SCALAR float32
-// instructions: a packed float32 instruction does not issue beside a streaming partner either (the mixer beside a
-// partner's loop: 5.6 us packed, 1.2 us scalar -- tools/mfma_fir2.hip BISECT=1, LDS-staged stamps), which pinned the
-// epilogue to the partner's loop in every round so far; -0.6 ... -1.4 us per buffer in a call over four.  (1 << 20,
-// 1 << 21: the bisection's other switches -- no Sincos, no step factors from LDS; neither matters.)
+// EXP: the kernel's compile-time switches.  The library's instantiations differ by the two loop forms alone
+// (hz_firmm2.hip); the others are for the tools that measure the kernel as shipped (tools/mfma_fir2.hip,
+// tools/mm2_glitch.hip).  The numbers are those of the records under profiles/.
+enum : int {
+    kExpNoLoads = 1,            // ablation: no input loads
+    kExpNoMatrix = 2,           // ablation: no matrix loop
+    kExpNoMixer = 4,            // ablation: no elementwise program
+    kExpNoStores = 8,           // ablation: no output stores
+    kExpPriorities = 32,        // wave priorities (see the pass loop's end)
+    kExpStamps = 64,            // s_memrealtime stamps per wave and phase, staged in LDS
+    kExpNoVmClear = 128,        // no explicit vmcnt(0) behind a landing
+    kExpChecksums = 256,        // the pair loop's accumulator checksums per pass and lane, taken right behind the matrix
+                                // loop and again behind the landing, stored (first launch) or compared (tools/mm2_glitch.hip)
+    kExpStampPerPass = 1 << 24, // with kExpStamps: a row of stamps for every pass of the wave, up to fifteen
+    kExpPlane = 1 << 29,        // loop form: one digit plane per A fragment, plane 0 on its window of step pairs
+    kExpReuse = 1 << 30,        // loop form, with kExpPlane: the per-plane loop that re-uses its tile windows
+};
 // NG: the window's groups (ks / GS) when the instantiation is for ONE tap count -- the matrix loop is then
 // straight-line code (a loop header drains the operand pipeline: the compiler cannot count outstanding
 // loads across a back edge); 0: any window, a loop over the groups.
@@ -193,17 +159,17 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     constexpr bool STRAIGHT = NG > 0 && UG == 0;
     constexpr int KU = NG > 0 ? ((pass_tiles(D) - 1 + NG) * PPT + 63) / 64 : kU;
     constexpr bool kWhole = NG > 0 && ((pass_tiles(D) - 1 + NG) * PPT) % 64 == 0;  // every lane has KU pieces
-    // (1 << 29: the straight-line form at D = 8 with ONE digit plane per A fragment -- v_mfma_i32_16x16x64_i8 over PAIRS
+    // (kExpPlane: the straight-line form at D = 8 with ONE digit plane per A fragment -- v_mfma_i32_16x16x64_i8 over PAIRS
     // of steps, plane 0 only on the pairs [G.p0_lo, G.p0_hi) where some tap can have a nonzero top digit; see the loop)
-    constexpr bool kPlane = STRAIGHT && D == 8 && (EXP & (1 << 29)) != 0;
-    static_assert(!kPlane || (EXP & (256 | 524288 | (1 << 23) | (1 << 27) | (1 << 28))) == 0, "not with the pair loop's experiments");
+    constexpr bool kPlane = STRAIGHT && D == 8 && (EXP & kExpPlane) != 0;
+    static_assert(!kPlane || (EXP & kExpChecksums) == 0, "the checksums are the pair loop's");
     static_assert(!kPlane || plane_form(D, NG * GS, 0), "the host sizes the LDS by plane_form");
-    // (1 << 30, with 1 << 29: the per-plane loop with the tiles interleaved over the column blocks -- a pair's B fragments
+    // (kExpReuse, with kExpPlane: the per-plane loop with the tiles interleaved over the column blocks -- a pair's B fragments
     // are the fragments of two pairs earlier, one column block on, in the same lane: ONE tile-window read per pair instead
     // of four; the slots in their own layout and the epilogue's exchange through LDS -- hz_firmm2_plan.h, reuse_form)
-    constexpr bool kReuse = kPlane && (EXP & (1 << 30)) != 0;
-    static_assert((EXP & (1 << 30)) == 0 || kPlane, "the re-using loop is a per-plane loop");
-    static_assert(!kReuse || ((EXP & 32768) == 0 && kXchgBytes == 2 * 64 * 16), "the landing by plain writes; two quads per lane and half in the exchange area");
+    constexpr bool kReuse = kPlane && (EXP & kExpReuse) != 0;
+    static_assert((EXP & kExpReuse) == 0 || kPlane, "the re-using loop is a per-plane loop");
+    static_assert(!kReuse || kXchgBytes == 2 * 64 * 16, "two quads per lane and half in the exchange area");
     // (the per-plane loop's slots: tiles 160 bytes apart, its reads are conflict-free there -- hz_firmm2_plan.h)
     constexpr int TS = tile_stride(D, kPlane);
     // (a tile's row in the slot)
@@ -215,7 +181,6 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     uint8_t *const tabp = mm_lds;
     unsigned *const ctr = reinterpret_cast<unsigned *>(mm_lds + 2 * tab_lds);
     uint8_t *const slot = mm_lds + 2 * tab_lds + kCtlBytes + (size_t)wave * slot_sz;
-    const int64_t n_bytes = 2 * (int64_t)n_in;
     const uint8_t *src = (const uint8_t *)in;
     const int pieces = (int)(image_bytes(D, G.ks) / 16);
     // A call over several buffers (hz_firmm2_plan.h: Batch): `in` / `out` are buffer 0's, buffer j's virtual base is
@@ -231,28 +196,28 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     auto vin_of = [&](int j) -> uint64_t { return j == 0 ? (uint64_t)(uintptr_t)src : B.vin[j]; };
     auto vout_of = [&](int j) -> uint64_t { return j == 0 ? (uint64_t)(uintptr_t)out : B.vout[j]; };
     typedef const v4i __attribute__((address_space(1))) *gload_p;
-    // (EXP & 64: s_memrealtime stamps, 10 ns ticks: slot 0 of a wave = its start and end, slots 1 .. 3 its passes)
+    // (kExpStamps: s_memrealtime stamps, 10 ns ticks: slot 0 of a wave = its start and end, slots 1 .. 3 its passes)
     // The stamps are kept in LDS (2 KB behind the kernel's own: the harness asks for them) and written out when the wave
     // ends: a global store does not issue while the SIMD partner's MFMAs are back to back (tools/epi_cost.hip), so a
     // stamp stored at once pinned the very phases it was to time to the partner's loop (rounds 3-4 read "the epilogue
     // takes as long as the partner's loop" off such stamps).
-    // (1 << 24, with 64: a row of stamps for EVERY pass of the wave, up to fifteen -- a call over four buffers gives a wave
+    // (kExpStampPerPass, with kExpStamps: a row of stamps for EVERY pass of the wave, up to fifteen -- a call over four buffers gives a wave
     // eight; 8 KB of staging behind the kernel's own LDS, which the harness asks for -- tools/mfma_fir2.hip PASSES=1)
     // (the per-plane form's LDS leaves 2 KB of the CU's 160: its stamped builds stage the stamps where the fix-up task's
     // scratch is, and the scratch moves onto the slots of waves 0 and 1, retired by then -- behind a barrier that the
     // shipped kernel does not need; the harness asks for no LDS beyond the kernel's own)
-    constexpr bool kStampShare = kPlane && (EXP & 64) != 0;
+    constexpr bool kStampShare = kPlane && (EXP & kExpStamps) != 0;
     static_assert(!kStampShare || (8 * 16 * 8 * kWaves <= 8192 && 2 * form_slot_bytes(D, NG * GS, true, kReuse) >= task_bytes(D, 1025)), "the shared areas fit");
-    constexpr int kStampRows = (EXP & (1 << 24)) != 0 ? 16 : 4;
+    constexpr int kStampRows = (EXP & kExpStampPerPass) != 0 ? 16 : 4;
     int stamp_pass = 0;
     [[maybe_unused]] unsigned long long *const lstamp =
         reinterpret_cast<unsigned long long *>(mm_lds + form_lds_bytes(D, G.ks, G.ne, G.ntaps, kPlane, kReuse) - (kStampShare ? task_bytes(D, G.ntaps) : 0)) +
         (size_t)wave * (8 * kStampRows);
-    if constexpr ((EXP & 64) != 0) {
+    if constexpr ((EXP & kExpStamps) != 0) {
         for (int i = l; i < 8 * kStampRows; i += 64) lstamp[i] = 0;
     }
     auto stamp = [&](int k) {
-        if constexpr ((EXP & 64) != 0) {
+        if constexpr ((EXP & kExpStamps) != 0) {
             if (l == 0 && stamp_pass < kStampRows)
                 lstamp[(k == 0 || k == 7 || (k >= 8 && k < 16) ? 0 : stamp_pass) * 8 + (k & 7)] = __builtin_amdgcn_s_memrealtime();
         }
@@ -260,8 +225,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     stamp(0);
     // (with the stamps: the shader clock the workgroup ran at -- s_memtime counts shader cycles, s_memrealtime 100 MHz)
     [[maybe_unused]] unsigned long long clk0 = 0, rt0 = 0;
-    if constexpr ((EXP & 64) != 0) clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-    if constexpr ((EXP & 32) != 0) __builtin_amdgcn_s_setprio(1);
+    if constexpr ((EXP & kExpStamps) != 0) clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
+    if constexpr ((EXP & kExpPriorities) != 0) __builtin_amdgcn_s_setprio(1);
     const Run run0 = L.run[0];  // (read with the header: most workgroups of most calls are in run 0)
     // Everything the way to the first loads reads from the kernel arguments, wanted HERE: the compiler then issues
     // these scalar loads together and waits once (left alone it reads each next to its use: five load-wait
@@ -295,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
         for (int u = 0; u < KU; u++) {
             x[u] = v4i{0, 0, 0, 0};  // (pieces past the image: the last piece again, not landed)
-            if constexpr ((EXP & 1) != 0) continue;
+            if constexpr ((EXP & kExpNoLoads) != 0) continue;
             if constexpr (kWhole) x[u] = __builtin_nontemporal_load(pl + 64 * u);
             else x[u] = __builtin_nontemporal_load(p + min(l + u * 64, pieces - 1));
         }
@@ -396,12 +361,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     };
     auto history_tasks = [&]() {
         if (wave >= kWaves / 2 || new_hist == nullptr || wb + L.grid * wave >= (int)((G.off + kHistPer - 1) / kHistPer)) return;
-        if constexpr ((EXP & 4096) != 0) {
-            history_tasks_cold(in, hist, new_hist, rhist, new_rhist, n_in, G, L, P, B);
-        } else {
-            HZ_COLD_ARGS;
-            history_tasks_cold(in, hist, new_hist, rhist, new_rhist, n_in, G, L, P, B);
-        }
+        HZ_COLD_ARGS;
+        history_tasks_cold(in, hist, new_hist, rhist, new_rhist, n_in, G, L, P, B);
     };
     // Round r: workgroup wb takes fix-up task wb + r grid.  Round 0 is called ONCE, in front of the run groups, the
     // further rounds of a call with more tasks than workgroups (short calls across many clock boundaries) BEHIND them
@@ -411,12 +372,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     auto tasks_front = [&](int round) {
         if (wave >= kWaves / 2) return;
         if ((L.grid - 1 - wb) + round * L.grid >= L.n_task) return;  // (what most workgroups of most calls find)
-        if constexpr ((EXP & 4096) != 0) {
-            tasks_front_cold(round, in, hist, new_hist, rhist, new_rhist, taps, n_in, G, L, P, F, B);
-        } else {
-            HZ_COLD_ARGS;
-            tasks_front_cold(round, in, hist, new_hist, rhist, new_rhist, taps, n_in, G, L, P, F, B);
-        }
+        HZ_COLD_ARGS;
+        tasks_front_cold(round, in, hist, new_hist, rhist, new_rhist, taps, n_in, G, L, P, F, B);
     };
     auto tasks_back_cold = [&](float2 *out0, const Geom &G, const Batch &B) {
         float2 *const xs = task_xs(G);
@@ -455,12 +412,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     };
     auto tasks_back = [&]() {  // behind the barrier that follows tasks_front
         if (wave >= kWaves / 2 || fix_cnt == 0) return;
-        if constexpr ((EXP & 4096) != 0) {
-            tasks_back_cold(out, G, B);
-        } else {
-            HZ_COLD_ARGS;
-            tasks_back_cold(out, G, B);
-        }
+        HZ_COLD_ARGS;
+        tasks_back_cold(out, G, B);
     };
     stamp(9);
     auto put = [&](int q, v4i v) {
@@ -474,21 +427,21 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // (the prefetch just issued waited for, instead of flying under the matrix loop).  An explicit vmcnt(0) where
     // nothing is in flight anyway -- after a landing -- tells the pass so.
     auto vm_clear = [&]() {
-        if constexpr ((EXP & 128) == 0) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), the other counters untouched
+        if constexpr ((EXP & kExpNoVmClear) == 0) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), the other counters untouched
     };
     // (flipped: the u8 sign flip has been applied to the registers already -- among the MFMAs of the matrix loop the
-    // bytes were in flight under, EXP & 262144)
+    // bytes were in flight under; straight-line forms)
     auto land = [&](v4i(&x)[KU], bool flipped = false) {
         // piece l + 64 u is piece l % PPT of tile l / PPT + (64 / PPT) u: one address and constants
         // (the re-using loop's rows: 64 / PPT = 8 rows on is two whole groups of four rows on, a constant all the same)
         uint8_t *lp = slot + row_at(l / PPT) + 16 * (l % PPT);
         constexpr int kLandStep = kReuse ? reuse_row_offset(64 / PPT) : (64 / PPT) * TS;
         static_assert(!kReuse || (64 / PPT) % 4 == 0, "whole groups of four rows");
-        // (1 << 25: the rare un-flipped landing -- a wave's first pass, a pass behind an inactive one -- as a BRANCH.  The
+        // (the rare un-flipped landing -- a wave's first pass, a pass behind an inactive one -- as a BRANCH.  The
         // condition is uniform, and the compiler turned `if (!flipped) x ^= c` into 40 v_xor + 40 v_cndmask executed
         // by EVERY landing: 80 of a pass's ~490 vector instructions, each of which costs the SIMD partner's matrix loop
         // ~2.5 cycles -- found in the ISA in round 6.  The empty asm keeps the block from being if-converted again.)
-        if constexpr (FMT == HZSDR_FMT_U8 && STRAIGHT && (EXP & 262144) != 0 && (EXP & (1 << 25)) != 0 && (EXP & 32768) == 0) {
+        if constexpr (FMT == HZSDR_FMT_U8 && STRAIGHT) {
             if (!flipped) {
 #pragma unroll
                 for (int u = 0; u < KU; u++) {
@@ -500,28 +453,10 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
         for (int u = 0; u < KU; u++)
             if (kWhole || l + u * 64 < pieces) {
-                if constexpr (FMT == HZSDR_FMT_U8 && (EXP & 32768) == 0) {
-                    if constexpr (STRAIGHT && (EXP & 262144) != 0 && (EXP & (1 << 25)) != 0) {
-                        // (flipped above, in one uniform branch)
-                    } else if constexpr (STRAIGHT && (EXP & 262144) != 0) {
-                        if (!flipped) x[u] ^= (int)0x80808080;  // (uniform: a wave's first pass, a pass behind an inactive one)
-                    } else {
-                        x[u] ^= (int)0x80808080;  // b - 128 as int8
-                    }
-                }
+                // (the straight-line forms: flipped among the MFMAs, or above in one uniform branch)
+                if constexpr (FMT == HZSDR_FMT_U8 && !STRAIGHT) x[u] ^= (int)0x80808080;  // b - 128 as int8
                 *reinterpret_cast<v4i *>(lp + u * kLandStep) = x[u];
             }
-        if constexpr (FMT == HZSDR_FMT_U8 && (EXP & 32768) != 0) {
-            // the sign flip by the LDS itself: two ds_xor_b64 per piece behind its write (a wave's LDS operations
-            // execute in order) instead of four v_xor_b32 -- no vector instruction, and the LDS is half idle
-#pragma unroll
-            for (int u = 0; u < KU; u++)
-                if (kWhole || l + u * 64 < pieces) {
-                    unsigned long long *q8 = reinterpret_cast<unsigned long long *>(lp + u * kLandStep);
-                    (void)__hip_atomic_fetch_xor(q8, 0x8080808080808080ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    (void)__hip_atomic_fetch_xor(q8 + 1, 0x8080808080808080ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                }
-        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     };
@@ -557,12 +492,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
         __builtin_amdgcn_wave_barrier();
     };
     auto land_edge = [&](uint32_t pass) {  // (the call's first and last passes)
-        if constexpr ((EXP & 4096) != 0) {
-            land_edge_cold(pass, src, rhist, n_bytes, G, L, B);
-        } else {
-            HZ_COLD_ARGS;
-            land_edge_cold(pass, (const uint8_t *)in, rhist, 2 * (int64_t)n_in, G, L, B);
-        }
+        HZ_COLD_ARGS;
+        land_edge_cold(pass, (const uint8_t *)in, rhist, 2 * (int64_t)n_in, G, L, B);
     };
 
     // A fragments: lane n is row (a = n >> 3, c = (n >> 2) & 1, part = (n >> 1) & 1, pl = n & 1) = output
@@ -615,13 +546,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
         };
         // the B registers of pair t: block j's fragment
         auto bsel = [](int j, int t) { return kReuse ? reuse_b_reg(j, t) : j; };
-        constexpr bool kFirstC0 = (EXP & 65536) != 0;  // (planes 1 .. 3: the first pair's MFMAs with the constant 0 as C)
-        if constexpr (!kFirstC0) {
-#pragma unroll
-            for (int p = 1; p < 4; p++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) pa[p][j] = v4i{0, 0, 0, 0};
-        }
+        // (planes 1 .. 3 are written by the first pair's MFMAs, the constant 0 as C: plane 0 alone is cleared)
 #pragma unroll
         for (int j = 0; j < 4; j++) pa[0][j] = v4i{0, 0, 0, 0};
         load(std::integral_constant<int, 0>{});
@@ -633,14 +558,15 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                 for (int p = 1; p < 4; p++)
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
-                        if constexpr (kFirstC0 && t == 0)
+                        // (inline assembly with early-clobber destinations: no clears, no overlap of destinations and sources)
+                        if constexpr (t == 0)
                             asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, 0" : "=&v"(pa[p][j]) : "v"(a[r][p]), "v"(b[r][bsel(j, t)]));
                         else
                             pa[p][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[r][p], b[r][bsel(j, t)], pa[p][j], 0, 0, 0);
                     }
-                // (u8: the next pass's bytes get their sign flip here, in the shadow of the wave's own MFMAs -- EXP 262144
-                // of the pair loop, four registers per pair, done a pair before the end)
-                if constexpr (FMT == HZSDR_FMT_U8 && (EXP & 262144) != 0) {
+                // (u8: the next pass's bytes get their sign flip here, in the shadow of the wave's own MFMAs -- as in the
+                // pair loop, four registers per pair, done a pair before the end)
+                if constexpr (FMT == HZSDR_FMT_U8) {
                     constexpr int kFlipFirst = KP - 1 - (KU + 3) / 4;
                     if constexpr (t == kFlipFirst) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
                     if constexpr (t >= kFlipFirst && 4 * (t - kFlipFirst) < KU) {
@@ -673,7 +599,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     };
 
     bool first_seg = true, first_stamp = true;
-    const double k3 = __hiloint2double((1023 - G.shift) << 20, 0), k2 = k3 * 256.0, k1 = k3 * 65536.0, k0 = k3 * 16777216.0;  // 2^-S 256^d
+    const double k3 = __hiloint2double((1023 - G.shift) << 20, 0), k2 = k3 * 256.0, k1 = k3 * 65536.0;  // 2^-S 256^d, d = 0, 1, 2
     // a lane holds outputs 4 h + a (a = 0 .. 3) of tile n of each block: planes 2 f + pl at q = 4 a + 2 part + pl.
     // The planes meet in float64 with power-of-two weights (exact; the constant part of a u8 stream and the scale
     // 2^-S folded in), one rounding to float32.
@@ -686,25 +612,13 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
                 for (int pt = 0; pt < 2; pt++) {
                     const int q = 4 * aa + 2 * pt;
-                    if constexpr ((EXP & (1 << 27)) != 0) {  // (tools/mfma_fir2.hip CLOCKS: what the float64 instructions cost -- NOT exact, timing only)
-                        const int hi = (int)(((unsigned)acc[0][b][q] << 8) + (unsigned)acc[0][b][q + 1]);
-                        float v = __fmaf_rn((float)acc[1][b][q + 1], (float)k3, (float)(pt ? dci : dcr));
-                        v = __fmaf_rn((float)acc[1][b][q], (float)k2, v);
-                        c2[pt] = __fmaf_rn((float)hi, (float)k1, v);
-                        continue;
-                    }
                     double v = __fma_rn((double)acc[1][b][q + 1], k3, pt ? dci : dcr);
                     v = __fma_rn((double)acc[1][b][q], k2, v);
-                    if constexpr ((EXP & 16384) != 0) {
-                        // planes 0 and 1 meet in int32 (one v_lshl_add_u32 for a conversion and an fma): the host chose
-                        // the taps' scale so that 256 |sum_0| + |sum_1| < 2^31 for every input (digit_shift); every
-                        // partial sum of the chain is exact in float64 either way, so the result is the same bits
-                        const int hi = (int)(((unsigned)acc[0][b][q] << 8) + (unsigned)acc[0][b][q + 1]);
-                        v = __fma_rn((double)hi, k1, v);
-                    } else {
-                        v = __fma_rn((double)acc[0][b][q + 1], k1, v);
-                        v = __fma_rn((double)acc[0][b][q], k0, v);
-                    }
+                    // planes 0 and 1 meet in int32 (one v_lshl_add_u32 for a conversion and an fma): the host chose
+                    // the taps' scale so that 256 |sum_0| + |sum_1| < 2^31 for every input (digit_shift); every
+                    // partial sum of the chain is exact in float64 either way, so the result is the same bits
+                    const int hi = (int)(((unsigned)acc[0][b][q] << 8) + (unsigned)acc[0][b][q + 1]);
+                    v = __fma_rn((double)hi, k1, v);
                     c2[pt] = (float)v;
                 }
                 y[b][aa] = make_float2(c2[0], c2[1]);
@@ -725,13 +639,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                 const int pt = k & 1;
                 double v = __fma_rn((double)pa[3][j][k], k3, pt ? dci : dcr);
                 v = __fma_rn((double)pa[2][j][k], k2, v);
-                if constexpr ((EXP & 16384) != 0) {
-                    const int hi = (int)(((unsigned)pa[0][j][k] << 8) + (unsigned)pa[1][j][k]);
-                    v = __fma_rn((double)hi, k1, v);
-                } else {
-                    v = __fma_rn((double)pa[1][j][k], k1, v);
-                    v = __fma_rn((double)pa[0][j][k], k0, v);
-                }
+                const int hi = (int)(((unsigned)pa[0][j][k] << 8) + (unsigned)pa[1][j][k]);
+                v = __fma_rn((double)hi, k1, v);
                 z[j][k >> 1][pt] = (float)v;
             }
 #pragma unroll
@@ -767,13 +676,8 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                 const int pt = k & 1;
                 double v = __fma_rn((double)pa[3][j][k], k3, pt ? dci : dcr);
                 v = __fma_rn((double)pa[2][j][k], k2, v);
-                if constexpr ((EXP & 16384) != 0) {
-                    const int hi = (int)(((unsigned)pa[0][j][k] << 8) + (unsigned)pa[1][j][k]);
-                    v = __fma_rn((double)hi, k1, v);
-                } else {
-                    v = __fma_rn((double)pa[1][j][k], k1, v);
-                    v = __fma_rn((double)pa[0][j][k], k0, v);
-                }
+                const int hi = (int)(((unsigned)pa[0][j][k] << 8) + (unsigned)pa[1][j][k]);
+                v = __fma_rn((double)hi, k1, v);
                 z[j][k] = (float)v;
             }
         // (the lane's three addresses formed HERE, a dozen integer instructions per pass: left to the compiler they are
@@ -817,7 +721,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         // (scalar products, kept from being paired: a packed float32 instruction waits for the SIMD
-                        // partner's matrix loop -- EXP's 1 << 22)
+                        // partner's matrix loop, as in the mixer)
                         float gx = __fmul_rn(y[b][q].x, o.a), gy = __fmul_rn(y[b][q].y, o.a);
                         asm volatile("" : "+v"(gx), "+v"(gy));
                         y[b][q] = make_float2(gx, gy);
@@ -846,130 +750,61 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
         };
         // (the program's ONE marked Shift stage: the mixer)
         auto shift_stage = [&]() {
-                // The stage's phase is a 64-bit accumulator in turns (exact increments, no float64).  ONE Sincos per
-                // lane, for its first output; the other seven are that factor turned on by the group's step factors
-                // exp(2 pi i (256 b + a) D dphi) -- double-float constants in LDS, two fma pairs and an add per
-                // component (0.4 ulp rms against the 0.3 of a Sincos each, a third of the instructions: every vector
-                // instruction here runs beside the SIMD partner's matrix loop and costs both waves).
-                const uint64_t ph0 = phi_r + (uint64_t)D * mb * dphi;
-                float s0, c0;
-                // (tools/mfma_fir2.hip BISECT: 1 << 20 = no Sincos, 1 << 21 = the step factors not read from LDS,
-                // 1 << 22 = the products in scalar float32 instead of packed)
-                if constexpr ((EXP & (1 << 20)) != 0) s0 = __uint_as_float((uint32_t)(ph0 >> 40)), c0 = 1.0f;
-                else sincos_turns32((uint32_t)(ph0 >> 32), s0, c0);
-                [[maybe_unused]] float4 wpin[4 * NB];
-                [[maybe_unused]] float4 chk_w = make_float4(0.f, 0.f, 0.f, 0.f);
-                [[maybe_unused]] float chk_cs = 0.f, chk_sn = 0.f;
-                if constexpr ((EXP & 512) != 0) {
+            // The stage's phase is a 64-bit accumulator in turns (exact increments, no float64).  ONE Sincos per
+            // lane, for its first output; the other seven are that factor turned on by the group's step factors
+            // exp(2 pi i (256 b + a) D dphi) -- double-float constants in LDS, two fma pairs and an add per
+            // component (0.4 ulp rms against the 0.3 of a Sincos each, a third of the instructions: every vector
+            // instruction here runs beside the SIMD partner's matrix loop and costs both waves).
+            // The products are SCALAR float32 instructions: a packed one (v_pk_mul_f32 / v_pk_fma_f32) does not issue
+            // beside a SIMD partner that streams MFMAs -- the mixer beside a partner's loop took 5.6 us packed and 1.2 us
+            // scalar, which had pinned the epilogue to the partner's loop -- and op_sel:[0,1] with src0 straight is the
+            // gfx950 hazard of hz_firmm.h besides.  The empty asm below keeps the compiler from pairing them again;
+            // tools/fix_pk_opsel.py checks the built unit all the same.  (The retired forms of the mixer: DESIGN.md.)
+            const uint64_t ph0 = phi_r + (uint64_t)D * mb * dphi;
+            float s0, c0;
+            sincos_turns32((uint32_t)(ph0 >> 32), s0, c0);
+            const v2f cs0{c0, s0};
 #pragma unroll
-                    for (int i = 1; i < 4 * NB; i++) wpin[i] = wtab[i];
-                    asm volatile("s_waitcnt lgkmcnt(0)\n s_nop 7" ::: "memory");
+            for (int b = 0; b < NB; b++)
 #pragma unroll
-                    for (int i = 1; i < 4 * NB; i++) asm volatile("" : "+v"(wpin[i].x), "+v"(wpin[i].y), "+v"(wpin[i].z), "+v"(wpin[i].w));
-                }
-                if constexpr ((EXP & 8192) != 0) {
-                    const v2f cs0{c0, s0};
-#pragma unroll
-                    for (int b = 0; b < NB; b++)
-#pragma unroll
-                        for (int q = 0; q < 4; q++) {
-                            v2f f = cs0;
-                            if (b + q > 0) {
-                                typedef float v4f_ __attribute__((ext_vector_type(4)));
-                                v4f_ w;
-                                if constexpr ((EXP & (1 << 21)) != 0) w = v4f_{c0, s0, 1e-8f * (float)(4 * b + q), 1e-9f};
-                                else w = *reinterpret_cast<const v4f_ *>(wtab + 4 * b + q);  // (cos hi, sin hi, cos lo, sin lo)
-                                if constexpr ((EXP & (1 << 22)) != 0) {
-                                    f.x = __fmaf_rn(c0, w.x, __fmaf_rn(-s0, w.y, __fmaf_rn(c0, w.z, -(s0 * w.w))));
-                                    f.y = __fmaf_rn(c0, w.y, __fmaf_rn(s0, w.x, __fmaf_rn(c0, w.w, s0 * w.z)));
-                                } else
-                                f = pk_turn(cs0, w.xy, w.zw);
-                            }
-                            if constexpr ((EXP & (1 << 22)) != 0) {
-                                float rx = __fmaf_rn(y[b][q].x, f.x, -(y[b][q].y * f.y)), ry = __fmaf_rn(y[b][q].x, f.y, y[b][q].y * f.x);
-                                asm volatile("" : "+v"(rx), "+v"(ry));  // (kept scalar: no re-vectorisation)
-                                y[b][q] = make_float2(rx, ry);
-                            } else {
-                            const v2f r = pk_cmul(v2f{y[b][q].x, y[b][q].y}, f);
-                            y[b][q] = make_float2(r.x, r.y);
-                            }
-                        }
-                } else
-#pragma unroll
-                for (int b = 0; b < NB; b++)
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        float cs = c0, sn = s0;
-                        if (b + q > 0) {
-                            float4 w;
-                            if constexpr ((EXP & 512) != 0) w = wpin[4 * b + q];
-                            else w = wtab[4 * b + q];  // (cos hi, sin hi, cos lo, sin lo)
-                            // (the small terms first, the large ones chained on: four instructions per component)
-                            cs = __fmaf_rn(c0, w.x, __fmaf_rn(-s0, w.y, __fmaf_rn(c0, w.z, -(s0 * w.w))));
-                            sn = __fmaf_rn(c0, w.y, __fmaf_rn(s0, w.x, __fmaf_rn(c0, w.w, s0 * w.z)));
-                            if constexpr ((EXP & 1024) != 0) {
-                                if (b == 0 && q == 1) chk_w = w, chk_cs = cs, chk_sn = sn;
-                            }
-                        }
-                        y[b][q] = make_float2(__fmaf_rn(y[b][q].x, cs, -(y[b][q].y * sn)), __fmaf_rn(y[b][q].x, sn, y[b][q].y * cs));
+                for (int q = 0; q < 4; q++) {
+                    v2f f = cs0;
+                    if (b + q > 0) {
+                        typedef float v4f_ __attribute__((ext_vector_type(4)));
+                        const v4f_ w = *reinterpret_cast<const v4f_ *>(wtab + 4 * b + q);  // (cos hi, sin hi, cos lo, sin lo)
+                        // (the small terms first, the large ones chained on: four instructions per component)
+                        f.x = __fmaf_rn(c0, w.x, __fmaf_rn(-s0, w.y, __fmaf_rn(c0, w.z, -(s0 * w.w))));
+                        f.y = __fmaf_rn(c0, w.y, __fmaf_rn(s0, w.x, __fmaf_rn(c0, w.w, s0 * w.z)));
                     }
-                if constexpr ((EXP & 1024) != 0) {
-                    float4 w2 = wtab[1];
-                    asm volatile("s_waitcnt lgkmcnt(0)\n s_nop 7" : "+v"(w2.x), "+v"(w2.y), "+v"(w2.z), "+v"(w2.w));
-                    float c0b = c0, s0b = s0;
-                    asm volatile("" : "+v"(c0b), "+v"(s0b));
-                    float csl = __fmaf_rn(c0b, w2.z, -(s0b * w2.w)), snl = __fmaf_rn(c0b, w2.w, s0b * w2.z);
-                    asm volatile("" : "+v"(csl), "+v"(snl));  // (no packed forms across these)
-                    float cs2 = __fmaf_rn(-s0b, w2.y, csl), sn2 = __fmaf_rn(s0b, w2.x, snl);
-                    asm volatile("" : "+v"(cs2), "+v"(sn2));
-                    cs2 = __fmaf_rn(c0b, w2.x, cs2), sn2 = __fmaf_rn(c0b, w2.y, sn2);
-                    if (__float_as_uint(cs2) != __float_as_uint(chk_cs) || __float_as_uint(sn2) != __float_as_uint(chk_sn)) {
-                        const unsigned long long slot_r = atomicAdd(&stamps[2], 1ull);
-                        if (slot_r < 4000) {
-                            unsigned long long *rec = stamps + 8 + 8 * slot_r;
-                            auto pk = [](float a, float bq) { return (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(bq) << 32); };
-                            rec[0] = (unsigned long long)(mb / kPassOut) | ((unsigned long long)l << 32) | ((unsigned long long)wave << 40);
-                            rec[1] = (unsigned long long)(unsigned)wb | ((unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)) << 32);
-                            rec[2] = pk(c0, s0);
-                            rec[3] = pk(chk_cs, chk_sn);
-                            rec[4] = pk(cs2, sn2);
-                            rec[5] = pk(chk_w.x, chk_w.y);
-                            rec[6] = pk(chk_w.z, chk_w.w);
-                            rec[7] = pk(w2.z, w2.w);
-                        }
-                    }
+                    float rx = __fmaf_rn(y[b][q].x, f.x, -(y[b][q].y * f.y)), ry = __fmaf_rn(y[b][q].x, f.y, y[b][q].y * f.x);
+                    asm volatile("" : "+v"(rx), "+v"(ry));  // (kept scalar: no re-vectorisation)
+                    y[b][q] = make_float2(rx, ry);
                 }
         };
         auto other_stage_at = [&](int oi) {
-                if constexpr ((EXP & 4096) != 0) {
-                    other_stage(oi, seg, P);
-                } else {
-                    HZ_COLD_ARGS;
-                    other_stage(oi, seg, P);
-                }
-                // (a multi-Shift stage's outputs come back through scratch memory: waited for HERE -- left pending they
-                // become a vmcnt(0) at the pass loop's top, behind the next pass's prefetch)
-                if constexpr ((EXP & 131072) != 0) __builtin_amdgcn_s_waitcnt(0x0F70);
+            HZ_COLD_ARGS;
+            other_stage(oi, seg, P);
+            // (a multi-Shift stage's outputs come back through scratch memory: waited for HERE -- left pending they
+            // become a vmcnt(0) at the pass loop's top, behind the next pass's prefetch, and eight register moves on the
+            // hot path where the two meet)
+            __builtin_amdgcn_s_waitcnt(0x0F70);
         };
-        const int n_ops = (EXP & 4) ? 0 : L.n_ops;
-        // (1 << 26: the common program -- ONE stage, the marked Shift -- outside the loop over the stages: rolled, the loop
+        const int n_ops = (EXP & kExpNoMixer) ? 0 : L.n_ops;
+        // (the common program -- ONE stage, the marked Shift -- outside the loop over the stages: rolled, the loop
         // carries a lane's sixteen outputs from trip to trip through eight v_mov_b64 that every pass executed)
-        if constexpr ((EXP & (1 << 26)) != 0) {
-            if (__builtin_expect(n_ops == 1 && L.shift_op == 0, 1)) {
-                shift_stage();
-                return;
-            }
+        if (__builtin_expect(n_ops == 1 && L.shift_op == 0, 1)) {
+            shift_stage();
+            return;
         }
 #pragma unroll 1
         for (int oi = 0; oi < n_ops; oi++) {  // uniform
-            bool other = L.shift_op != oi;
-            if constexpr ((EXP & 131072) != 0) other = __builtin_expect(other, 0);
+            const bool other = __builtin_expect(L.shift_op != oi, 0);  // (the cold path)
             if (other) other_stage_at(oi);
             else shift_stage();
         }
     };
     auto store_block = [&](uint64_t outb, float2(&y)[4], uint32_t mo, uint32_t lo, uint32_t hi) {  // (outb: the pass's buffer, virtual base)
-        if constexpr ((EXP & 8) != 0) return;
+        if constexpr ((EXP & kExpNoStores) != 0) return;
         typedef float v4f __attribute__((ext_vector_type(4)));
         typedef float v2f_ __attribute__((ext_vector_type(2)));
         if (mo >= lo && mo + 4 <= hi) {
@@ -987,34 +822,10 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
     // group and the run B behind it are ONE queue (A's passes, B's passes); the next group slides on by one run (B
     // becomes A, its table stays) behind a barrier.
     auto has_passes = [&](int rr) { return rr < L.n && max(pb0, (uint32_t)L.pass_first[rr]) < min(pb1, (uint32_t)L.pass_end[rr]); };
-    // EXP & 524288 (straight-line form): a pass's STORES wait for the wave's next matrix loop.  Measured
-    // (tools/epi_cost.hip): beside a SIMD partner that issues MFMAs back to back a wave's vector instructions, LDS
-    // reads and writes and global loads go through as if the partner were idle -- but a global STORE does not issue
-    // until the partner's stream of MFMAs pauses (its data leaves the register file by a path the MFMAs' operand reads
-    // hold).  An epilogue that ends in stores therefore ends when the partner's loop ends, whatever its length, and the
-    // wave reaches its next loop -- queue, prefetch, first operands -- only then: a bubble of ~1 us in the matrix pipe
-    // at every change of waves.  Issued among the wave's OWN MFMAs (the partner is in its epilogue by then) the stores
-    // cost a few cycles each.  The last pass of a wave stores behind its loop as before.
-    // 1 << 23: the same stores, but in ONE place -- at the next matrix loop's TOP, behind the queue, the prefetch's issue
-    // and the first operand reads, in front of the first MFMA: while the partner's loop runs the wave gets everything
-    // else of its next pass ready and waits at the stores; when the partner's stream of MFMAs ends they issue and the
-    // loop starts at once (without this the wave reaches its loop's top only behind the stores: ~0.5 us of idle matrix
-    // pipe per pass).  No branch inside the straight-line loop (524288's two cost more than they gave).
-    constexpr bool kDeferTop = STRAIGHT && (EXP & (1 << 23)) != 0;
-    constexpr bool kDefer = STRAIGHT && ((EXP & 524288) != 0 || kDeferTop);
-    [[maybe_unused]] float2 yd[NB][4];
-    [[maybe_unused]] uint64_t out_d = 0;
-    [[maybe_unused]] uint32_t mb_d = 0, lo_d = 0, hi_d = 0;
-    [[maybe_unused]] bool have_d = false;  // uniform
-    auto flush_deferred = [&]() {
-        if constexpr (kDefer) {
-            if (have_d) {
-#pragma unroll
-                for (int b = 0; b < NB; b++) store_block(out_d, yd[b], mb_d + (uint32_t)(32 * kT) * b, lo_d, hi_d);
-                have_d = false;
-            }
-        }
-    };
+    // (A pass's stores: beside a SIMD partner that issues MFMAs back to back a wave's vector instructions, LDS reads and
+    // writes and global loads go through as if the partner were idle, but a global STORE does not issue until the
+    // partner's stream of MFMAs pauses -- tools/epi_cost.hip.  An epilogue that ends in stores ends when the partner's
+    // loop ends.  Deferring them into the wave's next matrix loop was measured 1 us per buffer SLOWER: DESIGN.md.)
     int ra = 0;
     while (ra < L.n && !has_passes(ra)) ra++;
     Run ru = run0, rv = run0;
@@ -1090,14 +901,13 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
         if (tid == 0) *ctr = kEarly;
         __syncthreads();
         if (first_stamp) stamp(11);
-        if constexpr ((EXP & 32) != 0) {
+        if constexpr ((EXP & kExpPriorities) != 0) {
             if (first_group) __builtin_amdgcn_s_setprio(1);
         }
         if (wave >= kEarly) {
             cur = grab();
             in0 = prefetchable(cur);
             if (in0) issue(x, pass_of(cur));
-            if constexpr ((EXP & 16) != 0) __builtin_amdgcn_s_sleep(60);  // (experiment: a longer offset)
         }
         if (cur < seg_b) {
             if (in0) land(x);
@@ -1122,12 +932,12 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
             const uint32_t m_start = pass_of(cur) * (uint32_t)kPassOut;
             const uint32_t v_lo = max(m_lo, m_start), v_hi = min(m_hi, m_start + (uint32_t)kPassOut);
             const bool active = v_lo < v_hi;  // uniform
-            // (EXP & 65536, straight-line form: the first step writes the accumulators -- constant 0 as C -- and an
+            // (the straight-line forms: the first step writes the accumulators -- the constant 0 as C, through inline
+            // assembly with early-clobber destinations: no clears, no overlap of destinations and sources -- and an
             // inactive pass never reads them)
-            constexpr bool kFirstC0 = STRAIGHT && (EXP & 65536) != 0;
             v16i acc[2][NB];
             [[maybe_unused]] v4i pacc[4][4];
-            if constexpr (!kFirstC0 && !kPlane) {
+            if constexpr (!STRAIGHT) {
 #pragma unroll
                 for (int f = 0; f < 2; f++)
 #pragma unroll
@@ -1135,24 +945,10 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
                         for (int q = 0; q < 16; q++) acc[f][b][q] = 0;
             }
-            // (the accumulators as opaque registers: the straight-line form then starts them like every other
-            // step -- v_mfma acc, a, b, acc -- instead of with the constant 0 as the C operand.  EXP & 2048 lets the
-            // compiler use the constant: 64 clears per pass less, exact sums all the same (tools/mm2_glitch.hip; what
-            // round 3 saw "lose terms" with the constant was the mixer's packed instruction, hz_firmm.h) -- and 1.8 us
-            // per call SLOWER, measured A/B on one box: the first step's destinations then overlap its sources)
-            if constexpr (STRAIGHT && (EXP & 2048) == 0 && !kFirstC0 && !kPlane) {
-#pragma unroll
-                for (int f = 0; f < 2; f++)
-#pragma unroll
-                    for (int b = 0; b < NB; b++) asm volatile("" : "+v"(acc[f][b]));
-            }
-            if constexpr (kDefer) {
-                if (!(active && (EXP & 2) == 0)) flush_deferred();
-            }
             if constexpr (kPlane) {
-                if (active && (EXP & 2) == 0) plane_loop(pacc, tab_off);
+                if (active && (EXP & kExpNoMatrix) == 0) plane_loop(pacc, tab_off);
             }
-            if (active && (EXP & 2) == 0 && !kPlane) {
+            if (active && (EXP & kExpNoMatrix) == 0 && !kPlane) {
                 // step s = GS g + j of the window: the A entries 2 s below the lane's first, B piece 2 j + h of
                 // tile n + g -- constants off two per-lane addresses (NG > 0) or off two running ones
                 constexpr int KS = NG * GS;
@@ -1181,13 +977,9 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                 load_b(b[0], 0, 0);
                 load_a(a[1], 1);
                 load_b(b[1], 0, 1);
-                if constexpr (kDeferTop) {
-                    __builtin_amdgcn_sched_barrier(0);  // (behind the operand reads' issue, in front of the first MFMA)
-                    flush_deferred();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                // one step; SC: the step as a compile-time value (straight-line form), or -1
-                auto step = [&](auto sc, int g, int j, int jx = 0) {
+                // one step; SC: the step as a compile-time value (straight-line form), or -1.  What a step touches, by
+                // name: the accumulators, the operand rings, the next pass's image (its sign flip), the two loaders
+                auto step = [&acc, &a, &b, &x, &load_a, &load_b](auto sc, int g, int j, int jx = 0) {
                     constexpr int SC = decltype(sc)::value;
                     const int s = SC >= 0 ? SC : GS * g + j;
                     const int sx = SC >= 0 ? SC : jx;  // (ring positions: the step mod 3, or the step of the trip mod 4)
@@ -1197,29 +989,18 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
 #pragma unroll
                     for (int f = 0; f < 2; f++)
 #pragma unroll
-                        for (int qq = 0; qq < NB; qq++) {
-                            // (1 << 28: the step's MFMAs in "snake" order -- (A0,B0) (A0,B1) (A1,B1) (A1,B0): one operand
-                            // changes between neighbours -- an experiment on the operands' toggling, tools/mfma_fir2.hip AB8)
-                            const int q = ((EXP & (1 << 28)) != 0 && f == 1) ? NB - 1 - qq : qq;
-                            if constexpr (kFirstC0 && SC == 0)
+                        for (int q = 0; q < NB; q++) {
+                            if constexpr (STRAIGHT && SC == 0)
                                 asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=&v"(acc[f][q]) : "v"(a[sx % RG][f]), "v"(b[sx % RG][q]));
                             else
                                 acc[f][q] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[sx % RG][f], b[sx % RG][q], acc[f][q], 0, 0, 0);
                         }
-                    // (EXP & 524288: the PREVIOUS pass's stores, one column block each in two early steps)
-                    if constexpr (kDefer && !kDeferTop && SC >= 0) {
-                        if constexpr (SC >= 3 && (SC - 3) % 4 == 0 && (SC - 3) / 4 < NB) {
-                            constexpr int bq = (SC - 3) / 4;
-                            if (have_d) store_block(out_d, yd[bq], mb_d + (uint32_t)(32 * kT) * bq, lo_d, hi_d);
-                        }
-                        if constexpr (SC == 3 + 4 * (NB - 1)) have_d = false;
-                    }
-                    // (EXP & 262144, u8 sources: the NEXT pass's bytes -- in flight since the loop's first lines, here long
+                    // (u8 sources, straight-line form: the NEXT pass's bytes -- in flight since the loop's first lines, here long
                     // since -- get their sign flip in the shadow of this wave's own MFMAs, where a vector instruction
                     // costs 2-3 cycles; left to the landing they are 40 instructions of the epilogue, which runs
                     // beside the SIMD partner's loop at one instruction per MFMA slot.  Registers without a load in
                     // flight hold stale values that nobody lands.)
-                    if constexpr (STRAIGHT && FMT == HZSDR_FMT_U8 && (EXP & 262144) != 0 && SC >= 0) {
+                    if constexpr (STRAIGHT && FMT == HZSDR_FMT_U8 && SC >= 0) {
                         constexpr int kFlipFirst = KS - 2 - (KU + 1) / 2;  // two registers per step, done two steps before the end
                         if constexpr (SC == kFlipFirst) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
                         if constexpr (SC >= kFlipFirst && 2 * (SC - kFlipFirst) < KU) {
@@ -1294,12 +1075,12 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                         for (int q = 0; q < 16; q++) s1 += acc[f][b][q], s2 += (1 + q + 16 * (b + NB * f)) * acc[f][b][q];
                 asm volatile("" : "+v"(s1), "+v"(s2));
             };
-            if constexpr ((EXP & 256) != 0) csum(cs_e1, cs_e2);
-            if (in_next) land(x, active && (EXP & 2) == 0);  // (the matrix loop ran: it flipped the bytes' signs)
+            if constexpr ((EXP & kExpChecksums) != 0) csum(cs_e1, cs_e2);
+            if (in_next) land(x, active && (EXP & kExpNoMatrix) == 0);  // (the matrix loop ran: it flipped the bytes' signs)
             else if (has_next) land_edge(pass_of(nxt));
             vm_clear();
             stamp(3);
-            if constexpr ((EXP & 256) != 0) {
+            if constexpr ((EXP & kExpChecksums) != 0) {
                 // stamps[0]: 0 = store, 1 = compare; [1]: the stored checksums (int4 per pass and lane); [2]: records
                 // written; [8 + 8 r ...]: record r
                 csum(cs_l1, cs_l2);
@@ -1333,7 +1114,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                 if constexpr (kReuse) planes_xchg(pacc, y, dc[0] * k3, dc[1] * k3);
                 else if constexpr (kPlane) planes16(pacc, y, dc[0] * k3, dc[1] * k3);
                 else planes(acc, y, dc[0] * k3, dc[1] * k3);
-                if constexpr ((EXP & 64) != 0) {  // (the stamp behind the combination, not in the middle of it)
+                if constexpr ((EXP & kExpStamps) != 0) {  // (the stamp behind the combination, not in the middle of it)
 #pragma unroll
                     for (int b = 0; b < NB; b++)
 #pragma unroll
@@ -1346,29 +1127,18 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
                     program(y, mb, phi_r, dphi, sel ? rv.seg : ru.seg, reinterpret_cast<const float4 *>(dc + 2));
                     stamp(5);
                     const uint64_t outp = vout_of(buf_of(pass_of(cur)));
-                    if constexpr (kDefer) {
-                        // (kept for the wave's next matrix loop; a wave without one -- no next pass in this group --
-                        // stores now)
 #pragma unroll
-                        for (int b = 0; b < NB; b++)
-#pragma unroll
-                            for (int q = 0; q < 4; q++) yd[b][q] = y[b][q];
-                        out_d = outp, mb_d = mb, lo_d = v_lo, hi_d = v_hi, have_d = true;
-                        if (!has_next) flush_deferred();
-                    } else {
-#pragma unroll
-                        for (int b = 0; b < NB; b++) store_block(outp, y[b], mb + (uint32_t)(32 * kT) * b, v_lo, v_hi);
-                    }
+                    for (int b = 0; b < NB; b++) store_block(outp, y[b], mb + (uint32_t)(32 * kT) * b, v_lo, v_hi);
                 }
             }
             stamp(6);
-            // No wave priorities in the library (EXP & 32 turns them on for study: the matrix pipe goes to the wave of
+            // No wave priorities in the library (kExpPriorities turns them on for study: the matrix pipe goes to the wave of
             // higher priority, then to the OLDER one, and ranking a wave on its first pass above one that has finished
             // a pass makes the two waves of a SIMD alternate pass by pass): the kernel is as fast without them
             // (tools/mfma_fir2.hip: 38.6 against 38.9 us).  Round 4, tasks off the head: launch by launch with an event
-            // pair each (AB=1) the priorities are worth 0.4-1.8 us of the median -- and in bench.py's back-to-back
+            // pair each the priorities are worth 0.4-1.8 us of the median -- and in bench.py's back-to-back
             // stream they COST 0.6 us per step (0.0392 against 0.0386, three times over on one box).  Still off.
-            if constexpr ((EXP & 32) != 0) __builtin_amdgcn_s_setprio(0);
+            if constexpr ((EXP & kExpPriorities) != 0) __builtin_amdgcn_s_setprio(0);
             cur = nxt;
         }
         if (!b_here) break;
@@ -1393,7 +1163,7 @@ __global__ __launch_bounds__(kThreads) void fir_mm2_kernel(
         tasks_back();
     }
     stamp(7);
-    if constexpr ((EXP & 64) != 0) {
+    if constexpr ((EXP & kExpStamps) != 0) {
         for (int i = l; i < 8 * kStampRows; i += 64) stamps[((size_t)wb * kWaves + wave) * (8 * kStampRows) + i] = lstamp[i];
         if (tid == 0) {  // (behind every wave's rows: shader cycles and 10 ns ticks of this workgroup's first wave)
             unsigned long long *ck = stamps + (size_t)L.grid * kWaves * (8 * kStampRows) + 2 * (size_t)wb;

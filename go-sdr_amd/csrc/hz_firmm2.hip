@@ -21,16 +21,15 @@ static int launch(K kernel, dim3 grid, size_t lds, hipStream_t stream, A... args
     return hipGetLastError() == hipSuccess ? HZSDR_OK : HZSDR_ERR_HIP;
 }
 
-// What the library ships of the kernel's switches (hz_firmm2.h, EXP): round 5's instruction cuts.
-// (round 6: 1 << 25, the landing's rare sign flip as a uniform branch -- it was 80 vector instructions of every pass --, and
-// 1 << 26, the one-Shift program outside the loop over the stages)
-constexpr int kLibExp = 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 << 25) | (1 << 26) | (1 << 29);
-// (1 << 29: the per-plane v_mfma_i32_16x16x64_i8 loop of the 1024-tap window at D = 8, plane 0 on its window of step
-// pairs; hzsdr_chain_fir_options' loop_form 8 keeps the pair loop of two planes per 32x32x32 fragment, for A/B)
-constexpr int kPairExp = kLibExp & ~(1 << 29);
-// (1 << 30: the per-plane loop that re-uses its tile windows, one B read per pair -- loop_form 10, and what loop_form 0
+// What the library ships of the kernel's switches (hz_firmm2.h, EXP): the loop form, and nothing else.
+// (kExpPlane: the per-plane v_mfma_i32_16x16x64_i8 loop of the 1024-tap window at D = 8, plane 0 on its window of step
+// pairs -- it takes effect in the straight-line instantiation at D = 8 alone; hzsdr_chain_fir_options' loop_form 8 keeps
+// the pair loop of two planes per 32x32x32 fragment, for A/B)
+constexpr int kLibExp = kExpPlane;
+constexpr int kPairExp = 0;
+// (kExpReuse: the per-plane loop that re-uses its tile windows, one B read per pair -- loop_form 10, and what loop_form 0
 // means by hz_firmm2_plan.h's kLoopDefault; loop_form 9 keeps the per-plane loop of four B reads per pair)
-constexpr int kReuseExp = kLibExp | (1 << 30);
+constexpr int kReuseExp = kExpPlane | kExpReuse;
 
 template <int FMT>
 static int launch_fmt(hipStream_t stream, int num_cus, unsigned D, const void *in, float2 *out, const float2 *hist,

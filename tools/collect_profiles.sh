@@ -34,8 +34,7 @@ REPS=6 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_
 echo "== four buffers per launch (hzsdr_chain_run_batch)" >> $out/sq_counters.txt
 python3 tools/pmc_sq.py $out/sq4 >> $out/sq_counters.txt
 tools/bin/mfma_fir > $out/mfma_fir.txt 2>&1
-BISECT=1 tools/bin/mfma_fir2 > $out/mfma_fir2.txt 2>&1
-AB=1 tools/bin/mfma_fir2 > $out/mfma_fir2_ab.txt 2>&1
+tools/bin/mfma_fir2 > $out/mfma_fir2.txt 2>&1
 BATCH=4 tools/bin/mfma_fir2 > $out/mfma_fir2_batch4.txt 2>&1
 tools/bin/mfma_rate > $out/mfma_rate.txt 2>&1
 # round 5: what an epilogue's instructions cost beside the partner's matrix loop; the streaming kernels' access forms
@@ -56,8 +55,7 @@ python3 tools/firmm_probe.py 2>/dev/null | grep "path\|mean\|calls" > $out/firmm
 # sustains of bare MFMAs by operand content and duty, the round's A/Bs, config 2 and Downsample from HBM
 (cd tools; BATCH=4 PASSES=1 ./bin/mfma_fir2 > ../$out/pass_breakdown.txt 2>&1; ZERO=1 BATCH=4 PASSES=1 ./bin/mfma_fir2 > ../$out/pass_breakdown_zero.txt 2>&1
  for v in "" ZERO_IN=1 ZERO_TAB=1 ZERO=1; do echo "== $v"; env $v BATCH=4 PASSES=1 SPLIT=1 ./bin/mfma_fir2 2>&1 | grep "MIX\|shader clock"; done > ../$out/power_split.txt 2>&1
- ./bin/mfma_power > ../$out/mfma_power.txt 2>&1
- BATCH=4 AB6=1 ./bin/mfma_fir2 > ../$out/ab6_batch4.txt 2>&1; BATCH=4 AB7=1 ./bin/mfma_fir2 2>&1 | grep MIX > ../$out/ab7.txt; BATCH=8 AB6=1 ./bin/mfma_fir2 2>&1 | grep MIX > ../$out/ab6_batch8.txt)
+ ./bin/mfma_power > ../$out/mfma_power.txt 2>&1)
 python3 tools/shift_time.py 2>&1 | grep -v amdgpu > $out/shift_time_final.txt
 python3 tools/downsample_time.py 2>&1 | grep -v amdgpu > $out/downsample_time_final.txt
 for d in 16; do for t in 1024 512 256; do for impl in 0 2; do PROBE_D=$d PROBE_TAPS=$t PROBE_IMPL=$impl python3 tools/firmm_probe.py 2>/dev/null | head -2; done; done; done > $out/firmm_probe_d16.txt

@@ -24,7 +24,7 @@ static void pct(const char *name, std::vector<double> v) {
            v[v.size() / 2] / 100, v[v.size() * 9 / 10] / 100, v.back() / 100);
 }
 
-// PASSES=1: a row of stamps for every pass of every wave (EXP 64 | 1 << 24; s_memrealtime, 10 ns ticks, staged in LDS and
+// PASSES=1: a row of stamps for every pass of every wave (kExpStamps | kExpStampPerPass; s_memrealtime, 10 ns ticks, staged in LDS and
 // written out at the wave's end).  Row p of a wave: [0] the pass's top, [7] queue read, [1] the next pass's loads issued =
 // the matrix loop's start, [2] its end, [3] the next pass landed, [4] planes combined, [5] mixer done, [6] stores issued.
 // Reduced to what VERDICT r05 asked for: a per-phase table over all passes of the launch, the same split by whether the
@@ -139,7 +139,7 @@ template <int EXP, int MIXT = 1, int NGT = 17> static void run(void *const *in, 
     const size_t n = n_each * (size_t)g_batch;
     const unsigned off = (unsigned)((ntaps - 1 + D - 1) / D * D);
     mm2::Geom g = mm2::make_geom(ntaps, D, off, 40);
-    // (the per-plane loop's plane-0 window, EXP 1 << 29: P0=lo,hi step pairs; default every pair)
+    // (the per-plane loops' plane-0 window: P0=lo,hi step pairs; default every pair)
     if (const char *v = getenv("P0")) sscanf(v, "%d,%d", &g.p0_lo, &g.p0_hi);
     EwProgram P{};
     if (shift) {
@@ -176,8 +176,8 @@ template <int EXP, int MIXT = 1, int NGT = 17> static void run(void *const *in, 
         R.n_task = F.n_task;
     }
     // (+ the stamps' staging area; the per-plane form's LDS has no room behind it: its stamped builds stage the stamps inside the kernel's own, hz_firmm2.h kStampShare)
-    constexpr bool kPlaneT = (EXP & (1 << 29)) != 0;
-    const size_t lds = mm2::lds_bytes(D, g.ks, g.ne, g.ntaps, kPlaneT) + (((EXP & 64) && !kPlaneT) ? ((EXP & (1 << 24)) ? 8192 : 2048) : 0);
+    constexpr bool kPlaneT = (EXP & mm2::kExpPlane) != 0, kReuseT = (EXP & mm2::kExpReuse) != 0;
+    const size_t lds = mm2::form_lds_bytes(D, g.ks, g.ne, g.ntaps, kPlaneT, kReuseT) + (((EXP & mm2::kExpStamps) && !kPlaneT) ? ((EXP & mm2::kExpStampPerPass) ? 8192 : 2048) : 0);
     const unsigned grid = (unsigned)g_grid;
     auto k = mm2::fir_mm2_kernel<HZSDR_FMT_U8, D, NGT, EXP>;
     CK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -186,7 +186,7 @@ template <int EXP, int MIXT = 1, int NGT = 17> static void run(void *const *in, 
     CK(hipEventCreate(&e1));
     float best = 1e9f, sum = 0;
     std::vector<float> all;
-    const int reps = getenv("AB") ? 96 : 24;
+    const int reps = 24;
     for (int r = 0; r < reps + 4; r++) {
         const void *ins[mm2::kMaxBatch];
         void *outs[mm2::kMaxBatch];
@@ -205,11 +205,11 @@ template <int EXP, int MIXT = 1, int NGT = 17> static void run(void *const *in, 
     std::sort(all.begin(), all.end());
     printf("MIX %d EXP %6d%s: grid %u, LDS %zu, ks %d, passes %d, %d buffer(s) per launch: min %.1f us  median %.1f us  avg %.1f us PER BUFFER\n", MIXT, EXP, shift ? " +Shift" : "       ", grid, lds,
            g.ks, R.n_pass, g_batch, best * 1e3f / g_batch, all[all.size() / 2] * 1e3f / g_batch, sum / reps * 1e3f / g_batch);
-    if constexpr ((EXP & 64) != 0 && (EXP & (1 << 24)) != 0) {
+    if constexpr ((EXP & mm2::kExpStamps) != 0 && (EXP & mm2::kExpStampPerPass) != 0) {
         analyze_passes(grid);
         return;
     }
-    if (EXP & 64) {
+    if (EXP & mm2::kExpStamps) {
         const size_t nw = (size_t)grid * mm2::kWaves;
         std::vector<unsigned long long> st(nw * 32);
         CK(hipMemcpy(st.data(), g_stamps, st.size() * 8, hipMemcpyDeviceToHost));
@@ -347,109 +347,68 @@ int main(int argc, char **argv) {
     CK(hipMemcpy(tab, t.data(), t.size(), hipMemcpyHostToDevice));
     CK(hipMalloc(&g_stamps, 8 * 128 * 8 * 1024));
     CK(hipMemset(g_stamps, 0, 8 * 128 * 8 * 1024));
-    printf("fir_mm2_kernel<u8, 8>, 2^24 samples, %d taps; EXP 1 = no input loads, 2 = no matrix loop, 4 = no mixer, 8 = no stores, 32 = wave priorities, 128 = no explicit vmcnt(0)\n", ntaps);
-    constexpr int LIB5 = 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22);  // round 5's library
-    constexpr int LIB6 = LIB5 | (1 << 25) | (1 << 26);                          // round 6: the landing's flip as a branch, the one-Shift program peeled
+    printf("fir_mm2_kernel<u8, 8>, 2^24 samples, %d taps; EXP (hz_firmm2.h) 1 = no input loads, 2 = no matrix loop, 4 = no mixer, 8 = no stores, 32 = wave priorities, "
+           "64 = stamps, 128 = no explicit vmcnt(0), 1 << 24 = stamps per pass, 1 << 29 = per-plane loop, 1 << 30 = ... that re-uses its tile windows\n", ntaps);
+    using namespace hz::mm2;
+    // the kernel as the library ships it, by loop form (hz_firmm2.hip): the pair loop (loop_form 8), the per-plane loop (9) and
+    // the per-plane loop that re-uses its tile windows (10, the default); P0=lo,hi for the per-plane forms' plane-0 window
+    constexpr int PAIR = 0, PLANE = kExpPlane, REUSE = kExpPlane | kExpReuse;
+    constexpr int ST = kExpStamps | kExpStampPerPass;
     if (getenv("PASSES")) {  // the per-pass stamp table (BATCH=4 for the benchmarked form)
-        run<LIB6, 0>(in, out, taps, tab, n, ntaps, true);
-        run<LIB6 | 64 | (1 << 24), 0>(in, out, taps, tab, n, ntaps, true);
-        // the per-plane loop (what the library ships; P0=lo,hi for its plane-0 window)
-        run<LIB6 | (1 << 29), 0>(in, out, taps, tab, n, ntaps, true);
-        run<LIB6 | (1 << 29) | 64 | (1 << 24), 0>(in, out, taps, tab, n, ntaps, true);
+        run<PAIR, 0>(in, out, taps, tab, n, ntaps, true);
+        run<PAIR | ST, 0>(in, out, taps, tab, n, ntaps, true);
+        run<PLANE, 0>(in, out, taps, tab, n, ntaps, true);
+        run<PLANE | ST, 0>(in, out, taps, tab, n, ntaps, true);
+        run<REUSE, 0>(in, out, taps, tab, n, ntaps, true);
+        run<REUSE | ST, 0>(in, out, taps, tab, n, ntaps, true);
         if (getenv("SPLIT")) {  // where the power goes: the same launch without its mixer, without its stores, without both, without the input
-            run<LIB6 | 4, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | 8, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | 4 | 8, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | 1, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | 2, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | kExpNoMixer, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | kExpNoStores, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | kExpNoMixer | kExpNoStores, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | kExpNoLoads, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | kExpNoMatrix, 0>(in, out, taps, tab, n, ntaps, true);  // (see the default list's leg)
+            run<PAIR, 0>(in, out, taps, tab, n, ntaps, true);
+            run<REUSE | kExpNoMixer, 0>(in, out, taps, tab, n, ntaps, true);
+            run<REUSE | kExpNoStores, 0>(in, out, taps, tab, n, ntaps, true);
+            run<REUSE, 0>(in, out, taps, tab, n, ntaps, true);
         }
         return 0;
     }
     if (getenv("CLOCKS")) {  // the shader clock the chip holds under the kernel and under the kernel without one of its parts
-        constexpr int ST = 64 | (1 << 24);
         for (int r = 0; r < 2; r++) {
-            run<LIB6 | ST, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | ST | 4, 0>(in, out, taps, tab, n, ntaps, true);       // no mixer
-            run<LIB6 | ST | 8, 0>(in, out, taps, tab, n, ntaps, true);       // no stores
-            run<LIB6 | ST | (1 << 27), 0>(in, out, taps, tab, n, ntaps, true);  // the planes' combination in float32 (timing only: not exact)
-            run<LIB6 | ST, 0>(in, out, taps, tab, n, ntaps, false);          // no Shift stage at all
+            run<PAIR | ST, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | ST | kExpNoMixer, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | ST | kExpNoStores, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | ST, 0>(in, out, taps, tab, n, ntaps, false);  // no Shift stage at all
         }
         return 0;
     }
-    if (getenv("AB8")) {  // the MFMAs of a step in snake order (one operand changes between neighbours)
-        for (int r = 0; r < 5; r++) {
-            run<LIB6, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | (1 << 28), 0>(in, out, taps, tab, n, ntaps, true);
-        }
-        return 0;
-    }
-    if (getenv("AB7")) {  // what the float64 plane combination costs in the benchmarked form: the same kernel with a float32 one (NOT exact: timing only)
-        for (int r = 0; r < 5; r++) {
-            run<LIB6, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | (1 << 27), 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | 4, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6 | 4 | (1 << 27), 0>(in, out, taps, tab, n, ntaps, true);
-        }
-        return 0;
-    }
-    if (getenv("AB6")) {  // round 6's instruction cuts against round 5's library, interleaved (BATCH=4 for the benchmarked form)
-        for (int r = 0; r < 4; r++) {
-            run<LIB5, 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB5 | (1 << 25), 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB5 | (1 << 26), 0>(in, out, taps, tab, n, ntaps, true);
-            run<LIB6, 0>(in, out, taps, tab, n, ntaps, true);
-        }
-        return 0;
-    }
-    if (getenv("AB")) {  // A/B of the build's switches on one box, interleaved
-        // round 5: the instruction cuts one by one and together (hz_firmm2.h, EXP): 8192 packed mixer, 16384 int32 plane
-        // pair, 32768 sign flip by the LDS, 65536 constant-C first step, 131072 cold path fenced; 4 = no mixer at all
-        constexpr int ALL = 8192 | 16384 | 65536 | 131072 | 262144 | 524288;  // (kLibExp)
+    if (getenv("BATCH")) {  // k buffers per launch of the shipped forms
         for (int r = 0; r < 3; r++) {
-            run<0, 0>(in, out, taps, tab, n, ntaps, true);
-            run<ALL & ~524288, 0>(in, out, taps, tab, n, ntaps, true);
-            run<ALL, 0>(in, out, taps, tab, n, ntaps, true);
-            run<524288 | 131072, 0>(in, out, taps, tab, n, ntaps, true);
-            run<ALL | 4, 0>(in, out, taps, tab, n, ntaps, true);
-            run<ALL | 8, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PLANE, 0>(in, out, taps, tab, n, ntaps, true);
+            run<REUSE, 0>(in, out, taps, tab, n, ntaps, true);
+            run<PAIR | kExpNoMixer, 0>(in, out, taps, tab, n, ntaps, true);
         }
         return 0;
     }
-    if (getenv("BATCH")) {  // the shipped form, k buffers per launch
-        constexpr int ALL = 8192 | 16384 | 65536 | 131072 | 262144 | 524288;
-        for (int r = 0; r < 3; r++) {
-            run<ALL, 0>(in, out, taps, tab, n, ntaps, true);
-            run<ALL | (1 << 22), 0>(in, out, taps, tab, n, ntaps, true);                // the mixer's products in scalar float32
-            run<(ALL | (1 << 22)) & ~524288, 0>(in, out, taps, tab, n, ntaps, true);   // ... and the stores in the epilogue
-            run<((ALL | (1 << 22)) & ~524288) | (1 << 23), 0>(in, out, taps, tab, n, ntaps, true);  // ... the stores at the next loop's top
-            run<ALL | 4, 0>(in, out, taps, tab, n, ntaps, true);                        // no mixer at all
-            run<0, 0>(in, out, taps, tab, n, ntaps, true);                              // round 4's kernel
-        }
-        return 0;
-    }
-    run<8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22), 0>(in, out, taps, tab, n, ntaps, true);  // (what the library ships: kLibExp)
-    run<0, 0>(in, out, taps, tab, n, ntaps, true);
-    run<128, 0>(in, out, taps, tab, n, ntaps, true);
-    run<0, 0>(in, out, taps, tab, n, ntaps, true);
-    run<0, 0>(in, out, taps, tab, n, ntaps, false);
-    run<1, 0>(in, out, taps, tab, n, ntaps, true);
-    run<2, 0>(in, out, taps, tab, n, ntaps, true);
-    run<8, 0>(in, out, taps, tab, n, ntaps, true);
-    run<32, 0>(in, out, taps, tab, n, ntaps, true);
-    run<64 | 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22), 0>(in, out, taps, tab, n, ntaps, true);  // (kLibExp with stamps)
-    // the per-plane v_mfma_i32_16x16x64_i8 loop (1 << 29, hz_firmm2.h kPlane) without and with stamps
-    run<8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 << 29), 0>(in, out, taps, tab, n, ntaps, true);
-    run<64 | 8192 | 16384 | 65536 | 131072 | 262144 | (1 << 22) | (1 << 29), 0>(in, out, taps, tab, n, ntaps, true);
-    if (getenv("BISECT")) {  // which part of the epilogue waits for the partner's loop: without the mixer, without the stores
-        run<64 | 4 | 8192 | 16384 | 65536 | 131072 | 262144 | 524288, 0>(in, out, taps, tab, n, ntaps, true);
-        run<64 | 8 | 8192 | 16384 | 65536 | 131072 | 262144 | 524288, 0>(in, out, taps, tab, n, ntaps, true);
-        run<64 | 4 | 8 | 8192 | 16384 | 65536 | 131072 | 262144 | 524288, 0>(in, out, taps, tab, n, ntaps, true);
-        constexpr int ALLB = 64 | 8192 | 16384 | 65536 | 131072 | 262144 | 524288;
-        run<ALLB | (1 << 20), 0>(in, out, taps, tab, n, ntaps, true);
-        run<ALLB | (1 << 21), 0>(in, out, taps, tab, n, ntaps, true);
-        run<ALLB | (1 << 22), 0>(in, out, taps, tab, n, ntaps, true);
-        run<ALLB | (1 << 20) | (1 << 21), 0>(in, out, taps, tab, n, ntaps, true);
-    }
+    // each form plain and with stamps (a wave's first passes: start, loop, landing, planes, mixer, stores)
+    run<PAIR, 0>(in, out, taps, tab, n, ntaps, true);
+    run<PAIR | kExpStamps, 0>(in, out, taps, tab, n, ntaps, true);
+    run<PLANE, 0>(in, out, taps, tab, n, ntaps, true);
+    run<PLANE | kExpStamps, 0>(in, out, taps, tab, n, ntaps, true);
+    run<REUSE, 0>(in, out, taps, tab, n, ntaps, true);
+    run<REUSE | kExpStamps, 0>(in, out, taps, tab, n, ntaps, true);
+    // the pair loop without one of its parts
+    run<PAIR, 0>(in, out, taps, tab, n, ntaps, false);  // no Shift stage at all
+    run<PAIR | kExpNoLoads, 0>(in, out, taps, tab, n, ntaps, true);
+    // (no matrix loop: the straight-line forms have no accumulator clears -- their first step writes them -- so the
+    // epilogue here combines whatever the registers hold; timing only, like everything this program prints.  The records
+    // under profiles/ up to r06 ran this leg on the kernel of round 4, which cleared them: not comparable)
+    run<PAIR | kExpNoMatrix, 0>(in, out, taps, tab, n, ntaps, true);
+    run<PAIR | kExpNoMixer, 0>(in, out, taps, tab, n, ntaps, true);
+    run<PAIR | kExpNoStores, 0>(in, out, taps, tab, n, ntaps, true);
+    run<PAIR | kExpPriorities, 0>(in, out, taps, tab, n, ntaps, true);
+    run<PAIR | kExpNoVmClear, 0>(in, out, taps, tab, n, ntaps, true);
     return 0;
 }

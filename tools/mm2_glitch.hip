@@ -1,7 +1,7 @@
 // mm2_glitch.hip -- hunts the non-repeatable pass of hz::mm2::fir_mm2_kernel ("A hazard,
 // and a known issue") at the level of the int32 accumulators, thousands of launches per second.
 //
-//   leg 1 (EXP 256): the library's kernel with two checksums of a lane's 64 accumulator registers per pass --
+//   leg 1 (kExpChecksums): the library's pair-loop kernel with two checksums of a lane's 64 accumulator registers per pass --
 //          sum and index-weighted sum, taken right behind the matrix loop and again behind the landing of the
 //          next pass.  The first launch on a buffer stores them, every later launch compares in the kernel
 //          and appends a record (pass, lane, wave, workgroup, HW_ID, XCC_ID, both pairs, the stored pairs) on
@@ -9,8 +9,10 @@
 //          early and late alike (the sum IS wrong) or early only (a stale read), and -- with the exact
 //          per-step contributions recomputed from the table and the input bytes -- which window step and
 //          which half of its bytes the difference equals.
-//   leg 2 (EXP 0): the unmodified kernel; the float outputs of every launch compared bit for bit with the
-//          first launch on the same buffer by a second kernel (no instrumentation in the pass loop at all).
+//   leg 2: the pair-loop kernel as the library ships it (EXP 0: hzsdr_chain_fir_options' loop_form 8), and the
+//          same without its mixer (kExpNoMixer) and without the explicit vmcnt(0) (kExpNoVmClear); the float outputs
+//          of every launch compared bit for bit with the first launch on the same buffer by a second kernel (no
+//          instrumentation in the pass loop at all).
 // The table holds random digits in all four planes at every step (a dropped or corrupted term is visible
 // wherever it happens, not only where the real filter's taps are tiny).
 //   tools/bin/mm2_glitch [launches per leg = 20000] [taps = 1024]
@@ -208,7 +210,7 @@ int main(int argc, char **argv) {
 
     // ---- leg 1: checksums -------------------------------------------------------------------------------------
     {
-        auto k = mm2::fir_mm2_kernel<HZSDR_FMT_U8, D, 17, 256>;
+        auto k = mm2::fir_mm2_kernel<HZSDR_FMT_U8, D, 17, mm2::kExpChecksums>;
         CK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const size_t ref_bytes = (size_t)R.n_pass * 64 * 16, ctl_words = 8 + 8 * 4000;
         unsigned long long *ctl[NBUF];
@@ -313,38 +315,8 @@ int main(int argc, char **argv) {
             CK(hipFree(ctl[b]));
         }
     }
-    // ---- leg 3: the first step factor, formed twice (EXP 1024) ---------------------------------------------------
-    {
-        auto k = mm2::fir_mm2_kernel<HZSDR_FMT_U8, D, 17, 1024>;
-        CK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const size_t ctl_words = 8 + 8 * 4000;
-        unsigned long long *ctl;
-        CK(hipMalloc(&ctl, ctl_words * 8));
-        CK(hipMemset(ctl, 0, ctl_words * 8));
-        for (int r = 0; r < launches; r++)
-            hipLaunchKernelGGL(k, dim3(R.grid), dim3(mm2::kThreads), lds, 0, (const void *)in[r % NBUF], out, (const float2 *)nullptr, out + n_out,
-                               (const uint8_t *)taps, (uint8_t *)(out + n_out + 4096), taps, n, g, R, P, F, mm2::one_buffer(in[r % NBUF], out, n, D), ctl);
-        CK(hipDeviceSynchronize());
-        CK(hipGetLastError());
-        std::vector<unsigned long long> c(ctl_words);
-        CK(hipMemcpy(c.data(), ctl, ctl_words * 8, hipMemcpyDeviceToHost));
-        printf("leg 3 (EXP 1024): %llu lanes whose first step factor differs from its second evaluation, %d launches\n", c[2], launches);
-        auto f = [](unsigned long long v, int hi) { unsigned u = hi ? (unsigned)(v >> 32) : (unsigned)v; float x; memcpy(&x, &u, 4); return x; };
-        for (unsigned long long r = 0; r < std::min<unsigned long long>(c[2], 24); r++) {
-            const unsigned long long *q = &c[8 + 8 * r];
-            const float c0 = f(q[2], 0), s0 = f(q[2], 1), cs1 = f(q[3], 0), sn1 = f(q[3], 1), cs2 = f(q[4], 0), sn2 = f(q[4], 1);
-            const float wx = f(q[5], 0), wy = f(q[5], 1), wz = f(q[6], 0), ww = f(q[6], 1);
-            const float cs_hi = fmaf(c0, wx, -(s0 * wy)), sn_hi = fmaf(c0, wy, s0 * wx), cs_lo = fmaf(c0, wz, -(s0 * ww)), sn_lo = fmaf(c0, ww, s0 * wz);
-            printf("    pass %u lane %d wave %d wg %u: c0 %.9g s0 %.9g | used cs %.9g sn %.9g | again cs %.9g sn %.9g | w %.9g %.9g %.9g %.9g (again lo %.9g %.9g)\n"
-                   "        hi parts %.9g %.9g, lo parts %.9g %.9g; used - hi = %.9g %.9g\n",
-                   (unsigned)q[0], (int)((q[0] >> 32) & 0xff), (int)(q[0] >> 40), (unsigned)q[1], c0, s0, cs1, sn1, cs2, sn2, wx, wy, wz, ww, f(q[7], 0),
-                   f(q[7], 1), cs_hi, sn_hi, cs_lo, sn_lo, cs1 - cs_hi, sn1 - sn_hi);
-        }
-        CK(hipFree(ctl));
-    }
     leg2<0>("the unmodified kernel", launches, in, out, taps, n, g, R, P, F, lds);
-    leg2<4>("no mixer (EXP 4)", launches, in, out, taps, n, g, R, P, F, lds);
-    leg2<512>("the mixer's step factors waited for and pinned (EXP 512)", launches, in, out, taps, n, g, R, P, F, lds);
-    leg2<128>("no explicit vmcnt(0) (EXP 128)", launches, in, out, taps, n, g, R, P, F, lds);
+    leg2<mm2::kExpNoMixer>("no mixer (kExpNoMixer)", launches, in, out, taps, n, g, R, P, F, lds);
+    leg2<mm2::kExpNoVmClear>("no explicit vmcnt(0) (kExpNoVmClear)", launches, in, out, taps, n, g, R, P, F, lds);
     return 0;
 }
