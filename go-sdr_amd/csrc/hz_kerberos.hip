@@ -53,25 +53,40 @@ __global__ __launch_bounds__(kThreads) void peak_kernel(const float2 *__restrict
     if (threadIdx.x == 0) part[blockIdx.x] = Peak{sp[0], si[0]};
 }
 
+// A float64 sum carried with its rounding errors (Knuth's two-sum, the errors added up beside it): hi + lo is the sum
+// to within an ulp whatever the order and the length.  Plain sums of 262145 phases of -pi ended 8.5 * 2^-49 from -pi
+// (the 1024 partial sums added in order round at every step); tests/test_gpu_sync.py holds that mean to 2^-49.
+struct Sum2 {
+    double hi, lo;
+};
+
+__host__ __device__ __forceinline__ void sum2_add(Sum2 &s, double x, double xlo) {
+    const double t = s.hi + x;
+    const double z = t - s.hi;
+    s.lo += ((s.hi - (t - z)) + (x - z)) + xlo;  // (exact error of the addition; NaN and Inf pass through hi)
+    s.hi = t;
+}
+
 // rtl/kerberos/internal/align.go:257-262: Phase(complex128(a * conj(b))), i.e.
 // atan2(im, re) in float64 of the complex64 product.  Partial sums per
 // workgroup (fixed tree), combined in workgroup order on the host: deterministic,
-// not the reference's strictly sequential float64 sum (documented tolerance).
+// not the reference's strictly sequential float64 sum (documented tolerance) --
+// every step of it compensated, so the result is the exact sum rounded, then divided.
 __global__ __launch_bounds__(kThreads) void phase_kernel(const float2 *__restrict__ a,
                                                          const float2 *__restrict__ b, size_t n,
-                                                         double *__restrict__ part) {
-    double acc = 0.0;
+                                                         Sum2 *__restrict__ part) {
+    Sum2 acc{0.0, 0.0};
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float2 y = b[i];
         const float2 p = go_cmul(a[i], make_float2(y.x, -y.y));
-        acc += atan2((double)p.y, (double)p.x);
+        sum2_add(acc, atan2((double)p.y, (double)p.x), 0.0);
     }
-    __shared__ double s[kThreads];
+    __shared__ Sum2 s[kThreads];
     s[threadIdx.x] = acc;
     __syncthreads();
     for (int k = kThreads / 2; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) s[threadIdx.x] += s[threadIdx.x + k];
+        if ((int)threadIdx.x < k) sum2_add(s[threadIdx.x], s[threadIdx.x + k].hi, s[threadIdx.x + k].lo);
         __syncthreads();
     }
     if (threadIdx.x == 0) part[blockIdx.x] = s[0];
@@ -122,17 +137,17 @@ int hzsdr_mean_phase(hzsdr_ctx *ctx, const void *a, const void *b, size_t n, dou
     HZ_TRY(st.in(0, a, n * 8, &da));
     HZ_TRY(st.in(1, b, n * 8, &db));
     const unsigned blocks = blocks_for(ctx, n) < (unsigned)kRedBlocks ? blocks_for(ctx, n) : kRedBlocks;
-    HZ_TRY(ensure_slot(ctx, 8, sizeof(double) * kRedBlocks));
-    HZ_TRY(ensure_pinned(ctx, sizeof(double) * kRedBlocks));
-    double *dpart = (double *)ctx->slots[8].ptr, *hpart = (double *)ctx->pinned;
+    HZ_TRY(ensure_slot(ctx, 8, sizeof(Sum2) * kRedBlocks));
+    HZ_TRY(ensure_pinned(ctx, sizeof(Sum2) * kRedBlocks));
+    Sum2 *dpart = (Sum2 *)ctx->slots[8].ptr, *hpart = (Sum2 *)ctx->pinned;
     hipLaunchKernelGGL(phase_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, (const float2 *)da,
                        (const float2 *)db, n, dpart);
     HZ_HIP(ctx, hipGetLastError());
-    HZ_HIP(ctx, hipMemcpyAsync(hpart, dpart, sizeof(double) * blocks, hipMemcpyDeviceToHost, ctx->stream));
+    HZ_HIP(ctx, hipMemcpyAsync(hpart, dpart, sizeof(Sum2) * blocks, hipMemcpyDeviceToHost, ctx->stream));
     HZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    double acc = 0.0;
-    for (unsigned k = 0; k < blocks; k++) acc += hpart[k];
-    *mean_phase = acc / (double)n;  // align.go:266
+    Sum2 acc{0.0, 0.0};
+    for (unsigned k = 0; k < blocks; k++) sum2_add(acc, hpart[k].hi, hpart[k].lo);
+    *mean_phase = (acc.hi + acc.lo) / (double)n;  // align.go:266
     return HZSDR_OK;
 }
 

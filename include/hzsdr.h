@@ -307,8 +307,10 @@ int hzsdr_beamform_partial(hzsdr_ctx *ctx, void *out_c64, int format,
  * folded to negative lags.  *lag = -1 when every element is zero. */
 int hzsdr_peak_lag(hzsdr_ctx *ctx, const void *corr_c64, size_t n, int64_t *lag);
 /* The inner loop of PhaseOffsets for one channel pair, align.go:257-266: the
- * mean over i of Phase(a[i] * conj(b[i])) in float64 (radians).  The caller
- * finishes with cmplx.Rect(1, mean) as the reference does. */
+ * mean over i of Phase(a[i] * conj(b[i])) in float64 (radians).  The sum is
+ * compensated: the exact sum of the phases rounded once, then divided, not the
+ * reference's sequential float64 sum (they differ by at most n * pi * 2^-53).
+ * The caller finishes with cmplx.Rect(1, mean) as the reference does. */
 int hzsdr_mean_phase(hzsdr_ctx *ctx, const void *a_c64, const void *b_c64, size_t n,
                      double *mean_phase);
 
