@@ -449,6 +449,14 @@ class Context:
         from .iir import IirBank
         return IirBank(self, kind, sections, rows)
 
+    def symbol_sync(self, kind, params, rows=1):
+        """The symbol-timing recovery bank (include/hzsdr_symsync.h, symsync.SymbolSync): a Gardner loop around a cubic
+        interpolator over `rows` rows of real float32 samples (SYMSYNC_REAL_F32) or complex64 ones (FMT_C64), soft
+        symbols out at the symbol rate.  `params` is float32 (sps, limit, g_mu, g_omega) shared by all rows, or
+        (rows, 4); symsync.loop_gains gives the two gains."""
+        from .symsync import SymbolSync
+        return SymbolSync(self, kind, params, rows)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -890,6 +898,8 @@ from ._capi import COVAR_FORM_ONE_TILE, COVAR_FORM_THREE_TILES  # noqa: E402
 from .covar import Covariance, Scan, bartlett, capon, music, peaks, steering_weights  # noqa: E402
 from ._capi import IIR_FORM_COMPLEX, IIR_FORM_PER_ROW, IIR_MAX_ROWS, IIR_MAX_SECTIONS, IIR_REAL_F32  # noqa: E402
 from .iir import IirBank, butterworth, dc_block, deemphasis, highpass, lowpass, notch, one_pole  # noqa: E402
+from ._capi import SYMSYNC_FORM_COMPLEX, SYMSYNC_FORM_PER_ROW, SYMSYNC_MAX_ROWS, SYMSYNC_REAL_F32  # noqa: E402
+from .symsync import SymbolSync, loop_gains  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

@@ -305,9 +305,26 @@ IIR_REAL_F32 = 32
 IIR_MAX_SECTIONS, IIR_MAX_ROWS = 8, 8192
 IIR_FORM_PER_ROW, IIR_FORM_COMPLEX = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_symsync.h declares
+SYMSYNC_SIGNATURES = {
+    "hzsdr_symsync_create": (i32, [vp, i32, C.POINTER(f32), i32, sz, pvp]),
+    "hzsdr_symsync_push": (i32, [vp, vp, sz, sz, vp, sz, sz, vp, psz]),
+    "hzsdr_symsync_max_symbols": (i32, [vp, sz, psz]),
+    "hzsdr_symsync_set_params": (i32, [vp, C.POINTER(f32)]),
+    "hzsdr_symsync_get_state": (i32, [vp, C.POINTER(f32), sz]),
+    "hzsdr_symsync_set_state": (i32, [vp, C.POINTER(f32), sz, u64]),
+    "hzsdr_symsync_position": (i32, [vp, C.POINTER(u64)]),
+    "hzsdr_symsync_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_symsync_reset": (i32, [vp]),
+    "hzsdr_symsync_free": (i32, [vp]),
+}
+SYMSYNC_REAL_F32 = 32  # (IIR_REAL_F32: one value names the real float32 rows all along the chain)
+SYMSYNC_MAX_ROWS = 8192
+SYMSYNC_FORM_PER_ROW, SYMSYNC_FORM_COMPLEX = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
-                             *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items()):
+                             *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

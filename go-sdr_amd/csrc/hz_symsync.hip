@@ -1,0 +1,461 @@
+// hz_symsync.hip -- the symbol-timing recovery bank (include/hzsdr_symsync.h): a Gardner loop around a cubic interpolator
+// over R rows, real or complex, soft symbols out at the symbol rate.  The arithmetic of every symbol, count and state
+// value is hz_symsync_math.h (shared with the host restatement of tests/host/symsync_ref.cpp); the host arithmetic (rows
+// per wave, the two tiles, their address maps, the loop constants, the bound) is hz_symsync_plan.h.
+//
+// One kernel, in the IIR bank's shape (hz_iir.hip).  A workgroup is ONE wave, and it owns G consecutive rows for the
+// whole push: lane l < G owns row l of them, keeps the row's loop constants and its state in registers from the first
+// tile to the last, reads them from the object's state array before and writes them back behind.  Time goes by in tiles
+// of T samples through the wave's own LDS, so nothing ever waits for another wave:
+//   1. the tile's samples, fetched a tile ahead into registers by all 64 lanes (row fixed, lane = sample), are written
+//      into the sample tile TRANSPOSED, sample t of row r at float t P + r (P odd: one lane per bank);
+//   2. the loads of the NEXT tile are issued, and stay in flight under
+//   3. the walk: lane = row steps t = 0 ... T - 1, eight samples read ahead of the loop, every step computed without a
+//      divergent branch (the lanes' clocks differ: the interpolant and the loop update are predicated) and the symbol,
+//      where the step emits one, written into the SYMBOL TILE at the lane's own count k: float k P + lane.  One
+//      wave-uniform branch stays where a wave owns ONE row (R <= 1024): a sample without a strobe moves the counter
+//      and the samples only;
+//   4. the rows' counts and running totals are broadcast from their lanes, and the symbol tile is stored row by row,
+//      lane = symbol, 64 at a step, every store guarded by the row's capacity.
+// Shared parameters travel in the kernel's arguments: wave-uniform scalars, never lane by lane.
+#include <cmath>
+
+#include "hz_chain_host.h"
+#include "../../include/hzsdr_symsync.h"
+#include "hz_symsync_math.h"
+#include "hz_symsync_plan.h"
+
+struct hzsdr_symsync {
+    hzsdr_ctx *ctx;
+    int kind;
+    uint32_t R;
+    bool per_row;
+    hz::sp::Geom g{};
+    std::vector<float> params;      // the caller's: 4, or R * 4
+    std::vector<hz::sm::Loop> loop;  // derived from them: 1, or R
+    double amin = 1.0;               // the smallest hmin - g_mu over the rows
+    hz::sm::Loop *loop_rows = nullptr;  // per_row: `loop` on the device
+    float *state = nullptr;          // sp::state_floats, sp::state_index
+    uint32_t *maxw = nullptr;        // the largest count of a push, for a caller who asks
+    uint64_t pos = 0;
+};
+
+namespace hz {
+
+struct SymArgs {
+    const void *in;  // row r starts r * in_stride samples in
+    size_t in_stride;
+    void *out;  // row r's symbols start r * out_stride symbols in
+    size_t out_stride, out_cap;
+    uint64_t n;  // samples per row in the push
+    const sm::Loop *loop_rows;
+    float *state;
+    uint32_t *counts, *maxw;
+    uint32_t R, G, P;
+    sm::Loop loop;  // the shared constants
+};
+
+template <int PL> struct SymSrc {
+    using T = float2;
+    static __device__ __forceinline__ void split(float2 v, float (&x)[PL]) { x[0] = v.x, x[PL - 1] = v.y; }
+    static __device__ __forceinline__ float2 pack(float re, float im) { return make_float2(re, im); }
+};
+template <> struct SymSrc<1> {
+    using T = float;
+    static __device__ __forceinline__ void split(float v, float (&x)[1]) { x[0] = v; }
+    static __device__ __forceinline__ float pack(float re, float) { return re; }
+};
+
+// The wave's own LDS traffic in program order: what its lanes wrote is what its lanes read.  The workgroup IS the wave,
+// so no other wave is waited for.
+__device__ __forceinline__ void sym_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A value loaded before the tile loop is waited for HERE, not at its first use inside the loop: a wait placed in the loop
+// would, on every trip, also wait for the next tile's loads that are meant to stay in flight under the walk.
+__device__ __forceinline__ void sym_settle(float v) { asm volatile("" ::"v"(v)); }
+__device__ __forceinline__ void sym_settle(uint32_t v) { asm volatile("" ::"v"(v)); }
+
+// the tile's samples of the wave's rows into registers: lane = sample, K steps of 64 samples per row
+template <int PL, int K>
+__device__ __forceinline__ void sym_fetch(typename SymSrc<PL>::T (&raw)[sp::kMaxGroup][K], const typename SymSrc<PL>::T *in, size_t in_stride, uint32_t g,
+                                          uint64_t t0, uint64_t n, uint32_t lane) {
+#pragma unroll
+    for (uint32_t r = 0; r < sp::kMaxGroup; r++) {
+        if (r < g) {
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint64_t t = t0 + lane + sp::kLanes * k;
+                if (t < n) raw[r][k] = in[r * in_stride + t];
+            }
+        }
+    }
+}
+
+// one sample into the lane's row; its symbol, where there is one, into the lane's next slot of the symbol tile.  The
+// flag alternates whatever the data, so cnt stays below Y (sp::tile_symbols); the comparison costs one instruction and
+// keeps the write inside the tile whatever a state array brought in.
+template <int PL, bool IDLE>
+__device__ __forceinline__ void sym_sample(const float (&x)[PL], float *sy, uint32_t P, uint32_t Y, const sm::Loop &k, sm::State<PL> &s, uint32_t &cnt) {
+    // IDLE: no lane of the wave has a strobe in this sample (wave-uniform: the lanes stay together): only the counters
+    // and the samples move.  With one row per wave that is sps - 2 samples of every sps; with eight rows whose clocks
+    // differ it is next to none (0.6^8 of the samples at 5 per symbol), and the branch only cuts the walk into blocks
+    // (what was measured of both, and what was not: DESIGN.md section 4).
+    if (IDLE && __builtin_amdgcn_ballot_w64(s.c < 1.0f) == 0) {
+        sm::sync_idle<PL>(s, x);
+        return;
+    }
+    float y[PL];
+    const bool emit = sm::sync_step<PL>(s, k, x, y);
+    if (emit && cnt < Y) {
+#pragma unroll
+        for (int p = 0; p < PL; p++) sy[sp::emit_slot(0, cnt, p, P, Y)] = y[p];
+        cnt++;
+    }
+}
+
+// lane = row: samples [0, tn) of the tile through the loop -> the symbols emitted.  Eight samples are read before the
+// steps that consume them, so that no LDS latency sits on the loop-carried path.
+template <int PL, bool IDLE>
+__device__ __forceinline__ uint32_t sym_walk(const float *tl, float *sy, uint32_t P, uint32_t T, uint32_t Y, uint32_t tn, const sm::Loop &k,
+                                             sm::State<PL> &s) {
+    uint32_t cnt = 0, t = 0;
+#pragma unroll 1
+    for (; t + 8 <= tn; t += 8) {
+        float x[8][PL];
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+#pragma unroll
+            for (int p = 0; p < PL; p++) x[j][p] = tl[sp::walk_slot(0, t + j, p, P, T)];
+#pragma unroll
+        for (int j = 0; j < 8; j++) sym_sample<PL, IDLE>(x[j], sy, P, Y, k, s, cnt);
+    }
+#pragma unroll 1
+    for (; t < tn; t++) {
+        float x[PL];
+#pragma unroll
+        for (int p = 0; p < PL; p++) x[p] = tl[sp::walk_slot(0, t, p, P, T)];
+        sym_sample<PL, IDLE>(x, sy, P, Y, k, s, cnt);
+    }
+    return cnt;
+}
+
+template <int PL, int K, bool PER_ROW, bool IDLE>
+__global__ __launch_bounds__(sp::kLanes) void symsync_rows_kernel(SymArgs a) {
+    using Src = SymSrc<PL>;
+    using ST = typename Src::T;
+    constexpr uint32_t T = sp::kLanes * K, Y = sp::tile_symbols(T);
+    extern __shared__ __align__(16) unsigned char symsync_lds[];
+    float *tile = (float *)symsync_lds;
+    float *syms = tile + PL * T * a.P;  // (Geom::sym_base)
+    const uint32_t lane = threadIdx.x;
+    const uint32_t row0 = sp::wave_first_row(blockIdx.x, a.G), g = sp::wave_row_count(blockIdx.x, a.G, a.R);
+    const bool own = lane < g;
+    const size_t row = (size_t)row0 + lane;  // (the lane's row, where it owns one)
+
+    sm::Loop k = a.loop;
+    sm::State<PL> s{};
+    if (own) {
+        if (PER_ROW) k = a.loop_rows[row];
+        const float *z = a.state + row * sp::state_row_floats(PL);
+        s.c = z[sp::kStC];
+        s.h = z[sp::kStH];
+        s.flag = z[sp::kStFlag] != 0.0f ? 1u : 0u;
+#pragma unroll
+        for (int p = 0; p < PL; p++) {
+            s.yp[p] = z[sp::state_index(0, sp::kStYp, p, PL)];
+            s.ym[p] = z[sp::state_index(0, sp::kStYm, p, PL)];
+            s.x1[p] = z[sp::state_index(0, sp::kStX1, p, PL)];
+            s.x2[p] = z[sp::state_index(0, sp::kStX2, p, PL)];
+            s.x3[p] = z[sp::state_index(0, sp::kStX3, p, PL)];
+        }
+    }
+
+    const ST *in = (const ST *)a.in + (size_t)row0 * a.in_stride;
+    ST *out = (ST *)a.out + (size_t)row0 * a.out_stride;
+    ST raw[sp::kMaxGroup][K];
+    sym_fetch<PL, K>(raw, in, a.in_stride, g, 0, a.n, lane);
+    sym_settle(k.g_mu), sym_settle(k.g_omega), sym_settle(k.hmin), sym_settle(k.hmax);
+    sym_settle(s.c), sym_settle(s.h), sym_settle(s.flag);
+#pragma unroll
+    for (int p = 0; p < PL; p++) sym_settle(s.yp[p]), sym_settle(s.ym[p]), sym_settle(s.x1[p]), sym_settle(s.x2[p]), sym_settle(s.x3[p]);
+
+    uint32_t total = 0;  // the lane's row: symbols emitted by the push so far
+#pragma unroll 1
+    for (uint64_t t0 = 0; t0 < a.n; t0 += T) {
+        const uint64_t left = a.n - t0;
+        const uint32_t tn = left < T ? (uint32_t)left : T;
+        // 1. into the sample tile: row fixed, lane = sample
+#pragma unroll
+        for (uint32_t r = 0; r < sp::kMaxGroup; r++) {
+            if (r < g) {
+#pragma unroll
+                for (int kk = 0; kk < K; kk++) {
+                    if (lane + sp::kLanes * kk < tn) {
+                        float x[PL];
+                        Src::split(raw[r][kk], x);
+#pragma unroll
+                        for (int p = 0; p < PL; p++) tile[sp::load_slot(lane, kk, r, p, a.P, T)] = x[p];
+                    }
+                }
+            }
+        }
+        sym_wave_sync();
+        // 2. the next tile's loads, in flight under the walk
+        if (left > T) sym_fetch<PL, K>(raw, in, a.in_stride, g, t0 + T, a.n, lane);
+        // 3. lane = row
+        uint32_t cnt = 0;
+        if (own) cnt = sym_walk<PL, IDLE>(tile + lane, syms + lane, a.P, T, Y, tn, k, s);
+        sym_wave_sync();
+        // 4. out of the symbol tile: row fixed, lane = symbol.  The row's count and total come from its lane; both are
+        // wave-uniform, and so is the loop over the steps of 64.
+#pragma unroll
+        for (uint32_t r = 0; r < sp::kMaxGroup; r++) {
+            if (r < g) {
+                const uint32_t cr = (uint32_t)__builtin_amdgcn_readlane((int)cnt, (int)r);
+                const uint32_t tr = (uint32_t)__builtin_amdgcn_readlane((int)total, (int)r);
+                for (uint32_t j = 0; j * sp::kLanes < cr; j++) {
+                    const uint32_t i = lane + sp::kLanes * j;
+                    const size_t col = (size_t)tr + i;
+                    if (i < cr && col < a.out_cap) {  // (the guard that keeps a garbage row inside its capacity)
+                        const float re = syms[sp::store_slot(lane, j, r, 0, a.P, Y)];
+                        const float im = PL == 2 ? syms[sp::store_slot(lane, j, r, PL - 1, a.P, Y)] : 0.0f;
+                        out[r * a.out_stride + col] = Src::pack(re, im);
+                    }
+                }
+            }
+        }
+        total += cnt;
+        sym_wave_sync();  // (the next tile's symbols overwrite these)
+    }
+
+    if (own) {
+        float *z = a.state + row * sp::state_row_floats(PL);
+        z[sp::kStC] = s.c;
+        z[sp::kStH] = s.h;
+        z[sp::kStFlag] = s.flag ? 1.0f : 0.0f;
+#pragma unroll
+        for (int p = 0; p < PL; p++) {
+            z[sp::state_index(0, sp::kStYp, p, PL)] = s.yp[p];
+            z[sp::state_index(0, sp::kStYm, p, PL)] = s.ym[p];
+            z[sp::state_index(0, sp::kStX1, p, PL)] = s.x1[p];
+            z[sp::state_index(0, sp::kStX2, p, PL)] = s.x2[p];
+            z[sp::state_index(0, sp::kStX3, p, PL)] = s.x3[p];
+        }
+        const uint32_t written = (size_t)total < a.out_cap ? total : (uint32_t)a.out_cap;
+        a.counts[row] = written;
+        if (a.maxw) atomicMax(a.maxw, written);
+    }
+}
+
+static bool sym_complex(int kind) { return kind != HZSDR_SYMSYNC_REAL_F32; }
+static size_t sym_size(int kind) { return sym_complex(kind) ? sizeof(float2) : sizeof(float); }
+
+template <int PL>
+static int sym_launch_kind(hzsdr_symsync *f, const SymArgs &a) {
+    constexpr int K = sp::kSteps;  // (the plan's: f->g.K)
+    const dim3 grid(f->g.waves), block(sp::kLanes);
+    const bool idle = f->g.G == 1;  // one row per wave: the walk skips the samples without a strobe
+    if (f->per_row && idle)
+        HZ_TRY(launch_fv(symsync_rows_kernel<PL, K, true, true>, grid, block, f->g.lds_bytes, f->ctx->stream, a));
+    else if (f->per_row)
+        HZ_TRY(launch_fv(symsync_rows_kernel<PL, K, true, false>, grid, block, f->g.lds_bytes, f->ctx->stream, a));
+    else if (idle)
+        HZ_TRY(launch_fv(symsync_rows_kernel<PL, K, false, true>, grid, block, f->g.lds_bytes, f->ctx->stream, a));
+    else
+        HZ_TRY(launch_fv(symsync_rows_kernel<PL, K, false, false>, grid, block, f->g.lds_bytes, f->ctx->stream, a));
+    HZ_HIP(f->ctx, hipGetLastError());
+    return HZSDR_OK;
+}
+
+static size_t sym_param_sets(const hzsdr_symsync *f) { return f->per_row ? f->R : 1; }
+static size_t sym_state_bytes(const hzsdr_symsync *f) { return sp::state_floats(f->R, f->g.planes) * sizeof(float); }
+
+static int sym_check_params(hzsdr_ctx *ctx, const float *params, size_t sets) {
+    if (!params) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: null params");
+    for (size_t r = 0; r < sets; r++)
+        if (const char *why = sp::check_params(params + r * sp::kParams)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string("symsync: ") + why);
+    return HZSDR_OK;
+}
+
+// validated parameters into the object: the host's copy, the derived constants, the smallest advance, and the device's
+// rows of constants (per-row parameters; shared ones travel with each launch).  The device's rows go first: a copy
+// that fails leaves the object as it was.
+static int sym_take_params(hzsdr_symsync *f, const float *params) {
+    const size_t sets = sym_param_sets(f);
+    std::vector<sm::Loop> loop(sets);
+    double amin = 0.0;
+    for (size_t r = 0; r < sets; r++) {
+        loop[r] = sp::derive(params + r * sp::kParams).loop;
+        const double a = sp::least_advance(params + r * sp::kParams);
+        if (r == 0 || a < amin) amin = a;
+    }
+    if (f->per_row) {
+        HZ_HIP(f->ctx, hipMemcpyAsync(f->loop_rows, loop.data(), sets * sizeof(sm::Loop), hipMemcpyHostToDevice, f->ctx->stream));
+        HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
+    }
+    f->params.assign(params, params + sets * sp::kParams);
+    f->loop.swap(loop);
+    f->amin = amin;
+    return HZSDR_OK;
+}
+
+// the initial state: c = 0, h = h0 of the row, flag = 0, everything else +0
+static int sym_initial_state(hzsdr_symsync *f) {
+    const uint32_t per = sp::state_row_floats(f->g.planes);
+    std::vector<float> z(sp::state_floats(f->R, f->g.planes), 0.0f);
+    for (size_t r = 0; r < f->R; r++) z[r * per + sp::kStH] = sp::derive(f->params.data() + (f->per_row ? r : 0) * sp::kParams).h0;
+    HZ_HIP(f->ctx, hipMemcpyAsync(f->state, z.data(), sym_state_bytes(f), hipMemcpyHostToDevice, f->ctx->stream));
+    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));  // (z is free to go)
+    f->pos = 0;
+    return HZSDR_OK;
+}
+
+}  // namespace hz
+
+extern "C" {
+
+int hzsdr_symsync_create(hzsdr_ctx *ctx, int kind, const float *params, int per_row, size_t rows, hzsdr_symsync **out) {
+    using namespace hz;
+    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (kind != HZSDR_SYMSYNC_REAL_F32 && kind != HZSDR_FMT_C64) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "symsync: real float32 or complex64 rows");
+    if (rows == 0 || rows > sp::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: 1 ... 8192 rows");
+    hzsdr_symsync *f = new hzsdr_symsync{ctx, kind, (uint32_t)rows, per_row != 0};
+    auto undo = [&](int rc) {
+        hzsdr_symsync_free(f);
+        return rc;
+    };
+    int rc = sym_check_params(ctx, params, sym_param_sets(f));
+    if (rc == HZSDR_OK) rc = enter(ctx);
+    if (rc != HZSDR_OK) {
+        delete f;
+        return rc;
+    }
+    f->g = sp::symsync_geom(f->R, sym_complex(kind));
+    hipError_t e = hipMalloc((void **)&f->state, sym_state_bytes(f));
+    if (e == hipSuccess) e = hipMalloc((void **)&f->maxw, sizeof(uint32_t));
+    if (e == hipSuccess && f->per_row) e = hipMalloc((void **)&f->loop_rows, (size_t)f->R * sizeof(sm::Loop));
+    if (e != hipSuccess) return undo(hip_fail(ctx, e, "symsync_create", __FILE__, __LINE__));
+    rc = sym_take_params(f, params);
+    if (rc == HZSDR_OK) rc = sym_initial_state(f);
+    if (rc != HZSDR_OK) return undo(rc);
+    *out = f;
+    return HZSDR_OK;
+}
+
+int hzsdr_symsync_max_symbols(const hzsdr_symsync *f, size_t n, size_t *bound) {
+    if (!f || !bound) return HZSDR_ERR_INVALID_ARGUMENT;
+    *bound = (size_t)hz::sp::max_symbols(n, f->amin);
+    return HZSDR_OK;
+}
+
+int hzsdr_symsync_push(hzsdr_symsync *f, const void *in, size_t n, size_t in_stride, void *out, size_t out_cap, size_t out_stride,
+                       uint32_t *counts, size_t *max_written) {
+    using namespace hz;
+    if (max_written) *max_written = 0;
+    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
+    hzsdr_ctx *ctx = f->ctx;
+    const size_t R = f->R;
+    if (n && (!in || !counts)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: null input or counts");
+    if (R > 1 && in_stride < n) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: in_stride is below the samples of the push");
+    if (f->pos + n < f->pos || n > 0xfffffff0ull) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: the push is too long");
+    const size_t bound = (size_t)sp::max_symbols(n, f->amin);
+    HZ_TRY(check_rows_out(ctx, "symsync", R, out, out_cap, out_stride, bound, 0));
+    HZ_TRY(enter(ctx));
+    if (n == 0) {  // nothing written for any row
+        if (counts && ctx->memspace == HZSDR_MEM_HOST) memset(counts, 0, R * sizeof(uint32_t));
+        if (counts && ctx->memspace != HZSDR_MEM_HOST) HZ_HIP(ctx, hipMemsetAsync(counts, 0, R * sizeof(uint32_t), ctx->stream));
+        return HZSDR_OK;
+    }
+    Stage st(ctx);
+    const void *din;
+    void *dout, *dcounts;
+    size_t dstride, ostride = out_stride;
+    const size_t size = sym_size(f->kind);
+    HZ_TRY(st.in_rows(0, in, R, n, in_stride, size, &din, &dstride));
+    // the columns behind a row's count stay as they are: a HOST context's rows go up before they come back
+    if (R == 1 || out_stride == bound) {
+        HZ_TRY(st.out_preserve(1, out, R * bound * size, &dout));
+    } else {
+        const void *up;
+        HZ_TRY(st.in_rows(1, out, R, bound, out_stride, size, &up, &ostride));
+        HZ_TRY(st.out_rows(1, out, R, bound, out_stride, size, &dout, &ostride));
+    }
+    HZ_TRY(st.out(2, counts, R * sizeof(uint32_t), &dcounts));
+    if (max_written) HZ_HIP(ctx, hipMemsetAsync(f->maxw, 0, sizeof(uint32_t), ctx->stream));
+    SymArgs a{din, dstride, dout, ostride, bound, n, f->loop_rows, f->state, (uint32_t *)dcounts, max_written ? f->maxw : nullptr,
+              f->R, f->g.G, f->g.P, f->loop[0]};
+    HZ_TRY(f->g.planes == 2 ? sym_launch_kind<2>(f, a) : sym_launch_kind<1>(f, a));
+    f->pos += n;
+    HZ_TRY(st.finish());
+    if (max_written) {
+        uint32_t m = 0;
+        HZ_HIP(ctx, hipMemcpyAsync(&m, f->maxw, sizeof m, hipMemcpyDeviceToHost, ctx->stream));
+        HZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *max_written = m;
+    }
+    return HZSDR_OK;
+}
+
+int hzsdr_symsync_set_params(hzsdr_symsync *f, const float *params) {
+    using namespace hz;
+    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
+    HZ_TRY(sym_check_params(f->ctx, params, sym_param_sets(f)));
+    HZ_TRY(enter(f->ctx));
+    return sym_take_params(f, params);  // (behind the pushes so far on the context's stream)
+}
+
+int hzsdr_symsync_get_state(hzsdr_symsync *f, float *state, size_t cap) {
+    using namespace hz;
+    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
+    if (cap < sp::state_floats(f->R, f->g.planes)) return fail(f->ctx, HZSDR_ERR_DST_TOO_SMALL, "symsync: the state array is too small");
+    HZ_TRY(enter(f->ctx));
+    HZ_HIP(f->ctx, hipMemcpyAsync(state, f->state, sym_state_bytes(f), hipMemcpyDeviceToHost, f->ctx->stream));
+    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
+    return HZSDR_OK;
+}
+
+int hzsdr_symsync_set_state(hzsdr_symsync *f, const float *state, size_t count, uint64_t position) {
+    using namespace hz;
+    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
+    if (count != sp::state_floats(f->R, f->g.planes)) return fail(f->ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: the state has rows * 8 (complex rows: 13) floats");
+    HZ_TRY(enter(f->ctx));
+    HZ_HIP(f->ctx, hipMemcpyAsync(f->state, state, sym_state_bytes(f), hipMemcpyHostToDevice, f->ctx->stream));
+    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));  // (the caller's array is free to go)
+    f->pos = position;
+    return HZSDR_OK;
+}
+
+int hzsdr_symsync_position(const hzsdr_symsync *f, uint64_t *position) {
+    if (!f || !position) return HZSDR_ERR_INVALID_ARGUMENT;
+    *position = f->pos;
+    return HZSDR_OK;
+}
+
+int hzsdr_symsync_plan(const hzsdr_symsync *f, size_t *rows_per_wave, size_t *tile_samples, int *form) {
+    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
+    if (rows_per_wave) *rows_per_wave = f->g.G;
+    if (tile_samples) *tile_samples = f->g.T;
+    if (form) *form = (f->per_row ? HZSDR_SYMSYNC_FORM_PER_ROW : 0) | (f->g.planes == 2 ? HZSDR_SYMSYNC_FORM_COMPLEX : 0);
+    return HZSDR_OK;
+}
+
+int hzsdr_symsync_reset(hzsdr_symsync *f) {
+    using namespace hz;
+    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
+    HZ_TRY(enter(f->ctx));
+    return sym_initial_state(f);
+}
+
+int hzsdr_symsync_free(hzsdr_symsync *f) {
+    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
+    hz::bank_release(f->ctx, {f->loop_rows, f->state, f->maxw});
+    delete f;
+    return HZSDR_OK;
+}
+
+}  // extern "C"

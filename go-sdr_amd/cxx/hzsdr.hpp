@@ -32,6 +32,7 @@
 #include "../../include/hzsdr_chanbank.h"
 #include "../../include/hzsdr_covar.h"
 #include "../../include/hzsdr_iir.h"
+#include "../../include/hzsdr_symsync.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1269,6 +1270,75 @@ private:
     size_t rows_, sections_ = 0;
     bool complex_;
     hzsdr_iir *f_ = nullptr;
+};
+
+// The symbol-timing recovery bank (include/hzsdr_symsync.h): a Gardner loop around a cubic interpolator over `rows` rows
+// of HZSDR_SYMSYNC_REAL_F32 samples (float32 symbols: Push) or HZSDR_FMT_C64 ones (complex64 symbols: PushComplex), with
+// the parameters sps, limit, g_mu, g_omega shared by all rows, or rows of them when per_row.  Push runs `n` samples of
+// every row (row r starts r * in_stride samples into `in`; dense rows when in_stride is 0) and returns the rows' symbols,
+// each row cut to its own count; nothing to flush.
+class SymbolSync {
+public:
+    SymbolSync(const Context &x, int kind, const std::vector<float> &params, size_t rows = 1, bool per_row = false)
+        : x_(x), rows_(rows), complex_(kind != HZSDR_SYMSYNC_REAL_F32) {
+        if (params.size() != 4 * (per_row ? rows : 1)) throw std::invalid_argument("SymbolSync: params are 4, or rows * 4 values");
+        check(x_.raw(), hzsdr_symsync_create(x_.raw(), kind, params.data(), per_row ? 1 : 0, rows, &s_));
+    }
+    ~SymbolSync() { if (s_) hzsdr_symsync_free(s_); }
+    SymbolSync(const SymbolSync &) = delete;
+    SymbolSync &operator=(const SymbolSync &) = delete;
+    std::vector<std::vector<float>> Push(const void *in, size_t n, size_t in_stride = 0) {
+        if (complex_) throw std::invalid_argument("SymbolSync: complex rows go through PushComplex");
+        return push<float>(in, n, in_stride);
+    }
+    std::vector<std::vector<std::complex<float>>> PushComplex(const void *in, size_t n, size_t in_stride = 0) {
+        if (!complex_) throw std::invalid_argument("SymbolSync: real rows go through Push");
+        return push<std::complex<float>>(in, n, in_stride);
+    }
+    size_t MaxSymbols(size_t n) const {
+        size_t b = 0;
+        check(x_.raw(), hzsdr_symsync_max_symbols(s_, n, &b));
+        return b;
+    }
+    // the same form; the state and the position stay
+    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_symsync_set_params(s_, params.data())); }
+    // per row c, h, flag, y_prev, y_mid, x1, x2, x3 (hzsdr_symsync.h)
+    std::vector<float> State() const {
+        std::vector<float> z(rows_ * (complex_ ? 13 : 8));
+        check(x_.raw(), hzsdr_symsync_get_state(s_, z.data(), z.size()));
+        return z;
+    }
+    void SetState(const std::vector<float> &z, uint64_t position = 0) { check(x_.raw(), hzsdr_symsync_set_state(s_, z.data(), z.size(), position)); }
+    uint64_t Position() const {
+        uint64_t p = 0;
+        check(x_.raw(), hzsdr_symsync_position(s_, &p));
+        return p;
+    }
+    // -> (rows per wave, samples per tile, HZSDR_SYMSYNC_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_symsync_plan(s_, &g, &t, &f));
+        return {g, t, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_symsync_reset(s_)); }
+    size_t Rows() const { return rows_; }
+
+private:
+    template <class V> std::vector<std::vector<V>> push(const void *in, size_t n, size_t in_stride) {
+        const size_t bound = MaxSymbols(n);
+        std::vector<V> out(rows_ * bound);
+        std::vector<uint32_t> counts(rows_, 0);
+        size_t most = 0;
+        check(x_.raw(), hzsdr_symsync_push(s_, n ? in : nullptr, n, in_stride ? in_stride : n, bound ? out.data() : nullptr, bound, bound, counts.data(), &most));
+        std::vector<std::vector<V>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++) rows[r].assign(out.begin() + r * bound, out.begin() + r * bound + counts[r]);
+        return rows;
+    }
+    const Context &x_;
+    size_t rows_;
+    bool complex_;
+    hzsdr_symsync *s_ = nullptr;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

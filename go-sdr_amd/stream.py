@@ -978,6 +978,31 @@ def iir_rows(src, bank, block=READER_BLOCK):
             yield bank.push(b)
 
 
+# ---- a Reader, or a chain's blocks, through the symbol-timing recovery bank (include/hzsdr_symsync.h) ----
+
+def symbol_rows(src, bank, block=READER_BLOCK):
+    """Push `src` through `bank` (a symsync.SymbolSync on a HOST context) and yield each push's (symbols, counts).
+    `src` is a Reader of complex64 samples, read to its end in blocks of `block` samples (a one-row bank: a BPSK or
+    QPSK carrier), or any iterable of blocks the bank takes as they are -- iir_rows(demodulator_blocks(...)) into a bank
+    of SYMSYNC_REAL_F32 rows.  Row r of a push holds counts[r] symbols; bank.ragged(symbols, counts) cuts them.  The
+    loop's state carries from block to block and there is nothing to flush."""
+    if isinstance(src, Reader):
+        if bank.kind != src.sample_format():
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield bank.push(buf[:k])
+        return
+    for b in src:
+        if b.shape[-1]:
+            yield bank.push(b)
+
+
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
 
 def tuner_rows(r, bank, block=READER_BLOCK):
