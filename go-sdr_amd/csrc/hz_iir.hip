@@ -1,18 +1,13 @@
 // hz_iir.hip -- the IIR bank (include/hzsdr_iir.h): a cascade of S biquads in transposed direct form II over R rows, real
 // or complex.  The arithmetic of every output is hz_iir_math.h (shared with the host restatement of
-// tests/host/iir_ref.cpp); the host arithmetic (rows per wave, the tile, its address maps) is hz_iir_plan.h.
+// tests/host/iir_ref.cpp); the host arithmetic is hz_iir_plan.h.
 //
-// One kernel.  A workgroup is ONE wave, and it owns G consecutive rows for the whole push: lane l < G owns row l of
-// them, keeps the row's coefficients and its 2 S (4 S for complex rows) state values in registers from the first tile
-// to the last, reads them from the object's state array before and writes them back behind.  Time goes by in tiles of
-// T samples through the wave's own LDS, so nothing ever waits for another wave:
-//   1. the tile's raw samples, fetched a tile ahead into registers by all 64 lanes (row fixed, lane = sample: K = 4
-//      instructions per row that cover 256 consecutive samples, 512 bytes or more), are converted and written into
-//      the tile TRANSPOSED, sample t of row r at float t P + r (P odd: one lane per bank);
-//   2. the loads of the NEXT tile are issued, and stay in flight under
-//   3. the recursion: lane = row walks t = 0 ... T - 1, eight samples read ahead of the chain, each y written over its x;
-//      the loop-carried path is two dependent fused steps per section (y -> z1 -> y);
-//   4. the tile is read back row by row (lane = sample again) and stored likewise.
+// One kernel, a row-wave one: the wave, its tile and the four steps of a tile are described in hz_rowwave.h, which
+// holds the wave's sync, the wait before the loop and the fetch.  Lane l < G keeps its row's coefficients and its 2 S
+// (4 S for complex rows) state values in registers from the first tile to the last, reads them from the object's state
+// array before and writes them back behind.  The walk is the recursion: eight samples read ahead of the chain, each y
+// written over its x; the loop-carried path is two dependent fused steps per section (y -> z1 -> y).  The tile is read
+// back as it was written.
 // A shared cascade travels in the kernel's arguments: wave-uniform scalars, never lane by lane.
 #include <cmath>
 
@@ -20,6 +15,7 @@
 #include "../../include/hzsdr_iir.h"
 #include "hz_iir_math.h"
 #include "hz_iir_plan.h"
+#include "hz_rowwave.h"
 
 struct hzsdr_iir {
     hzsdr_ctx *ctx;
@@ -61,34 +57,6 @@ template <> struct IirSrc<HZSDR_IIR_REAL_F32> {
     static __device__ __forceinline__ float2 cvt(float r) { return make_float2(r, 0.0f); }
     static __device__ __forceinline__ float pack(float re, float) { return re; }
 };
-
-// The wave's own LDS traffic in program order: what its lanes wrote is what its lanes read.  The workgroup IS the wave,
-// so no other wave is waited for.
-__device__ __forceinline__ void iir_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A value loaded before the tile loop is waited for HERE, not at its first use inside the loop: a wait placed in the loop
-// would, on every trip, also wait for the next tile's loads that are meant to stay in flight under the recursion.
-__device__ __forceinline__ void iir_settle(float v) { asm volatile("" ::"v"(v)); }
-
-// the tile's samples of the wave's rows into registers: lane = sample, K steps of 64 samples per row
-template <int KIND, int K>
-__device__ __forceinline__ void iir_fetch(typename IirSrc<KIND>::RT (&raw)[ip::kMaxGroup][K], const typename IirSrc<KIND>::RT *in, size_t in_stride,
-                                          uint32_t g, uint64_t t0, uint64_t n, uint32_t lane) {
-#pragma unroll
-    for (uint32_t r = 0; r < ip::kMaxGroup; r++) {
-        if (r < g) {
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                const uint64_t t = t0 + lane + ip::kLanes * k;
-                if (t < n) raw[r][k] = in[r * in_stride + t];
-            }
-        }
-    }
-}
 
 // lane = row: samples [0, tn) of the tile through the S sections, y over x.  Eight samples are read before the chain
 // that consumes them, so that no LDS latency sits on the loop-carried path.
@@ -138,10 +106,7 @@ __global__ __launch_bounds__(ip::kLanes) void iir_rows_kernel(IirArgs a) {
     constexpr uint32_t T = ip::kLanes * K;
     extern __shared__ __align__(16) unsigned char iir_lds[];
     float *tile = (float *)iir_lds;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t row0 = ip::wave_first_row(blockIdx.x, a.G), g = ip::wave_row_count(blockIdx.x, a.G, a.R);
-    const bool own = lane < g;
-    const size_t row = (size_t)row0 + lane;  // (the lane's row, where it owns one)
+    const auto [lane, row0, g, own, row] = rw::wave(a);
 
     float c[ip::kMaxSections][im::kCoefs];
     float z[ip::kMaxSections][2][PL];
@@ -168,15 +133,15 @@ __global__ __launch_bounds__(ip::kLanes) void iir_rows_kernel(IirArgs a) {
     const RT *in = (const RT *)a.in + (size_t)row0 * a.in_stride;
     OT *out = (OT *)a.out + (size_t)row0 * a.out_stride;
     RT raw[ip::kMaxGroup][K];
-    iir_fetch<KIND, K>(raw, in, a.in_stride, g, 0, a.n, lane);
+    rw::fetch<RT, K>(raw, in, a.in_stride, g, 0, a.n, lane);
 #pragma unroll
     for (uint32_t s = 0; s < ip::kMaxSections; s++) {
 #pragma unroll
-        for (int k = 0; k < im::kCoefs; k++) iir_settle(c[s][k]);
+        for (int k = 0; k < im::kCoefs; k++) rw::settle(c[s][k]);
 #pragma unroll
         for (int q = 0; q < 2; q++)
 #pragma unroll
-            for (int p = 0; p < PL; p++) iir_settle(z[s][q][p]);
+            for (int p = 0; p < PL; p++) rw::settle(z[s][q][p]);
     }
 #pragma unroll 1
     for (uint64_t t0 = 0; t0 < a.n; t0 += T) {
@@ -196,9 +161,9 @@ __global__ __launch_bounds__(ip::kLanes) void iir_rows_kernel(IirArgs a) {
                 }
             }
         }
-        iir_wave_sync();
+        rw::wave_sync();
         // 2. the next tile's loads, in flight under the recursion
-        if (left > T) iir_fetch<KIND, K>(raw, in, a.in_stride, g, t0 + T, a.n, lane);
+        if (left > T) rw::fetch<RT, K>(raw, in, a.in_stride, g, t0 + T, a.n, lane);
         // 3. lane = row
         if (own) {
             float *tl = tile + lane;
@@ -213,7 +178,7 @@ __global__ __launch_bounds__(ip::kLanes) void iir_rows_kernel(IirArgs a) {
             default: iir_walk<8, PL>(tl, a.P, T, tn, c, z); break;
             }
         }
-        iir_wave_sync();
+        rw::wave_sync();
         // 4. out of the tile: row fixed, lane = sample
 #pragma unroll
         for (uint32_t r = 0; r < ip::kMaxGroup; r++) {
@@ -229,7 +194,7 @@ __global__ __launch_bounds__(ip::kLanes) void iir_rows_kernel(IirArgs a) {
                 }
             }
         }
-        iir_wave_sync();  // (the next tile's samples overwrite these)
+        rw::wave_sync();  // (the next tile's samples overwrite these)
     }
 
     if (own) {
@@ -272,7 +237,8 @@ static int iir_launch(hzsdr_iir *f, const IirArgs &a) {
 }
 
 static size_t iir_coefs(const hzsdr_iir *f) { return (size_t)(f->per_row ? f->R : 1) * f->S * im::kCoefs; }
-static size_t iir_state_bytes(const hzsdr_iir *f) { return ip::state_floats(f->R, f->S, f->g.planes) * sizeof(float); }
+static size_t iir_state_floats(const hzsdr_iir *f) { return ip::state_floats(f->R, f->S, f->g.planes); }
+static size_t iir_state_bytes(const hzsdr_iir *f) { return iir_state_floats(f) * sizeof(float); }
 
 static int iir_check_sections(hzsdr_ctx *ctx, const float *sections, size_t count) {
     if (!sections) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: null sections");
@@ -283,10 +249,7 @@ static int iir_check_sections(hzsdr_ctx *ctx, const float *sections, size_t coun
 
 // the object's host copy of the coefficients onto the device (per-row cascades; a shared one travels with each launch)
 static int iir_upload(hzsdr_iir *f) {
-    if (!f->per_row) return HZSDR_OK;
-    HZ_HIP(f->ctx, hipMemcpyAsync(f->coef_rows, f->coef.data(), f->coef.size() * sizeof(float), hipMemcpyHostToDevice, f->ctx->stream));
-    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
-    return HZSDR_OK;
+    return f->per_row ? bank_upload(f->ctx, f->coef_rows, f->coef.data(), f->coef.size() * sizeof(float)) : HZSDR_OK;
 }
 
 }  // namespace hz
@@ -368,22 +331,13 @@ int hzsdr_iir_set_sections(hzsdr_iir *f, const float *sections, size_t n_section
 }
 
 int hzsdr_iir_get_state(hzsdr_iir *f, float *state, size_t cap) {
-    using namespace hz;
     if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (cap < ip::state_floats(f->R, f->S, f->g.planes)) return fail(f->ctx, HZSDR_ERR_DST_TOO_SMALL, "iir: the state array is too small");
-    HZ_TRY(enter(f->ctx));
-    HZ_HIP(f->ctx, hipMemcpyAsync(state, f->state, iir_state_bytes(f), hipMemcpyDeviceToHost, f->ctx->stream));
-    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
-    return HZSDR_OK;
+    return hz::bank_state_get(f->ctx, "iir", state, cap, f->state, hz::iir_state_floats(f));
 }
 
 int hzsdr_iir_set_state(hzsdr_iir *f, const float *state, size_t count, uint64_t position) {
-    using namespace hz;
     if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (count != ip::state_floats(f->R, f->S, f->g.planes)) return fail(f->ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: the state has rows * sections * 2 (* 2) floats");
-    HZ_TRY(enter(f->ctx));
-    HZ_HIP(f->ctx, hipMemcpyAsync(f->state, state, iir_state_bytes(f), hipMemcpyHostToDevice, f->ctx->stream));
-    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));  // (the caller's array is free to go)
+    HZ_TRY(hz::bank_state_set(f->ctx, "iir", f->state, state, count, hz::iir_state_floats(f), "the state has rows * sections * 2 (* 2) floats"));
     f->pos = position;
     return HZSDR_OK;
 }

@@ -3,13 +3,10 @@
 // value is hz_symsync_math.h (shared with the host restatement of tests/host/symsync_ref.cpp); the host arithmetic (rows
 // per wave, the two tiles, their address maps, the loop constants, the bound) is hz_symsync_plan.h.
 //
-// One kernel, in the IIR bank's shape (hz_iir.hip).  A workgroup is ONE wave, and it owns G consecutive rows for the
-// whole push: lane l < G owns row l of them, keeps the row's loop constants and its state in registers from the first
-// tile to the last, reads them from the object's state array before and writes them back behind.  Time goes by in tiles
-// of T samples through the wave's own LDS, so nothing ever waits for another wave:
-//   1. the tile's samples, fetched a tile ahead into registers by all 64 lanes (row fixed, lane = sample), are written
-//      into the sample tile TRANSPOSED, sample t of row r at float t P + r (P odd: one lane per bank);
-//   2. the loads of the NEXT tile are issued, and stay in flight under
+// One kernel, a row-wave one: the wave, its sample tile and steps 1 and 2 of a tile are described in hz_rowwave.h,
+// which holds the wave's sync, the wait before the loop and the fetch.  Lane l < G keeps its row's loop constants and
+// its state in registers from the first tile to the last, reads them from the object's state array before and writes
+// them back behind.  Its own:
 //   3. the walk: lane = row steps t = 0 ... T - 1, eight samples read ahead of the loop, every step computed without a
 //      divergent branch (the lanes' clocks differ: the interpolant and the loop update are predicated) and the symbol,
 //      where the step emits one, written into the SYMBOL TILE at the lane's own count k: float k P + lane.  One
@@ -24,6 +21,7 @@
 #include "../../include/hzsdr_symsync.h"
 #include "hz_symsync_math.h"
 #include "hz_symsync_plan.h"
+#include "hz_rowwave.h"
 
 struct hzsdr_symsync {
     hzsdr_ctx *ctx;
@@ -65,35 +63,6 @@ template <> struct SymSrc<1> {
     static __device__ __forceinline__ void split(float v, float (&x)[1]) { x[0] = v; }
     static __device__ __forceinline__ float pack(float re, float) { return re; }
 };
-
-// The wave's own LDS traffic in program order: what its lanes wrote is what its lanes read.  The workgroup IS the wave,
-// so no other wave is waited for.
-__device__ __forceinline__ void sym_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A value loaded before the tile loop is waited for HERE, not at its first use inside the loop: a wait placed in the loop
-// would, on every trip, also wait for the next tile's loads that are meant to stay in flight under the walk.
-__device__ __forceinline__ void sym_settle(float v) { asm volatile("" ::"v"(v)); }
-__device__ __forceinline__ void sym_settle(uint32_t v) { asm volatile("" ::"v"(v)); }
-
-// the tile's samples of the wave's rows into registers: lane = sample, K steps of 64 samples per row
-template <int PL, int K>
-__device__ __forceinline__ void sym_fetch(typename SymSrc<PL>::T (&raw)[sp::kMaxGroup][K], const typename SymSrc<PL>::T *in, size_t in_stride, uint32_t g,
-                                          uint64_t t0, uint64_t n, uint32_t lane) {
-#pragma unroll
-    for (uint32_t r = 0; r < sp::kMaxGroup; r++) {
-        if (r < g) {
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                const uint64_t t = t0 + lane + sp::kLanes * k;
-                if (t < n) raw[r][k] = in[r * in_stride + t];
-            }
-        }
-    }
-}
 
 // one sample into the lane's row; its symbol, where there is one, into the lane's next slot of the symbol tile.  The
 // flag alternates whatever the data, so cnt stays below Y (sp::tile_symbols); the comparison costs one instruction and
@@ -151,10 +120,7 @@ __global__ __launch_bounds__(sp::kLanes) void symsync_rows_kernel(SymArgs a) {
     extern __shared__ __align__(16) unsigned char symsync_lds[];
     float *tile = (float *)symsync_lds;
     float *syms = tile + PL * T * a.P;  // (Geom::sym_base)
-    const uint32_t lane = threadIdx.x;
-    const uint32_t row0 = sp::wave_first_row(blockIdx.x, a.G), g = sp::wave_row_count(blockIdx.x, a.G, a.R);
-    const bool own = lane < g;
-    const size_t row = (size_t)row0 + lane;  // (the lane's row, where it owns one)
+    const auto [lane, row0, g, own, row] = rw::wave(a);
 
     sm::Loop k = a.loop;
     sm::State<PL> s{};
@@ -177,11 +143,11 @@ __global__ __launch_bounds__(sp::kLanes) void symsync_rows_kernel(SymArgs a) {
     const ST *in = (const ST *)a.in + (size_t)row0 * a.in_stride;
     ST *out = (ST *)a.out + (size_t)row0 * a.out_stride;
     ST raw[sp::kMaxGroup][K];
-    sym_fetch<PL, K>(raw, in, a.in_stride, g, 0, a.n, lane);
-    sym_settle(k.g_mu), sym_settle(k.g_omega), sym_settle(k.hmin), sym_settle(k.hmax);
-    sym_settle(s.c), sym_settle(s.h), sym_settle(s.flag);
+    rw::fetch<ST, K>(raw, in, a.in_stride, g, 0, a.n, lane);
+    rw::settle(k.g_mu), rw::settle(k.g_omega), rw::settle(k.hmin), rw::settle(k.hmax);
+    rw::settle(s.c), rw::settle(s.h), rw::settle(s.flag);
 #pragma unroll
-    for (int p = 0; p < PL; p++) sym_settle(s.yp[p]), sym_settle(s.ym[p]), sym_settle(s.x1[p]), sym_settle(s.x2[p]), sym_settle(s.x3[p]);
+    for (int p = 0; p < PL; p++) rw::settle(s.yp[p]), rw::settle(s.ym[p]), rw::settle(s.x1[p]), rw::settle(s.x2[p]), rw::settle(s.x3[p]);
 
     uint32_t total = 0;  // the lane's row: symbols emitted by the push so far
 #pragma unroll 1
@@ -198,18 +164,18 @@ __global__ __launch_bounds__(sp::kLanes) void symsync_rows_kernel(SymArgs a) {
                         float x[PL];
                         Src::split(raw[r][kk], x);
 #pragma unroll
-                        for (int p = 0; p < PL; p++) tile[sp::load_slot(lane, kk, r, p, a.P, T)] = x[p];
+                        for (int p = 0; p < PL; p++) tile[sp::move_slot(lane, kk, r, p, a.P, T)] = x[p];
                     }
                 }
             }
         }
-        sym_wave_sync();
+        rw::wave_sync();
         // 2. the next tile's loads, in flight under the walk
-        if (left > T) sym_fetch<PL, K>(raw, in, a.in_stride, g, t0 + T, a.n, lane);
+        if (left > T) rw::fetch<ST, K>(raw, in, a.in_stride, g, t0 + T, a.n, lane);
         // 3. lane = row
         uint32_t cnt = 0;
         if (own) cnt = sym_walk<PL, IDLE>(tile + lane, syms + lane, a.P, T, Y, tn, k, s);
-        sym_wave_sync();
+        rw::wave_sync();
         // 4. out of the symbol tile: row fixed, lane = symbol.  The row's count and total come from its lane; both are
         // wave-uniform, and so is the loop over the steps of 64.
 #pragma unroll
@@ -229,7 +195,7 @@ __global__ __launch_bounds__(sp::kLanes) void symsync_rows_kernel(SymArgs a) {
             }
         }
         total += cnt;
-        sym_wave_sync();  // (the next tile's symbols overwrite these)
+        rw::wave_sync();  // (the next tile's symbols overwrite these)
     }
 
     if (own) {
@@ -272,7 +238,8 @@ static int sym_launch_kind(hzsdr_symsync *f, const SymArgs &a) {
 }
 
 static size_t sym_param_sets(const hzsdr_symsync *f) { return f->per_row ? f->R : 1; }
-static size_t sym_state_bytes(const hzsdr_symsync *f) { return sp::state_floats(f->R, f->g.planes) * sizeof(float); }
+static size_t sym_state_floats(const hzsdr_symsync *f) { return sp::state_floats(f->R, f->g.planes); }
+static size_t sym_state_bytes(const hzsdr_symsync *f) { return sym_state_floats(f) * sizeof(float); }
 
 static int sym_check_params(hzsdr_ctx *ctx, const float *params, size_t sets) {
     if (!params) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: null params");
@@ -293,10 +260,7 @@ static int sym_take_params(hzsdr_symsync *f, const float *params) {
         const double a = sp::least_advance(params + r * sp::kParams);
         if (r == 0 || a < amin) amin = a;
     }
-    if (f->per_row) {
-        HZ_HIP(f->ctx, hipMemcpyAsync(f->loop_rows, loop.data(), sets * sizeof(sm::Loop), hipMemcpyHostToDevice, f->ctx->stream));
-        HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
-    }
+    if (f->per_row) HZ_TRY(bank_upload(f->ctx, f->loop_rows, loop.data(), sets * sizeof(sm::Loop)));
     f->params.assign(params, params + sets * sp::kParams);
     f->loop.swap(loop);
     f->amin = amin;
@@ -306,10 +270,9 @@ static int sym_take_params(hzsdr_symsync *f, const float *params) {
 // the initial state: c = 0, h = h0 of the row, flag = 0, everything else +0
 static int sym_initial_state(hzsdr_symsync *f) {
     const uint32_t per = sp::state_row_floats(f->g.planes);
-    std::vector<float> z(sp::state_floats(f->R, f->g.planes), 0.0f);
+    std::vector<float> z(sym_state_floats(f), 0.0f);
     for (size_t r = 0; r < f->R; r++) z[r * per + sp::kStH] = sp::derive(f->params.data() + (f->per_row ? r : 0) * sp::kParams).h0;
-    HZ_HIP(f->ctx, hipMemcpyAsync(f->state, z.data(), sym_state_bytes(f), hipMemcpyHostToDevice, f->ctx->stream));
-    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));  // (z is free to go)
+    HZ_TRY(bank_upload(f->ctx, f->state, z.data(), sym_state_bytes(f)));
     f->pos = 0;
     return HZSDR_OK;
 }
@@ -410,22 +373,13 @@ int hzsdr_symsync_set_params(hzsdr_symsync *f, const float *params) {
 }
 
 int hzsdr_symsync_get_state(hzsdr_symsync *f, float *state, size_t cap) {
-    using namespace hz;
     if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (cap < sp::state_floats(f->R, f->g.planes)) return fail(f->ctx, HZSDR_ERR_DST_TOO_SMALL, "symsync: the state array is too small");
-    HZ_TRY(enter(f->ctx));
-    HZ_HIP(f->ctx, hipMemcpyAsync(state, f->state, sym_state_bytes(f), hipMemcpyDeviceToHost, f->ctx->stream));
-    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
-    return HZSDR_OK;
+    return hz::bank_state_get(f->ctx, "symsync", state, cap, f->state, hz::sym_state_floats(f));
 }
 
 int hzsdr_symsync_set_state(hzsdr_symsync *f, const float *state, size_t count, uint64_t position) {
-    using namespace hz;
     if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (count != sp::state_floats(f->R, f->g.planes)) return fail(f->ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: the state has rows * 8 (complex rows: 13) floats");
-    HZ_TRY(enter(f->ctx));
-    HZ_HIP(f->ctx, hipMemcpyAsync(f->state, state, sym_state_bytes(f), hipMemcpyHostToDevice, f->ctx->stream));
-    HZ_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));  // (the caller's array is free to go)
+    HZ_TRY(hz::bank_state_set(f->ctx, "symsync", f->state, state, count, hz::sym_state_floats(f), "the state has rows * 8 (complex rows: 13) floats"));
     f->pos = position;
     return HZSDR_OK;
 }

@@ -1,15 +1,10 @@
 // hz_symsync_plan.h -- the host arithmetic of the symbol-timing recovery bank (include/hzsdr_symsync.h), HIP-free so that
-// tests/host/symsync_plan.cpp can run it under the sanitizers: how the rows are dealt to waves, the two tiles and
-// their LDS request, the address maps the kernel itself uses (a host program counts bank conflicts from the same
-// functions), the derivation and validation of a row's loop constants, the bound on a push's symbols and the indices
-// of the kept state.
+// tests/host/symsync_plan.cpp can run it under the sanitizers.  The bank is a row-wave bank: how the rows are dealt to
+// waves, the sample tile and its address maps are hz_rowwave_plan.h, with the reasons.  Here: the symbol tile, its
+// address maps (a host program counts bank conflicts from the same functions) and the LDS request of both tiles, the
+// derivation and validation of a row's loop constants, the bound on a push's symbols and the indices of the kept state.
 //
-// The shape is the IIR bank's (hz_iir_plan.h): a workgroup is one wave, it owns G = ceil(R / 1024)
-// consecutive rows (8 at most) for the whole push, lane = row walks time, and time goes by in tiles of T = 256 samples
-// stored TRANSPOSED in the wave's own LDS -- sample t of row r at float t * P + r of its plane, P = G made odd, re and
-// im in planes of their own.
-//
-// New here: the output is ragged.  A strobe is found at most once per sample and the flag alternates between the
+// The output is ragged.  A strobe is found at most once per sample and the flag alternates between the
 // mid-symbol and the symbol strobe whatever the data, so a tile of T samples emits at most T / 2 + 1 symbols per row
 // (tile_symbols; T / 2 when T is even, one more kept in hand).  The SYMBOL TILE holds them apart from the sample tile:
 // the k-th symbol of the tile of row r at float k * P + r of its plane, (T / 2 + 1) * P floats per plane.  The walk
@@ -22,70 +17,36 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "hz_plan.h"
+#include "hz_rowwave_plan.h"
 #include "hz_symsync_math.h"
 
 namespace hz {
 namespace sp {
 
-constexpr uint32_t kMaxRows = 8192, kLanes = 64;
-constexpr uint32_t kWaves = 1024;   // the waves the rows are spread over before a wave takes a second row
-constexpr uint32_t kMaxGroup = 8;   // rows per wave at most: kMaxRows / kWaves
-static_assert(kMaxRows <= kWaves * kMaxGroup, "a wave's rows are unrolled kMaxGroup times");
-constexpr uint32_t kSteps = 4;      // K: samples of a row per lane and tile
-constexpr uint32_t kParams = 4;     // sps, limit, g_mu, g_omega
-constexpr size_t kLdsBudget = 66 * 1024;  // the family's LDS budget per workgroup
-constexpr size_t kLdsOwn = 28 * 1024;     // what both tiles of this bank stay under
+using rw::kMaxRows, rw::kLanes, rw::kWaves, rw::kMaxGroup, rw::kSteps, rw::kLdsBudget;
+using rw::wave_first_row, rw::wave_row_count, rw::tile_slot, rw::move_slot, rw::walk_slot;
+
+constexpr uint32_t kParams = 4;        // sps, limit, g_mu, g_omega
+constexpr size_t kLdsOwn = 28 * 1024;  // what both tiles of this bank stay under
 
 // the most symbols of one row out of a tile of T samples
 constexpr uint32_t tile_symbols(uint32_t T) { return T / 2 + 1; }
 
-struct Geom {
-    uint32_t G;       // rows per wave (the last wave may own fewer)
-    uint32_t waves;   // ceil(R / G)
-    uint32_t P;       // floats from one sample (one symbol) of a tile to the next: G made odd
-    uint32_t K;       // samples of a row per lane and tile
-    uint32_t T;       // samples per tile: 64 K
-    uint32_t Y;       // symbols per row the symbol tile holds: tile_symbols(T)
-    uint32_t planes;  // 1: real rows, 2: complex rows (re, im)
+struct Geom : rw::Geom {  // (P is also the floats from one symbol of the symbol tile to the next)
+    uint32_t Y;         // symbols per row the symbol tile holds: tile_symbols(T)
     uint32_t sym_base;  // floats from the start of the LDS to the symbol tile
     size_t lds_bytes;
 };
 
 inline Geom symsync_geom(uint32_t rows, bool complex_rows) {
-    Geom g{};
-    g.G = (rows + kWaves - 1) / kWaves;
-    if (g.G < 1) g.G = 1;
-    if (g.G > kMaxGroup) g.G = kMaxGroup;
-    g.waves = (rows + g.G - 1) / g.G;
-    g.P = g.G | 1u;
-    g.K = kSteps;
-    g.T = kLanes * g.K;
+    Geom g{rw::geom(rows, complex_rows), 0, 0, 0};
     g.Y = tile_symbols(g.T);
-    g.planes = complex_rows ? 2u : 1u;
-    g.sym_base = g.planes * g.T * g.P;
+    g.sym_base = rw::tile_floats(g);
     g.lds_bytes = ((size_t)g.sym_base + (size_t)g.planes * g.Y * g.P) * 4;
     return g;
 }
 
-// the rows of wave w: [first, first + count)
-HZ_HD uint32_t wave_first_row(uint32_t w, uint32_t G) { return w * G; }
-HZ_HD uint32_t wave_row_count(uint32_t w, uint32_t G, uint32_t rows) {
-    const uint32_t first = w * G;
-    return first >= rows ? 0u : (rows - first < G ? rows - first : G);
-}
-
-// ---- the sample tile's address maps, in floats from the start of the wave's LDS ----
-// sample t of row r (of the wave), plane p
-HZ_HD uint32_t tile_slot(uint32_t t, uint32_t r, uint32_t p, uint32_t P, uint32_t T) { return p * T * P + t * P + r; }
-// the loader: lane l, step k of K, row r
-HZ_HD uint32_t load_slot(uint32_t lane, uint32_t k, uint32_t r, uint32_t p, uint32_t P, uint32_t T) {
-    return tile_slot(lane + kLanes * k, r, p, P, T);
-}
-// the walk: lane l owns row l, at sample t
-HZ_HD uint32_t walk_slot(uint32_t lane, uint32_t t, uint32_t p, uint32_t P, uint32_t T) { return tile_slot(t, lane, p, P, T); }
-
-// ---- the symbol tile's, in floats from its own start (Geom::sym_base) ----
+// ---- the symbol tile's address maps, in floats from its own start (Geom::sym_base) ----
 // symbol k of the tile of row r, plane p; Y = tile_symbols(T)
 HZ_HD uint32_t sym_slot(uint32_t k, uint32_t r, uint32_t p, uint32_t P, uint32_t Y) { return p * Y * P + k * P + r; }
 // the walk: lane l owns row l and writes its k-th symbol of the tile

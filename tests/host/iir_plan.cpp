@@ -1,5 +1,6 @@
 // iir_plan.cpp -- csrc/hz_iir_plan.h as a stand-alone program, built with -fsanitize=address,undefined by
-// tests/test_iir_plan.py.  For every R = 1 ... 8192, each input kind (real float32; complex from 8-, 4- and 2-byte
+// tests/test_iir_plan.py (what it shares with the symbol-timing bank, csrc/hz_rowwave_plan.h, by the checks of
+// rowwave_check.h).  For every R = 1 ... 8192, each input kind (real float32; complex from 8-, 4- and 2-byte
 // samples) and every S = 1 ... 8:
 //   - the LDS request is planes * T * P * 4 bytes, inside the family's budget, and a tile covers 256 bytes of a row;
 //   - the waves' rows cover [0, R) exactly once, in order, 1 ... G rows each, G <= kMaxGroup;
@@ -9,68 +10,17 @@
 //   - the lanes per bank, bank = slot mod 32, in each 32-lane group of both accesses (the loader / storer: row fixed,
 //     lane = sample; the recursion: sample fixed, lane = row) are 1.
 // Prints "banks: G K planes move walk" per geometry, "largest lds: bytes", and "iir_plan ok".
-#include <cstdint>
-#include <cstdio>
 #include <set>
 #include <tuple>
-#include <vector>
 
 #include "hz_iir_plan.h"
+#include "rowwave_check.h"
 
 using namespace hz::ip;
 
-static int failures = 0;
-#define CHECK(cond)                                                \
-    do {                                                           \
-        if (!(cond)) {                                             \
-            if (failures++ < 20) printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-        }                                                          \
-    } while (0)
-
-// the largest number of lanes of one 32-lane group that share a bank
-static uint32_t worst(const std::vector<uint32_t> &slots) {
-    uint32_t w = 0;
-    for (size_t base = 0; base < slots.size(); base += 32) {
-        uint32_t per[32] = {0};
-        for (size_t l = base; l < base + 32 && l < slots.size(); l++) {
-            const uint32_t c = ++per[slots[l] % 32];
-            if (c > w) w = c;
-        }
-    }
-    return w;
-}
-
 static void check_geometry(const Geom &g) {
-    const uint32_t floats = g.planes * g.T * g.P;
-    std::vector<int> seen(floats, 0);
-    uint32_t move = 0, walk = 0;
-    for (uint32_t p = 0; p < g.planes; p++) {
-        for (uint32_t r = 0; r < g.G; r++)
-            for (uint32_t k = 0; k < g.K; k++) {
-                std::vector<uint32_t> slots;
-                for (uint32_t lane = 0; lane < kLanes; lane++) {
-                    const uint32_t s = move_slot(lane, k, r, p, g.P, g.T);
-                    CHECK(s < floats);
-                    if (s < floats) seen[s]++;
-                    CHECK(s == walk_slot(r, lane + kLanes * k, p, g.P, g.T));
-                    slots.push_back(s);
-                }
-                const uint32_t w = worst(slots);
-                if (w > move) move = w;
-            }
-        for (uint32_t t = 0; t < g.T; t++) {
-            std::vector<uint32_t> slots;
-            for (uint32_t lane = 0; lane < g.G; lane++) slots.push_back(walk_slot(lane, t, p, g.P, g.T));
-            const uint32_t w = worst(slots);
-            if (w > walk) walk = w;
-        }
-    }
-    uint32_t used = 0;
-    for (uint32_t s = 0; s < floats; s++) {
-        CHECK(seen[s] <= 1);
-        used += seen[s];
-    }
-    CHECK(used == g.planes * g.T * g.G);
+    uint32_t move, walk;
+    check_tile(g, &move, &walk);
     CHECK(move == 1 && walk == 1);
     printf("banks: %u %u %u %u %u\n", g.G, g.K, g.planes, move, walk);
 }
@@ -92,15 +42,7 @@ int main() {
             CHECK((size_t)g.T * kd.bytes >= kRunBytes);
             CHECK(g.lds_bytes == (size_t)g.planes * g.T * g.P * 4 && g.lds_bytes <= kLdsBudget);
             if (g.lds_bytes > largest) largest = g.lds_bytes;
-            // the rows, wave by wave
-            uint32_t next = 0;
-            CHECK(g.waves == (R + g.G - 1) / g.G);
-            for (uint32_t w = 0; w < g.waves; w++) {
-                const uint32_t c = wave_row_count(w, g.G, R);
-                CHECK(wave_first_row(w, g.G) == next && c >= 1 && c <= g.G);
-                next += c;
-            }
-            CHECK(next == R && wave_row_count(g.waves, g.G, R) == 0);
+            check_rows(g, R);
             for (uint32_t S = 1; S <= kMaxSections; S++) {
                 CHECK(state_floats(R, S, g.planes) == (size_t)R * S * 2 * g.planes);
                 // the first, a middle and the last row's state values are consecutive runs in row order

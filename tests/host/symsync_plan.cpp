@@ -1,5 +1,6 @@
 // symsync_plan.cpp -- csrc/hz_symsync_plan.h as a stand-alone program, built with -fsanitize=address,undefined by
-// tests/test_symsync_plan.py.  For every R = 1 ... 8192 and both kinds:
+// tests/test_symsync_plan.py (what it shares with the IIR bank, csrc/hz_rowwave_plan.h, by the checks of
+// rowwave_check.h).  For every R = 1 ... 8192 and both kinds:
 //   - the LDS request is (planes T P + planes (T / 2 + 1) P) * 4 bytes, under 28 KiB and so inside the family's budget;
 //   - the waves' rows cover [0, R) exactly once, in order, 1 ... G rows each, G <= kMaxGroup;
 //   - the state index is a bijection onto [0, state_floats), in the documented order;
@@ -20,58 +21,25 @@
 // way through a sample in which no lane has a strobe) against sync_step, every state word.
 // Prints "banks: G planes load walk emit store" per geometry, "largest lds: bytes", and "symsync_plan ok".
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <set>
 #include <tuple>
 #include <vector>
 
 #include "hz_symsync_plan.h"
+#include "rowwave_check.h"
 
 using namespace hz::sp;
-
-static int failures = 0;
-#define CHECK(cond)                                                \
-    do {                                                           \
-        if (!(cond)) {                                             \
-            if (failures++ < 20) printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-        }                                                          \
-    } while (0)
-
-// the largest number of lanes of one 32-lane group that share a bank
-static uint32_t worst(const std::vector<uint32_t> &slots) {
-    uint32_t w = 0;
-    for (size_t base = 0; base < slots.size(); base += 32) {
-        uint32_t per[32] = {0};
-        for (size_t l = base; l < base + 32 && l < slots.size(); l++) {
-            const uint32_t c = ++per[slots[l] % 32];
-            if (c > w) w = c;
-        }
-    }
-    return w;
-}
 
 static void check_geometry(const Geom &g) {
     const uint32_t samples = g.planes * g.T * g.P, symbols = g.planes * g.Y * g.P;
     CHECK(g.sym_base == samples && g.lds_bytes == (size_t)(samples + symbols) * 4);
-    std::vector<int> seen(samples, 0), seen_y(symbols, 0);
-    uint32_t load = 0, walk = 0, emit = 0, store = 0;
+    std::vector<int> seen_y(symbols, 0);
+    uint32_t load, walk, emit = 0, store = 0;
+    check_tile(g, &load, &walk);
     const uint32_t steps = (g.Y + kLanes - 1) / kLanes;
     for (uint32_t p = 0; p < g.planes; p++) {
-        for (uint32_t r = 0; r < g.G; r++) {
-            for (uint32_t k = 0; k < g.K; k++) {
-                std::vector<uint32_t> slots;
-                for (uint32_t lane = 0; lane < kLanes; lane++) {
-                    const uint32_t s = load_slot(lane, k, r, p, g.P, g.T);
-                    CHECK(s < samples);
-                    if (s < samples) seen[s]++;
-                    CHECK(s == walk_slot(r, lane + kLanes * k, p, g.P, g.T));
-                    slots.push_back(s);
-                }
-                const uint32_t w = worst(slots);
-                if (w > load) load = w;
-            }
+        for (uint32_t r = 0; r < g.G; r++)
             for (uint32_t j = 0; j < steps; j++) {
                 std::vector<uint32_t> slots;
                 for (uint32_t lane = 0; lane < kLanes && lane + kLanes * j < g.Y; lane++) {
@@ -84,13 +52,6 @@ static void check_geometry(const Geom &g) {
                 const uint32_t w = worst(slots);
                 if (w > store) store = w;
             }
-        }
-        for (uint32_t t = 0; t < g.T; t++) {
-            std::vector<uint32_t> slots;
-            for (uint32_t lane = 0; lane < g.G; lane++) slots.push_back(walk_slot(lane, t, p, g.P, g.T));
-            const uint32_t w = worst(slots);
-            if (w > walk) walk = w;
-        }
         for (uint32_t k = 0; k < g.Y; k++) {
             std::vector<uint32_t> slots;
             for (uint32_t lane = 0; lane < g.G; lane++) slots.push_back(emit_slot(lane, k, p, g.P, g.Y));
@@ -98,16 +59,12 @@ static void check_geometry(const Geom &g) {
             if (w > emit) emit = w;
         }
     }
-    uint32_t used = 0, used_y = 0;
-    for (uint32_t s = 0; s < samples; s++) {
-        CHECK(seen[s] <= 1);
-        used += seen[s];
-    }
+    uint32_t used_y = 0;
     for (uint32_t s = 0; s < symbols; s++) {
         CHECK(seen_y[s] <= 1);
         used_y += seen_y[s];
     }
-    CHECK(used == g.planes * g.T * g.G && used_y == g.planes * g.Y * g.G);
+    CHECK(used_y == g.planes * g.Y * g.G);
     CHECK(load == 1 && walk == 1 && emit == 1 && store == 1);
     printf("banks: %u %u %u %u %u %u\n", g.G, g.planes, load, walk, emit, store);
 }
@@ -259,14 +216,7 @@ int main() {
             CHECK(g.lds_bytes == ((size_t)g.planes * g.T * g.P + (size_t)g.planes * g.Y * g.P) * 4);
             CHECK(g.lds_bytes < kLdsOwn && kLdsOwn <= kLdsBudget);
             if (g.lds_bytes > largest) largest = g.lds_bytes;
-            uint32_t next = 0;
-            CHECK(g.waves == (R + g.G - 1) / g.G);
-            for (uint32_t w = 0; w < g.waves; w++) {
-                const uint32_t c = wave_row_count(w, g.G, R);
-                CHECK(wave_first_row(w, g.G) == next && c >= 1 && c <= g.G);
-                next += c;
-            }
-            CHECK(next == R && wave_row_count(g.waves, g.G, R) == 0);
+            check_rows(g, R);
             CHECK(state_floats(R, g.planes) == (size_t)R * (cplx ? 13 : 8) && state_row_floats(g.planes) == (cplx ? 13u : 8u));
             for (uint32_t r : {0u, R / 2, R - 1}) {
                 size_t want = (size_t)r * state_row_floats(g.planes);

@@ -94,8 +94,9 @@ def test_constants_match_header(hz):
     assert int(defs["HZSDR_IIR_FORM_COMPLEX"]) == hz.IIR_FORM_COMPLEX == ref.FORM_COMPLEX == 2
     assert int(defs["HZSDR_IIR_MAX_SECTIONS"]) == hz.IIR_MAX_SECTIONS == 8
     assert int(defs["HZSDR_IIR_MAX_ROWS"]) == hz.IIR_MAX_ROWS == 8192
-    plan = open(os.path.join(ROOT, "go-sdr_amd", "csrc", "hz_iir_plan.h")).read()
-    assert "kMaxRows = 8192, kMaxSections = 8, kLanes = 64" in plan
+    csrc = os.path.join(ROOT, "go-sdr_amd", "csrc")
+    assert "kMaxRows = 8192, kLanes = 64" in open(os.path.join(csrc, "hz_rowwave_plan.h")).read()  # (the row-wave banks')
+    assert "kMaxSections = 8;" in open(os.path.join(csrc, "hz_iir_plan.h")).read()
     assert hz.IIR_REAL_F32 is importlib.import_module("go-sdr_amd.iir").IIR_REAL_F32
 
 

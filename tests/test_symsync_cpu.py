@@ -99,8 +99,9 @@ def test_constants_match_header(hz):
     assert int(defs["HZSDR_SYMSYNC_FORM_PER_ROW"]) == hz.SYMSYNC_FORM_PER_ROW == ref.FORM_PER_ROW == 1
     assert int(defs["HZSDR_SYMSYNC_FORM_COMPLEX"]) == hz.SYMSYNC_FORM_COMPLEX == ref.FORM_COMPLEX == 2
     assert int(defs["HZSDR_SYMSYNC_MAX_ROWS"]) == hz.SYMSYNC_MAX_ROWS == ref.MAX_ROWS == 8192
-    plan = open(os.path.join(ROOT, "go-sdr_amd", "csrc", "hz_symsync_plan.h")).read()
-    assert "kMaxRows = 8192, kLanes = 64" in plan and "kParams = 4" in plan
+    csrc = os.path.join(ROOT, "go-sdr_amd", "csrc")
+    assert "kMaxRows = 8192, kLanes = 64" in open(os.path.join(csrc, "hz_rowwave_plan.h")).read()  # (the row-wave banks')
+    assert "kParams = 4;" in open(os.path.join(csrc, "hz_symsync_plan.h")).read()
     assert hz.SYMSYNC_REAL_F32 is importlib.import_module("go-sdr_amd.symsync").SYMSYNC_REAL_F32
 
 
