@@ -6,6 +6,7 @@ import importlib
 import numpy as np
 import pytest
 
+from spectrum_ref import want_rows
 from util import FMT, splitmix64
 
 pytestmark = pytest.mark.gpu
@@ -59,20 +60,6 @@ def converted(orc, x):
     return out
 
 
-def want_rows(c, n, hop, avg, w, scale):
-    """float64 restatement: the complete rows of one stream of converted samples c, ZeroFirst."""
-    L = c.shape[0]
-    F = (L - n) // hop + 1 if L >= n else 0
-    rows = F // avg
-    if rows == 0:
-        return np.zeros((0, n))
-    idx = np.arange(rows * avg)[:, None] * hop + np.arange(n)[None, :]
-    w64 = np.ones(n) if w is None else w.astype(np.float64)
-    X = np.fft.fft(c.astype(np.complex128)[idx] * w64, axis=1)
-    p = (X.real ** 2 + X.imag ** 2).reshape(rows, avg, n).sum(axis=1)
-    return float(scale) * p
-
-
 def bound(n, avg):
     return 2 * (3e-7 * np.log2(n) + 1e-7) + 6e-8 * (avg + 4)
 
@@ -107,7 +94,7 @@ def push_all(s, x, cuts=None):
 # ---- 1. accuracy -------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("fmt", ["u8", "i8", "i16", "c64"])
-@pytest.mark.parametrize("n", [256, 1024, 4096, 8192])
+@pytest.mark.parametrize("n", [256, 512, 1024, 2048, 4096, 8192])
 def test_rows_against_float64(hz, sp, orc, ctx, fmt, n):
     worst = 0.0
     for hop in (1, n // 2, n, n + 37):
