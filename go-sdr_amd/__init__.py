@@ -457,6 +457,14 @@ class Context:
         from .symsync import SymbolSync
         return SymbolSync(self, kind, params, rows)
 
+    def carrier_loop(self, mode, params, rows=1, per_row=False):
+        """The carrier recovery bank (include/hzsdr_carrier.h, carrier.CarrierLoop): a second-order loop around a
+        numerically controlled oscillator over `rows` complex64 rows, one derotated output per input; `mode` is
+        CARRIER_TONE, CARRIER_BPSK or CARRIER_QPSK.  `params` is float32 (alpha, beta, f0, fmin, fmax) shared by all
+        rows, or (rows, 5) with per_row; carrier.carrier_gains gives the two gains."""
+        from .carrier import CarrierLoop
+        return CarrierLoop(self, mode, params, rows, per_row)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -900,6 +908,8 @@ from ._capi import IIR_FORM_COMPLEX, IIR_FORM_PER_ROW, IIR_MAX_ROWS, IIR_MAX_SEC
 from .iir import IirBank, butterworth, dc_block, deemphasis, highpass, lowpass, notch, one_pole  # noqa: E402
 from ._capi import SYMSYNC_FORM_COMPLEX, SYMSYNC_FORM_PER_ROW, SYMSYNC_MAX_ROWS, SYMSYNC_REAL_F32  # noqa: E402
 from .symsync import SymbolSync, loop_gains  # noqa: E402
+from ._capi import CARRIER_BPSK, CARRIER_FORM_MODE, CARRIER_FORM_PER_ROW, CARRIER_MAX_ROWS, CARRIER_QPSK, CARRIER_TONE  # noqa: E402
+from .carrier import CarrierLoop, carrier_gains  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

@@ -322,9 +322,26 @@ SYMSYNC_REAL_F32 = 32  # (IIR_REAL_F32: one value names the real float32 rows al
 SYMSYNC_MAX_ROWS = 8192
 SYMSYNC_FORM_PER_ROW, SYMSYNC_FORM_COMPLEX = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_carrier.h declares
+CARRIER_SIGNATURES = {
+    "hzsdr_carrier_create": (i32, [vp, i32, C.POINTER(f32), i32, sz, pvp]),
+    "hzsdr_carrier_push": (i32, [vp, vp, sz, sz, vp, sz, vp, sz]),
+    "hzsdr_carrier_set_params": (i32, [vp, C.POINTER(f32)]),
+    "hzsdr_carrier_get_state": (i32, [vp, C.POINTER(C.c_uint32), sz]),
+    "hzsdr_carrier_set_state": (i32, [vp, C.POINTER(C.c_uint32), sz, u64]),
+    "hzsdr_carrier_position": (i32, [vp, C.POINTER(u64)]),
+    "hzsdr_carrier_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_carrier_reset": (i32, [vp]),
+    "hzsdr_carrier_free": (i32, [vp]),
+}
+CARRIER_TONE, CARRIER_BPSK, CARRIER_QPSK = 0, 1, 2
+CARRIER_MAX_ROWS = 8192
+CARRIER_FORM_PER_ROW, CARRIER_FORM_MODE = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
-                             *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items()):
+                             *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
+                             *CARRIER_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

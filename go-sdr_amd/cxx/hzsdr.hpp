@@ -33,6 +33,7 @@
 #include "../../include/hzsdr_covar.h"
 #include "../../include/hzsdr_iir.h"
 #include "../../include/hzsdr_symsync.h"
+#include "../../include/hzsdr_carrier.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1339,6 +1340,61 @@ private:
     size_t rows_;
     bool complex_;
     hzsdr_symsync *s_ = nullptr;
+};
+
+// The carrier recovery bank (include/hzsdr_carrier.h): a second-order loop around a numerically controlled oscillator over
+// `rows` complex64 rows, with the detector `mode` (HZSDR_CARRIER_TONE, _BPSK, _QPSK) and the parameters alpha, beta, f0,
+// fmin, fmax shared by all rows, or rows of them when per_row.  Push runs `n` samples of every row (row r starts
+// r * in_stride samples into `in`; dense rows when in_stride is 0) and returns dense rows of n derotated samples; where
+// `track` is given it takes dense rows of n frequency estimates, in cycles per sample.  One output per input, no flush.
+class CarrierLoop {
+public:
+    CarrierLoop(const Context &x, int mode, const std::vector<float> &params, size_t rows = 1, bool per_row = false) : x_(x), rows_(rows) {
+        if (params.size() != 5 * (per_row ? rows : 1)) throw std::invalid_argument("CarrierLoop: params are 5, or rows * 5 values");
+        check(x_.raw(), hzsdr_carrier_create(x_.raw(), mode, params.data(), per_row ? 1 : 0, rows, &c_));
+    }
+    ~CarrierLoop() { if (c_) hzsdr_carrier_free(c_); }
+    CarrierLoop(const CarrierLoop &) = delete;
+    CarrierLoop &operator=(const CarrierLoop &) = delete;
+    std::vector<std::complex<float>> Push(const void *in, size_t n, size_t in_stride = 0, std::vector<float> *track = nullptr) {
+        std::vector<std::complex<float>> out(rows_ * n);
+        if (track) track->assign(rows_ * n, 0.0f);
+        check(x_.raw(), hzsdr_carrier_push(c_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n,
+                                           track && n ? track->data() : nullptr, n));
+        return out;
+    }
+    // the rows derotated where they lie (pitch: samples from one row's start to the next; n when 0)
+    void PushInPlace(std::complex<float> *rows, size_t n, size_t pitch = 0) {
+        check(x_.raw(), hzsdr_carrier_push(c_, n ? rows : nullptr, n, pitch ? pitch : n, n ? rows : nullptr, pitch ? pitch : n, nullptr, 0));
+    }
+    // the same form; theta, F and the position stay
+    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_carrier_set_params(c_, params.data())); }
+    // per row theta, F (hzsdr_carrier.h)
+    std::vector<uint32_t> State() const {
+        std::vector<uint32_t> z(rows_ * 2);
+        check(x_.raw(), hzsdr_carrier_get_state(c_, z.data(), z.size()));
+        return z;
+    }
+    void SetState(const std::vector<uint32_t> &z, uint64_t position = 0) { check(x_.raw(), hzsdr_carrier_set_state(c_, z.data(), z.size(), position)); }
+    uint64_t Position() const {
+        uint64_t p = 0;
+        check(x_.raw(), hzsdr_carrier_position(c_, &p));
+        return p;
+    }
+    // -> (rows per wave, samples per tile, HZSDR_CARRIER_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_carrier_plan(c_, &g, &t, &f));
+        return {g, t, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_carrier_reset(c_)); }
+    size_t Rows() const { return rows_; }
+
+private:
+    const Context &x_;
+    size_t rows_;
+    hzsdr_carrier *c_ = nullptr;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

@@ -1003,6 +1003,31 @@ def symbol_rows(src, bank, block=READER_BLOCK):
             yield bank.push(b)
 
 
+# ---- a Reader, or a tuner's blocks, through the carrier recovery bank (include/hzsdr_carrier.h) ----
+
+def carrier_rows(src, bank, block=READER_BLOCK):
+    """Push `src` through `bank` (a carrier.CarrierLoop on a HOST context) and yield each push's derotated rows.  `src`
+    is a Reader of complex64 samples, read to its end in blocks of `block` samples (a one-row bank: a PSK carrier, a
+    pilot), or any iterable of complex64 blocks the bank takes as they are -- the rows of tuner_rows(...), say; the
+    blocks go on into symbol_rows(...).  One output per input; the loop's state carries from block to block and there is
+    nothing to flush."""
+    if isinstance(src, Reader):
+        if src.sample_format() != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield bank.push(buf[:k])
+        return
+    for b in src:
+        if b.shape[-1]:
+            yield bank.push(b)
+
+
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
 
 def tuner_rows(r, bank, block=READER_BLOCK):
