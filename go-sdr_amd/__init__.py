@@ -465,6 +465,14 @@ class Context:
         from .carrier import CarrierLoop
         return CarrierLoop(self, mode, params, rows, per_row)
 
+    def agc(self, kind, params, rows=1, per_row=False):
+        """The AGC bank (include/hzsdr_agc.h, agc.Agc): a multiplicative gain loop over `rows` rows of `kind`
+        (AGC_REAL_F32: float32 rows; FMT_C64: complex64 rows), one output per input at the level `ref`, whatever the
+        input's level.  `params` is float32 (ref, attack, decay, floor, g0, gmin, gmax) shared by all rows, or (rows, 7)
+        with per_row; agc.agc_rates gives the two rates."""
+        from .agc import Agc
+        return Agc(self, kind, params, rows, per_row)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -910,6 +918,8 @@ from ._capi import SYMSYNC_FORM_COMPLEX, SYMSYNC_FORM_PER_ROW, SYMSYNC_MAX_ROWS,
 from .symsync import SymbolSync, loop_gains  # noqa: E402
 from ._capi import CARRIER_BPSK, CARRIER_FORM_MODE, CARRIER_FORM_PER_ROW, CARRIER_MAX_ROWS, CARRIER_QPSK, CARRIER_TONE  # noqa: E402
 from .carrier import CarrierLoop, carrier_gains  # noqa: E402
+from ._capi import AGC_FORM_COMPLEX, AGC_FORM_PER_ROW, AGC_MAX_ROWS, AGC_REAL_F32  # noqa: E402
+from .agc import Agc, agc_rates  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

@@ -338,10 +338,26 @@ CARRIER_TONE, CARRIER_BPSK, CARRIER_QPSK = 0, 1, 2
 CARRIER_MAX_ROWS = 8192
 CARRIER_FORM_PER_ROW, CARRIER_FORM_MODE = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_agc.h declares
+AGC_SIGNATURES = {
+    "hzsdr_agc_create": (i32, [vp, i32, C.POINTER(f32), i32, sz, pvp]),
+    "hzsdr_agc_push": (i32, [vp, vp, sz, sz, vp, sz, vp, sz]),
+    "hzsdr_agc_set_params": (i32, [vp, C.POINTER(f32)]),
+    "hzsdr_agc_get_state": (i32, [vp, C.POINTER(f32), sz]),
+    "hzsdr_agc_set_state": (i32, [vp, C.POINTER(f32), sz, u64]),
+    "hzsdr_agc_position": (i32, [vp, C.POINTER(u64)]),
+    "hzsdr_agc_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_agc_reset": (i32, [vp]),
+    "hzsdr_agc_free": (i32, [vp]),
+}
+AGC_REAL_F32 = 32  # (IIR_REAL_F32: one value names the real float32 rows all along the chain)
+AGC_MAX_ROWS = 8192
+AGC_FORM_PER_ROW, AGC_FORM_COMPLEX = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
-                             *CARRIER_SIGNATURES.items()):
+                             *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

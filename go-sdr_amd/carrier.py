@@ -13,9 +13,10 @@ integer updates (the header has the step).  The state carries from push to push,
 depend on how the stream is cut, on the memory space, on the number of rows, on any pitch or on the other rows.  A NaN
 stays in its sample.  One row runs at one lane's rate: the parallelism is across the rows.
 
-The detectors are amplitude-dependent: scale the rows to unit symbol amplitude, or the gains by the amplitude.
+The detectors are amplitude-dependent: put the AGC bank (include/hzsdr_agc.h, Context.agc) in front to bring the rows
+to unit symbol amplitude, or scale the gains by the amplitude.
 
-Not here: AGC, decision-directed detectors for 8PSK or QAM, a lock indicator.
+Not here: decision-directed detectors for 8PSK or QAM, a lock indicator.
 """
 import ctypes as C
 import math

@@ -34,6 +34,7 @@
 #include "../../include/hzsdr_iir.h"
 #include "../../include/hzsdr_symsync.h"
 #include "../../include/hzsdr_carrier.h"
+#include "../../include/hzsdr_agc.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1395,6 +1396,65 @@ private:
     const Context &x_;
     size_t rows_;
     hzsdr_carrier *c_ = nullptr;
+};
+
+// The AGC bank (include/hzsdr_agc.h): a multiplicative gain loop over `rows` rows of `kind` (HZSDR_AGC_REAL_F32: float
+// rows; HZSDR_FMT_C64: std::complex<float> rows), with the parameters ref, attack, decay, floor, g0, gmin, gmax shared by
+// all rows, or rows of them when per_row.  Push runs `n` samples of every row (row r starts r * in_stride samples into
+// `in`; dense rows when in_stride is 0) and returns dense rows of n levelled samples of the input's type (S is float or
+// std::complex<float>, as the kind says); where `track` is given it takes dense rows of n applied gains.  One output per
+// input, no flush.
+class Agc {
+public:
+    Agc(const Context &x, int kind, const std::vector<float> &params, size_t rows = 1, bool per_row = false) : x_(x), kind_(kind), rows_(rows) {
+        if (params.size() != 7 * (per_row ? rows : 1)) throw std::invalid_argument("Agc: params are 7, or rows * 7 values");
+        check(x_.raw(), hzsdr_agc_create(x_.raw(), kind, params.data(), per_row ? 1 : 0, rows, &a_));
+    }
+    ~Agc() { if (a_) hzsdr_agc_free(a_); }
+    Agc(const Agc &) = delete;
+    Agc &operator=(const Agc &) = delete;
+    template <typename S> std::vector<S> Push(const S *in, size_t n, size_t in_stride = 0, std::vector<float> *track = nullptr) {
+        if (sizeof(S) != (kind_ == HZSDR_FMT_C64 ? 8u : 4u)) throw std::invalid_argument("Agc: samples are not of the bank's kind");
+        std::vector<S> out(rows_ * n);
+        if (track) track->assign(rows_ * n, 0.0f);
+        check(x_.raw(), hzsdr_agc_push(a_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n,
+                                       track && n ? track->data() : nullptr, n));
+        return out;
+    }
+    // the rows levelled where they lie (pitch: samples from one row's start to the next; n when 0)
+    template <typename S> void PushInPlace(S *rows, size_t n, size_t pitch = 0) {
+        if (sizeof(S) != (kind_ == HZSDR_FMT_C64 ? 8u : 4u)) throw std::invalid_argument("Agc: samples are not of the bank's kind");
+        check(x_.raw(), hzsdr_agc_push(a_, n ? rows : nullptr, n, pitch ? pitch : n, n ? rows : nullptr, pitch ? pitch : n, nullptr, 0));
+    }
+    // the same form; the gains and the position stay
+    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_agc_set_params(a_, params.data())); }
+    // per row the gain (hzsdr_agc.h); ref / gain is the row's level
+    std::vector<float> State() const {
+        std::vector<float> g(rows_);
+        check(x_.raw(), hzsdr_agc_get_state(a_, g.data(), g.size()));
+        return g;
+    }
+    void SetState(const std::vector<float> &g, uint64_t position = 0) { check(x_.raw(), hzsdr_agc_set_state(a_, g.data(), g.size(), position)); }
+    uint64_t Position() const {
+        uint64_t p = 0;
+        check(x_.raw(), hzsdr_agc_position(a_, &p));
+        return p;
+    }
+    // -> (rows per wave, samples per tile, HZSDR_AGC_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_agc_plan(a_, &g, &t, &f));
+        return {g, t, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_agc_reset(a_)); }
+    size_t Rows() const { return rows_; }
+
+private:
+    const Context &x_;
+    int kind_;
+    size_t rows_;
+    hzsdr_agc *a_ = nullptr;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

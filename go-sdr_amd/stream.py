@@ -1028,6 +1028,31 @@ def carrier_rows(src, bank, block=READER_BLOCK):
             yield bank.push(b)
 
 
+# ---- a Reader, or a tuner's blocks, through the AGC bank (include/hzsdr_agc.h) ----
+
+def agc_rows(src, bank, block=READER_BLOCK):
+    """Push `src` through `bank` (an agc.Agc on a HOST context) and yield each push's levelled rows.  `src` is a Reader
+    of complex64 samples, read to its end in blocks of `block` samples (a one-row complex bank), or any iterable of
+    blocks the bank takes as they are -- the rows of tuner_rows(...) or demod_rows(...), say; the blocks go on into
+    carrier_rows(...) and symbol_rows(...).  One output per input; the gains carry from block to block and there is
+    nothing to flush."""
+    if isinstance(src, Reader):
+        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield bank.push(buf[:k])
+        return
+    for b in src:
+        if b.shape[-1]:
+            yield bank.push(b)
+
+
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
 
 def tuner_rows(r, bank, block=READER_BLOCK):

@@ -3,10 +3,10 @@
  * oscillator over one complex64 row, or over many rows at once, one derotated complex64 output per input.  It is the
  * next member of the family of hzsdr_tuner.h, hzsdr_iir.h and hzsdr_symsync.h and takes their complex64 rows as they
  * are: a tuner channel that is never exactly on frequency goes in, a row whose residual carrier offset and phase the
- * loop has removed comes out, and hzsdr_symsync.h makes coherent soft symbols of it.  What it leaves to others:
- * amplitude normalisation and AGC (the detectors are AMPLITUDE-DEPENDENT, as the Gardner detector is: scale the rows to
- * unit symbol amplitude, or the gains by the amplitude -- by its square for BPSK), decision-directed detectors for
- * 8PSK or QAM, a lock indicator.
+ * loop has removed comes out, and hzsdr_symsync.h makes coherent soft symbols of it.  The detectors are
+ * AMPLITUDE-DEPENDENT, as the Gardner detector is: the AGC bank of hzsdr_agc.h in front brings the rows to unit symbol
+ * amplitude (or scale the gains by the amplitude -- by its square for BPSK).  What it leaves to others:
+ * decision-directed detectors for 8PSK or QAM, a lock indicator.
  *
  * The entries live beside hzsdr.h and the other headers (same conventions, same status codes, same context).  The
  * reference has no carrier recovery: the definition below is the contract, restated under tests/.
