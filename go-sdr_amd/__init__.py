@@ -473,6 +473,14 @@ class Context:
         from .agc import Agc
         return Agc(self, kind, params, rows, per_row)
 
+    def frame_sync(self, kind, word_bits, words, maps, payload_bits, bits_per_symbol=1, mask=None, thr=0, diff=0, holdoff=None, rows=1):
+        """The frame sync bank (include/hzsdr_framesync.h, framesync.FrameSync): hard decisions, a search for a sync word
+        of `word_bits` bits under the hypotheses (`words`, `maps`; framesync.sync_hypotheses builds them) and the
+        `payload_bits` bits behind every hit, over `rows` rows of soft symbols of `kind` (SYMSYNC_REAL_F32, or FMT_C64
+        with 1 or 2 bits per symbol): the symbol-timing bank's (symbols, counts) as they are."""
+        from .framesync import FrameSync
+        return FrameSync(self, kind, word_bits, words, maps, payload_bits, bits_per_symbol, mask, thr, diff, holdoff, rows)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -920,6 +928,9 @@ from ._capi import CARRIER_BPSK, CARRIER_FORM_MODE, CARRIER_FORM_PER_ROW, CARRIE
 from .carrier import CarrierLoop, carrier_gains  # noqa: E402
 from ._capi import AGC_FORM_COMPLEX, AGC_FORM_PER_ROW, AGC_MAX_ROWS, AGC_REAL_F32  # noqa: E402
 from .agc import Agc, agc_rates  # noqa: E402
+from ._capi import (FRAMESYNC_FORM_COMPLEX, FRAMESYNC_FORM_DIBIT, FRAMESYNC_FORM_DIFF, FRAMESYNC_MAX_HYPOTHESES,  # noqa: E402
+                    FRAMESYNC_MAX_PAYLOAD, FRAMESYNC_MAX_ROWS, FRAMESYNC_MAX_WORD)
+from .framesync import FrameSync, pack_bits, sync_hypotheses, unpack_bits  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

@@ -354,10 +354,24 @@ AGC_REAL_F32 = 32  # (IIR_REAL_F32: one value names the real float32 rows all al
 AGC_MAX_ROWS = 8192
 AGC_FORM_PER_ROW, AGC_FORM_COMPLEX = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_framesync.h declares
+FRAMESYNC_SIGNATURES = {
+    "hzsdr_framesync_create": (i32, [vp, i32, C.c_uint, C.c_uint, u64, C.c_uint, C.c_uint, C.POINTER(u64), C.POINTER(C.c_uint), C.c_uint, i32, u64, sz, pvp]),
+    "hzsdr_framesync_push": (i32, [vp, vp, sz, sz, vp, vp, sz, sz, vp, vp, vp, psz]),
+    "hzsdr_framesync_get_state": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), sz]),
+    "hzsdr_framesync_set_state": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), sz]),
+    "hzsdr_framesync_positions": (i32, [vp, C.POINTER(u64), sz]),
+    "hzsdr_framesync_plan": (i32, [vp, psz, psz, psz, C.POINTER(i32)]),
+    "hzsdr_framesync_reset": (i32, [vp]),
+    "hzsdr_framesync_free": (i32, [vp]),
+}
+FRAMESYNC_MAX_ROWS, FRAMESYNC_MAX_WORD, FRAMESYNC_MAX_PAYLOAD, FRAMESYNC_MAX_HYPOTHESES = 8192, 64, 8192, 4
+FRAMESYNC_FORM_COMPLEX, FRAMESYNC_FORM_DIBIT, FRAMESYNC_FORM_DIFF = 1, 2, 4
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
-                             *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items()):
+                             *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -35,6 +35,7 @@
 #include "../../include/hzsdr_symsync.h"
 #include "../../include/hzsdr_carrier.h"
 #include "../../include/hzsdr_agc.h"
+#include "../../include/hzsdr_framesync.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1455,6 +1456,94 @@ private:
     int kind_;
     size_t rows_;
     hzsdr_agc *a_ = nullptr;
+};
+
+// The frame sync bank (include/hzsdr_framesync.h): hard decisions, a search for a sync word of `word_bits` bits under the
+// hypotheses (words[h], maps[h]) and the `payload_bits` bits behind every accepted hit, over `rows` rows of soft symbols
+// of `kind` (HZSDR_SYMSYNC_REAL_F32: float rows; HZSDR_FMT_C64: std::complex<float> rows, 1 or 2 bits per symbol).  Push
+// runs min(in_counts[r], n) symbols of every row (row r starts r * in_stride symbols into `in`; dense rows when in_stride
+// is 0; every row has n when in_counts is null) and returns, per row, the frames the push completed, up to `cap` of them;
+// a row that accepted more than `cap` throws, since a loss must not pass in silence.  Nothing to flush.
+class FrameSync {
+public:
+    struct Frame {
+        std::vector<uint8_t> bytes;  // payload bit k in byte k / 8, bit 7 - k % 8
+        uint64_t position;           // the payload's first symbol
+        unsigned distance, hypothesis;
+    };
+    struct Config {
+        unsigned bits_per_symbol = 1, word_bits = 0;
+        uint64_t mask = 0;  // 0: all word_bits bits
+        unsigned thr = 0;
+        std::vector<uint64_t> words;
+        std::vector<unsigned> maps;
+        unsigned payload_bits = 0;
+        int diff = 0;
+        uint64_t holdoff = 0;  // 0: one frame's symbols
+    };
+    FrameSync(const Context &x, int kind, const Config &c, size_t rows = 1) : x_(x), rows_(rows), c_(c) {
+        if (c.words.empty() || c.words.size() != c.maps.size()) throw std::invalid_argument("FrameSync: a map for every word, at least one");
+        const uint64_t mask = c.mask ? c.mask : (c.word_bits >= 64 ? ~0ull : (1ull << c.word_bits) - 1);
+        const uint64_t holdoff = c.holdoff ? c.holdoff : (c.word_bits + c.payload_bits) / (c.bits_per_symbol ? c.bits_per_symbol : 1);
+        check(x_.raw(), hzsdr_framesync_create(x_.raw(), kind, c.bits_per_symbol, c.word_bits, mask, c.thr, (unsigned)c.words.size(), c.words.data(),
+                                               c.maps.data(), c.payload_bits, c.diff, holdoff, rows, &f_));
+    }
+    ~FrameSync() { if (f_) hzsdr_framesync_free(f_); }
+    FrameSync(const FrameSync &) = delete;
+    FrameSync &operator=(const FrameSync &) = delete;
+    std::vector<std::vector<Frame>> Push(const void *in, size_t n, size_t in_stride = 0, const uint32_t *in_counts = nullptr, size_t cap = 4) {
+        const size_t fb = FrameBytes();
+        std::vector<uint8_t> out(rows_ * cap * fb);
+        std::vector<uint64_t> pos(rows_ * cap);
+        std::vector<uint32_t> info(rows_ * cap), counts(rows_, 0);
+        size_t most = 0;
+        check(x_.raw(), hzsdr_framesync_push(f_, n ? in : nullptr, n, in_stride ? in_stride : n, in_counts, out.data(), cap, cap * fb, pos.data(),
+                                             info.data(), counts.data(), &most));
+        if (most > cap) throw std::length_error("FrameSync: a row accepted more frames than cap");
+        std::vector<std::vector<Frame>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++)
+            for (size_t f = 0; f < counts[r]; f++) {
+                const uint8_t *p = out.data() + (r * cap + f) * fb;
+                rows[r].push_back({std::vector<uint8_t>(p, p + fb), pos[r * cap + f], info[r * cap + f] & 0xffu, info[r * cap + f] >> 8});
+            }
+        return rows;
+    }
+    struct StateArrays {
+        std::vector<uint64_t> positions, holds;
+        std::vector<uint8_t> history, last;  // history: rows * ceil(K / 8) bytes, oldest bit first, most significant bit first
+    };
+    StateArrays State() const {
+        StateArrays z{std::vector<uint64_t>(rows_), std::vector<uint64_t>(rows_), std::vector<uint8_t>(rows_ * HistoryBytes()), std::vector<uint8_t>(rows_)};
+        check(x_.raw(), hzsdr_framesync_get_state(f_, z.positions.data(), z.holds.data(), z.history.data(), z.last.data(), rows_));
+        return z;
+    }
+    void SetState(const StateArrays &z) {
+        if (z.positions.size() != rows_ || z.holds.size() != rows_ || z.history.size() != rows_ * HistoryBytes() || z.last.size() != rows_)
+            throw std::invalid_argument("FrameSync: the state has an entry per row");
+        check(x_.raw(), hzsdr_framesync_set_state(f_, z.positions.data(), z.holds.data(), z.history.data(), z.last.data(), rows_));
+    }
+    std::vector<uint64_t> Positions() const {
+        std::vector<uint64_t> p(rows_);
+        check(x_.raw(), hzsdr_framesync_positions(f_, p.data(), p.size()));
+        return p;
+    }
+    // -> (rows per wave, bits per tile, words of the history ring, HZSDR_FRAMESYNC_FORM_*)
+    std::tuple<size_t, size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0, r = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_framesync_plan(f_, &g, &t, &r, &f));
+        return {g, t, r, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_framesync_reset(f_)); }
+    size_t Rows() const { return rows_; }
+    size_t FrameBytes() const { return (c_.payload_bits + 7) / 8; }
+    size_t HistoryBytes() const { return (c_.word_bits + c_.payload_bits - 1 + 7) / 8; }
+
+private:
+    const Context &x_;
+    size_t rows_;
+    Config c_;
+    hzsdr_framesync *f_ = nullptr;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

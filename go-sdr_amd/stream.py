@@ -1053,6 +1053,38 @@ def agc_rows(src, bank, block=READER_BLOCK):
             yield bank.push(b)
 
 
+# ---- a Reader, or a symbol-timing bank's pushes, through the frame sync bank (include/hzsdr_framesync.h) ----
+
+def frame_rows(src, bank, cap=4, block=READER_BLOCK):
+    """Push `src` through `bank` (a framesync.FrameSync on a HOST context) and yield, per push, bank.ragged(...) of its
+    results: a list of `rows` triples (frames (k, FB) uint8, positions (k,), info (k,)).  `src` is a Reader of complex64
+    samples at ONE sample per symbol, read to its end in blocks of `block` symbols (a one-row complex bank), or any
+    iterable of (symbols, counts) pairs -- what symbol_rows(...) yields -- or of blocks of symbols alone.  `cap` frames
+    per row and push are kept; a row that accepted more raises ErrShortBuffer, since nothing here may be lost in silence.  The
+    state carries from block to block; a frame still open at the end is not emitted."""
+    def push(symbols, counts=None):
+        frames, positions, info, got = bank.push(symbols, counts, cap)
+        if int(got.max()) > cap:
+            raise ErrShortBuffer("sdr: a row accepted more frames in one push than frame_rows keeps")
+        return bank.ragged(frames, positions, info, got)
+    if isinstance(src, Reader):
+        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield push(buf[:k])
+        return
+    for b in src:
+        symbols, counts = b if isinstance(b, tuple) else (b, None)
+        if symbols.shape[-1]:
+            yield push(symbols, counts)
+
+
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
 
 def tuner_rows(r, bank, block=READER_BLOCK):

@@ -15,8 +15,9 @@ counts[r] symbols, at most max_symbols(n) of them; the columns behind a row's co
 infinity may silence or garble its own row until reset() or set_state().  The latency is two samples and there is
 nothing to flush.  One row runs at one lane's rate: the parallelism is across the rows.
 
-Not here: the matched filter (the resampler's taps or the demodulator's post-filter in front of this stage), the
-carrier, the decisions.
+Not here: the matched filter (the resampler's taps or the demodulator's post-filter in front of this stage) and the
+carrier.  The decisions, the sync-word search and the frames are the frame sync bank's (include/hzsdr_framesync.h,
+Context.frame_sync): it takes (symbols, counts) as push returns them.
 """
 import ctypes as C
 

@@ -3,7 +3,9 @@
  * out of many rows at once, real or complex.  It is the next member of the family of hzsdr_channelizer.h,
  * hzsdr_resampler.h, hzsdr_demod.h, hzsdr_tuner.h and hzsdr_iir.h and takes their rows as they are: the demodulator's or
  * the IIR bank's real float32 block (an FM-detected GMSK or FSK channel: AIS, PMR, POCSAG) and any complex64 block (a
- * BPSK or QPSK carrier).  What it leaves to others: the matched filter in front of it, the carrier, the decisions.
+ * BPSK or QPSK carrier).  What it leaves to others: the matched filter in front of it, the carrier (hzsdr_carrier.h),
+ * and the decisions, the sync-word search and the frames: the frame sync bank (hzsdr_framesync.h) takes this bank's
+ * symbols and counts as they are, on the device.
  *
  * The entries live beside hzsdr.h and the other headers (same conventions, same status codes, same context).  The
  * reference has no timing recovery: the definition below is the contract, restated under tests/.
