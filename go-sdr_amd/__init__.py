@@ -481,6 +481,14 @@ class Context:
         from .framesync import FrameSync
         return FrameSync(self, kind, word_bits, words, maps, payload_bits, bits_per_symbol, mask, thr, diff, holdoff, rows)
 
+    def viterbi(self, kind, K, gens, data_bits, inv=0, pattern=None, termination=0, scale=1.0, crc=None, rows=1):
+        """The Viterbi decoder bank (include/hzsdr_viterbi.h, viterbi.ViterbiDecoder): frames of a rate 1 / len(gens)
+        convolutional code of constraint length `K`, packed hard bits (VITERBI_BITS: the frame sync bank's frames as
+        they are) or soft float32 values (VITERBI_SOFT_F32), to `data_bits` data bits, a path metric and a CRC verdict
+        per frame, over `rows` rows of frames."""
+        from .viterbi import ViterbiDecoder
+        return ViterbiDecoder(self, kind, K, gens, data_bits, inv, pattern, termination, scale, crc, rows)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -931,6 +939,9 @@ from .agc import Agc, agc_rates  # noqa: E402
 from ._capi import (FRAMESYNC_FORM_COMPLEX, FRAMESYNC_FORM_DIBIT, FRAMESYNC_FORM_DIFF, FRAMESYNC_MAX_HYPOTHESES,  # noqa: E402
                     FRAMESYNC_MAX_PAYLOAD, FRAMESYNC_MAX_ROWS, FRAMESYNC_MAX_WORD)
 from .framesync import FrameSync, pack_bits, sync_hypotheses, unpack_bits  # noqa: E402
+from ._capi import (VITERBI_BITS, VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH, VITERBI_MAX_BITS, VITERBI_MAX_FRAMES, VITERBI_MAX_K,  # noqa: E402
+                    VITERBI_MAX_PATTERN, VITERBI_MAX_RATE, VITERBI_MAX_ROWS, VITERBI_MIN_K, VITERBI_SOFT_F32, VITERBI_TAIL, VITERBI_TRUNCATED)
+from .viterbi import CCSDS_K7, ViterbiDecoder, conv_encode, crc_register, puncture_pattern  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

@@ -368,10 +368,24 @@ FRAMESYNC_SIGNATURES = {
 FRAMESYNC_MAX_ROWS, FRAMESYNC_MAX_WORD, FRAMESYNC_MAX_PAYLOAD, FRAMESYNC_MAX_HYPOTHESES = 8192, 64, 8192, 4
 FRAMESYNC_FORM_COMPLEX, FRAMESYNC_FORM_DIBIT, FRAMESYNC_FORM_DIFF = 1, 2, 4
 
+# name -> (restype, argtypes); every symbol include/hzsdr_viterbi.h declares
+VITERBI_SIGNATURES = {
+    "hzsdr_viterbi_create": (i32, [vp, i32, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.c_uint, u64, C.c_uint, i32, sz, f32, C.c_uint, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, sz, pvp]),
+    "hzsdr_viterbi_decode": (i32, [vp, vp, sz, vp, sz, vp, sz, vp]),
+    "hzsdr_viterbi_sizes": (i32, [vp, psz, psz, psz, psz]),
+    "hzsdr_viterbi_plan": (i32, [vp, psz, psz, psz, C.POINTER(i32)]),
+    "hzsdr_viterbi_free": (i32, [vp]),
+}
+VITERBI_MAX_ROWS, VITERBI_MIN_K, VITERBI_MAX_K, VITERBI_MAX_RATE, VITERBI_MAX_PATTERN, VITERBI_MAX_BITS, VITERBI_MAX_FRAMES = 8192, 3, 9, 4, 64, 8192, 1 << 22
+VITERBI_BITS, VITERBI_SOFT_F32 = 1, 32
+VITERBI_TAIL, VITERBI_TRUNCATED = 0, 1
+VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
-                             *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items()):
+                             *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

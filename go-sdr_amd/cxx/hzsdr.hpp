@@ -36,6 +36,7 @@
 #include "../../include/hzsdr_carrier.h"
 #include "../../include/hzsdr_agc.h"
 #include "../../include/hzsdr_framesync.h"
+#include "../../include/hzsdr_viterbi.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1544,6 +1545,93 @@ private:
     size_t rows_;
     Config c_;
     hzsdr_framesync *f_ = nullptr;
+};
+
+// The Viterbi decoder bank (include/hzsdr_viterbi.h): frames of a rate 1 / gens.size() convolutional code -- packed hard
+// bits (HZSDR_VITERBI_BITS: the frame sync bank's frames as they are) or soft floats (HZSDR_VITERBI_SOFT_F32) -- to
+// data_bits data bits, a path metric and a CRC verdict per frame, over `rows` rows of `cap` frame slots.  Decode runs
+// min(in_counts[r], cap) frames of every row (row r starts r * in_stride bytes or floats into `in`; dense rows when
+// in_stride is 0; every row has cap frames when in_counts is null).  The bank keeps no state.
+class Viterbi {
+public:
+    struct Frame {
+        std::vector<uint8_t> bytes;  // data bit k in byte k / 8, bit 7 - k % 8
+        uint32_t metric;             // hard input: the channel bit errors corrected
+        bool crc_ok;
+    };
+    struct Config {
+        unsigned K = 7;
+        std::vector<unsigned> gens = {0171, 0133};
+        unsigned inv = 0;
+        uint64_t pattern = 0;  // pattern_bits 0: no puncturing
+        unsigned pattern_bits = 0;
+        int termination = HZSDR_VITERBI_TAIL;
+        size_t data_bits = 0;
+        float scale = 1.0f;
+        unsigned crc_bits = 0;
+        uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;
+    };
+    Viterbi(const Context &x, int kind, const Config &c, size_t rows = 1) : x_(x), kind_(kind), rows_(rows) {
+        if (c.gens.empty()) throw std::invalid_argument("Viterbi: at least two generators");
+        const unsigned n = (unsigned)c.gens.size();
+        const uint64_t pattern = c.pattern_bits ? c.pattern : (1ull << n) - 1;
+        check(x_.raw(), hzsdr_viterbi_create(x_.raw(), kind, c.K, n, c.gens.data(), c.inv, pattern, c.pattern_bits ? c.pattern_bits : n, c.termination,
+                                             c.data_bits, c.scale, c.crc_bits, c.crc_poly, c.crc_init, c.crc_xorout, rows, &v_));
+        check(x_.raw(), hzsdr_viterbi_sizes(v_, &n_, &fb_, &t_, &db_));
+    }
+    ~Viterbi() { if (v_) hzsdr_viterbi_free(v_); }
+    Viterbi(const Viterbi &) = delete;
+    Viterbi &operator=(const Viterbi &) = delete;
+    std::vector<std::vector<Frame>> Decode(const void *in, size_t cap, size_t in_stride = 0, const uint32_t *in_counts = nullptr) {
+        std::vector<uint8_t> out(rows_ * cap * db_);
+        std::vector<uint32_t> info(rows_ * cap);
+        const size_t width = cap * (kind_ == HZSDR_VITERBI_BITS ? fb_ : n_);
+        check(x_.raw(), hzsdr_viterbi_decode(v_, in, in_stride ? in_stride : width, in_counts, cap, out.data(), cap * db_, info.data()));
+        std::vector<std::vector<Frame>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            const size_t k = in_counts && in_counts[r] < cap ? in_counts[r] : cap;
+            for (size_t f = 0; f < k; f++) {
+                const uint8_t *p = out.data() + (r * cap + f) * db_;
+                rows[r].push_back({std::vector<uint8_t>(p, p + db_), info[r * cap + f] & 0x7fffffffu, (info[r * cap + f] >> 31) != 0});
+            }
+        }
+        return rows;
+    }
+    // what FrameSync::Push returned, frame for frame (HZSDR_VITERBI_BITS; a frame's bytes are the bank's FB)
+    std::vector<std::vector<Frame>> Decode(const std::vector<std::vector<FrameSync::Frame>> &frames) {
+        if (kind_ != HZSDR_VITERBI_BITS || frames.size() != rows_) throw std::invalid_argument("Viterbi: hard-bit frames, a list per row");
+        size_t cap = 1;
+        for (const auto &row : frames) cap = row.size() > cap ? row.size() : cap;
+        std::vector<uint8_t> in(rows_ * cap * fb_, 0);
+        std::vector<uint32_t> counts(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            counts[r] = (uint32_t)frames[r].size();
+            for (size_t f = 0; f < frames[r].size(); f++) {
+                if (frames[r][f].bytes.size() != fb_) throw std::invalid_argument("Viterbi: a frame of another size");
+                std::copy(frames[r][f].bytes.begin(), frames[r][f].bytes.end(), in.begin() + (r * cap + f) * fb_);
+            }
+        }
+        return Decode(in.data(), cap, 0, counts.data());
+    }
+    // -> (frames per wave, states per lane, bytes of a frame's decisions, HZSDR_VITERBI_FORM_*)
+    std::tuple<size_t, size_t, size_t, int> Plan() const {
+        size_t g = 0, s = 0, d = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_viterbi_plan(v_, &g, &s, &d, &f));
+        return {g, s, d, f};
+    }
+    size_t Rows() const { return rows_; }
+    size_t ReceivedBits() const { return n_; }
+    size_t FrameBytes() const { return fb_; }
+    size_t Steps() const { return t_; }
+    size_t DataBytes() const { return db_; }
+
+private:
+    const Context &x_;
+    int kind_;
+    size_t rows_;
+    size_t n_ = 0, fb_ = 0, t_ = 0, db_ = 0;
+    hzsdr_viterbi *v_ = nullptr;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

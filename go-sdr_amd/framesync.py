@@ -14,7 +14,8 @@ its last bit.  Positions, the hold-off and the last W + P - 1 bits carry from pu
 positions, info, counts and state do not depend on how the stream is cut, on the memory space, on the number of rows, on
 either pitch or on the other rows.  counts[r] above `cap` says that row r lost frames in this push.
 
-Not here: descrambling, bit unstuffing, CRCs; soft outputs; sync words above 64 bits.
+Not here: decoding a convolutionally coded payload and its CRC (include/hzsdr_viterbi.h, Context.viterbi: it takes
+frames and counts as push returns them); descrambling, bit unstuffing; soft outputs; sync words above 64 bits.
 """
 import ctypes as C
 

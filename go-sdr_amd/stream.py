@@ -1085,6 +1085,43 @@ def frame_rows(src, bank, cap=4, block=READER_BLOCK):
             yield push(symbols, counts)
 
 
+# ---- frame_rows with the Viterbi decoder bank behind the frame sync bank (include/hzsdr_viterbi.h) ----
+
+def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK):
+    """Push `src` through `bank` (a framesync.FrameSync) as frame_rows does and decode every push's frames with
+    `decoder` (a viterbi.ViterbiDecoder of VITERBI_BITS input over the same rows, whose received positions N are the
+    bank's payload bits).  The frame block and its counts go from the one bank to the other as they are, in the
+    context's memory space, with nothing read in between.  Yields, per push, a list of `rows` tuples (data (k, DB) uint8,
+    positions (k,), sync info (k,), metric (k,), crc_ok (k,)).  As in frame_rows, a row that accepted more than `cap`
+    frames in one push raises ErrShortBuffer."""
+    if decoder.rows != bank.rows or decoder.N != bank.P:
+        raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
+
+    def push(symbols, counts=None):
+        frames, positions, info, got = bank.push(symbols, counts, cap)
+        data, verdict = decoder.decode(frames, got, cap)
+        if int(got.max()) > cap:
+            raise ErrShortBuffer("sdr: a row accepted more frames in one push than decoded_frames keeps")
+        found = bank.ragged(frames, positions, info, got)
+        return [(d, p, i, m, ok) for (_, p, i), (d, m, ok) in zip(found, decoder.ragged(data, verdict, got))]
+    if isinstance(src, Reader):
+        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield push(buf[:k])
+        return
+    for b in src:
+        symbols, counts = b if isinstance(b, tuple) else (b, None)
+        if symbols.shape[-1]:
+            yield push(symbols, counts)
+
+
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
 
 def tuner_rows(r, bank, block=READER_BLOCK):

@@ -1,0 +1,200 @@
+"""The Viterbi decoder bank (include/hzsdr_viterbi.h): convolutionally coded frames -- the frame sync bank's packed
+payload bits, or soft float32 values -- to data bits, a path metric and an optional CRC verdict per frame.
+
+    K, gens, inv = hz.CCSDS_K7
+    vd = ctx.viterbi(hz.VITERBI_BITS, K, gens, data_bits=78, inv=inv, crc=(16, 0x1021, 0xFFFF, 0), rows=100)
+    frames, positions, sync, counts = fs.push(symbols, symbol_counts, cap=4)   # the frame sync bank, on the device
+    data, info = vd.decode(frames, counts)        # data (rows, cap, DB) uint8; info = metric | crc_ok << 31
+
+The code is rate 1/n (n = 2, 3, 4) with constraint length K = 3 ... 9, generators whose most significant bit multiplies
+the newest input bit, an inversion mask and a puncture pattern; TAIL frames end in K - 1 zero bits, TRUNCATED ones do
+not.  Soft values are quantised to -127 ... 127 by q = rint(clamp(x * scale)), a NaN is an erasure; hard bits are +-1,
+so that the metric of a hard frame is the number of channel bit errors corrected.  Row r decodes min(counts[r], cap)
+frames; the other slots of the destinations stay as they are.  Frames are independent and the bank keeps no state.
+
+Not here: tail-biting, one continuous stream across frames, soft outputs, descrambling, bit unstuffing.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import ErrInvalidArgument, _is_torch, lib
+from ._capi import (VITERBI_BITS, VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH, VITERBI_MAX_BITS, VITERBI_MAX_FRAMES, VITERBI_MAX_K, VITERBI_MAX_PATTERN,
+                    VITERBI_MAX_RATE, VITERBI_MAX_ROWS, VITERBI_MIN_K, VITERBI_SOFT_F32, VITERBI_TAIL, VITERBI_TRUNCATED)
+
+CCSDS_K7 = (7, (0o171, 0o133), 0b10)  # (K, generators, inv): the second output inverted
+
+_PATTERNS = {"1/2": "11", "2/3": "1101", "3/4": "110110", "5/6": "1101100110", "7/8": "11010101100110"}
+
+
+def puncture_pattern(rate):
+    """(pattern, pattern_bits) of the usual punctured rates of the K = 7 rate 1/2 code (DVB-S): "1/2", "2/3", "3/4",
+    "5/6", "7/8"; the pattern's first bit is its most significant"""
+    try:
+        s = _PATTERNS[rate]
+    except KeyError:
+        raise ValueError('puncture_pattern: the rate is "1/2", "2/3", "3/4", "5/6" or "7/8"') from None
+    return int(s, 2), len(s)
+
+
+def _pattern(pattern, n):
+    if pattern is None:
+        return (1 << n) - 1, n
+    if isinstance(pattern, str):
+        return puncture_pattern(pattern)
+    p, bits = pattern
+    return int(p), int(bits)
+
+
+def conv_encode(bits, K, gens, inv=0, pattern=None, termination=VITERBI_TAIL):
+    """The encoder of the definition, in numpy: data bits (D,) of 0 / 1 -> the N transmitted code bits (uint8).
+    `pattern` is None (no puncturing), a rate name of puncture_pattern, or (pattern, pattern_bits)."""
+    u = np.asarray(bits, np.uint8).reshape(-1) & 1
+    n = len(gens)
+    pat, lp = _pattern(pattern, n)
+    if termination == VITERBI_TAIL:
+        u = np.concatenate([u, np.zeros(K - 1, np.uint8)])
+    out, state = [], 0
+    for t, b in enumerate(u):
+        reg = (int(b) << (K - 1)) | state
+        for j, g in enumerate(gens):
+            if (pat >> (lp - 1 - (t * n + j) % lp)) & 1:
+                out.append((bin(reg & int(g)).count("1") & 1) ^ ((inv >> j) & 1))
+        state = reg >> 1
+    return np.array(out, np.uint8)
+
+
+def crc_register(bits, C, poly, init=0, xorout=0):
+    """The CRC register of the definition over `bits` in stream order: no reflection, the first bit first"""
+    reg, mask = int(init), (1 << C) - 1
+    for b in np.asarray(bits, np.uint8).reshape(-1):
+        top = ((reg >> (C - 1)) & 1) ^ (int(b) & 1)
+        reg = (reg << 1) & mask
+        if top:
+            reg ^= int(poly)
+    return reg ^ int(xorout)
+
+
+class ViterbiDecoder:
+    """hzsdr_viterbi: decode(frames, counts) -> (data, info).  `kind` is VITERBI_BITS (uint8 frames of FB = ceil(N / 8)
+    bytes, most significant bit first: FrameSync.push's frames) or VITERBI_SOFT_F32 (float32 frames of N values, positive
+    meaning 1).  frames is (rows, cap, FB or N) -- (cap, ...) will do for one row -- with contiguous rows and any row
+    pitch.  `crc` is None or (bits, poly, init, xorout).  numpy in a HOST context; torch tensors on the context's device,
+    written on the context's stream, in a DEVICE context (info and counts are int32 there: the same bits)."""
+
+    def __init__(self, ctx, kind, K, gens, data_bits, inv=0, pattern=None, termination=VITERBI_TAIL, scale=1.0, crc=None, rows=1):
+        self.ctx, self.kind, self.rows = ctx, int(kind), int(rows)
+        if self.rows <= 0:
+            raise ErrInvalidArgument("viterbi: rows is at least 1")
+        gens = [int(g) for g in gens]
+        self.K, self.gens, self.n, self.inv, self.D = int(K), gens, len(gens), int(inv), int(data_bits)
+        self.pattern, self.pattern_bits = _pattern(pattern, self.n)
+        self.termination, self.scale = int(termination), float(scale)
+        self.crc = (0, 0, 0, 0) if crc is None else tuple(int(v) for v in crc)
+        values = gens + [self.K, self.inv, self.D, self.pattern, self.pattern_bits, *self.crc]
+        if not 1 <= self.n <= 8 or len(self.crc) != 4 or min(values) < 0 or max(gens + [self.K, self.inv, self.pattern_bits, *self.crc]) >= 1 << 32 or \
+                self.pattern >= 1 << 64 or self.D >= 1 << 62:
+            raise ErrInvalidArgument("viterbi: generators, sizes, the pattern and the CRC are unsigned values of their widths")
+        self._h = C.c_void_p()
+        g = (C.c_uint * self.n)(*gens)
+        ctx._ck(lib.hzsdr_viterbi_create(ctx._h, self.kind, self.K, self.n, g, self.inv, self.pattern, self.pattern_bits, self.termination, self.D,
+                                         self.scale, *self.crc, self.rows, C.byref(self._h)))
+        self.N, self.frame_bytes, self.T, self.data_bytes = self.sizes()
+
+    def sizes(self):
+        """(N received positions, FB = ceil(N / 8), T trellis steps, DB = ceil(D / 8)) of a frame"""
+        v = [C.c_size_t(0) for _ in range(4)]
+        self.ctx._ck(lib.hzsdr_viterbi_sizes(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def plan(self):
+        """(frames per wave, states per lane, bytes of a frame's decisions, VITERBI_FORM_LDS or VITERBI_FORM_SCRATCH)"""
+        g, s, d, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
+        self.ctx._ck(lib.hzsdr_viterbi_plan(self._h, C.byref(g), C.byref(s), C.byref(d), C.byref(f)))
+        return g.value, s.value, d.value, f.value
+
+    @staticmethod
+    def _block(a, shape, dtype, what):
+        """(pointer, row pitch in elements) of a (rows, cap, width) block with contiguous rows"""
+        if _is_torch(a):
+            import torch
+            ok = a.dtype == {np.uint8: torch.uint8, np.float32: torch.float32}[dtype]
+            strides, ptr = tuple(a.stride()), a.data_ptr()
+        else:
+            ok, strides, ptr = a.dtype == dtype, tuple(s // a.itemsize for s in a.strides), a.ctypes.data
+        R, cap, w = shape
+        if not ok or tuple(a.shape) != shape or (w > 1 and strides[2] != 1) or (cap > 1 and strides[1] != w) or (R > 1 and strides[0] < cap * w):
+            raise ValueError(f"viterbi: {what} is {np.dtype(dtype).name} {shape} with contiguous rows")
+        return ptr, int(strides[0]) if R > 1 else cap * w
+
+    @staticmethod
+    def _dense(a, shape, what):
+        if _is_torch(a):
+            import torch
+            ok, ptr = a.dtype == torch.int32 and a.is_contiguous(), a.data_ptr()
+        else:
+            ok, ptr = a.dtype == np.uint32 and a.flags.c_contiguous, a.ctypes.data
+        if not ok or tuple(a.shape) != tuple(shape):
+            raise ValueError(f"viterbi: {what} is a contiguous uint32 {tuple(shape)} (torch: int32)")
+        return ptr
+
+    def _new(self, shape, dtype, like):
+        if _is_torch(like):
+            import torch
+            return torch.zeros(shape, dtype={np.uint8: torch.uint8, np.uint32: torch.int32}[dtype], device=like.device)
+        return np.zeros(shape, dtype)
+
+    def decode(self, frames, counts=None, cap=None, out=None):
+        """Decode min(counts[r], cap) frames of every row -> (data uint8 (rows, cap, DB), info (rows, cap) =
+        metric | crc_ok << 31).  `counts`, when given, is what FrameSync.push returned beside the frames (values above
+        cap are clamped); without it every row decodes cap frames.  `cap` defaults to the frames' second-last extent.
+        Slots from a row's count up hold what the destination held (a new one is zero).  `out`, when given, is such a
+        pair (data, info); data may be a view with a row pitch above cap * DB."""
+        R = self.rows
+        width = self.frame_bytes if self.kind == VITERBI_BITS else self.N
+        dtype = np.uint8 if self.kind == VITERBI_BITS else np.float32
+        if frames.ndim == 2 and R == 1:
+            frames = frames[None]
+        if frames.ndim != 3:
+            raise ValueError("viterbi: frames are (rows, cap, FB or N)")
+        cap = int(frames.shape[1]) if cap is None else int(cap)
+        fptr, fpitch = self._block(frames, (R, cap, width), dtype, "frames")
+        if out is None:
+            out = (self._new((R, cap, self.data_bytes), np.uint8, frames), self._new((R, cap), np.uint32, frames))
+        data, info = out
+        dptr, dpitch = self._block(data, (R, cap, self.data_bytes), np.uint8, "data")
+        iptr = self._dense(info, (R, cap), "info")
+        cptr = None if counts is None else self._dense(counts, (R,), "the frames' counts")
+        self.ctx._ck(lib.hzsdr_viterbi_decode(self._h, fptr, fpitch, cptr, cap, dptr, dpitch, iptr))
+        return data, info
+
+    def ragged(self, data, info, counts=None):
+        """A call's results -> a list of `rows` host triples (data (k, DB), metric (k,) uint32, crc_ok (k,) bool),
+        k = min(counts[r], cap) (this waits for the device in a DEVICE context)."""
+        if _is_torch(data):
+            data, info = data.cpu().numpy(), info.cpu().numpy()
+            counts = None if counts is None else counts.cpu().numpy()
+        cap = data.shape[1]
+        info = np.asarray(info).view(np.uint32)
+        got = np.full(self.rows, cap, np.uint32) if counts is None else np.asarray(counts).reshape(-1).view(np.uint32)
+        out = []
+        for r, c in enumerate(got):
+            k = min(int(c), cap)
+            out.append((data[r, :k].copy(), info[r, :k] & np.uint32(0x7FFFFFFF), (info[r, :k] >> np.uint32(31)).astype(bool)))
+        return out
+
+    def close(self):
+        if self._h:
+            lib.hzsdr_viterbi_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+__all__ = ["ViterbiDecoder", "conv_encode", "puncture_pattern", "crc_register", "CCSDS_K7", "VITERBI_BITS", "VITERBI_SOFT_F32", "VITERBI_TAIL",
+           "VITERBI_TRUNCATED", "VITERBI_FORM_LDS", "VITERBI_FORM_SCRATCH", "VITERBI_MAX_ROWS", "VITERBI_MIN_K", "VITERBI_MAX_K", "VITERBI_MAX_RATE",
+           "VITERBI_MAX_PATTERN", "VITERBI_MAX_BITS", "VITERBI_MAX_FRAMES"]

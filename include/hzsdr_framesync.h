@@ -3,8 +3,9 @@
  * bits over one row of soft symbols, or over many rows at once.  It is the next member of the family of hzsdr_tuner.h,
  * hzsdr_iir.h, hzsdr_agc.h, hzsdr_carrier.h and hzsdr_symsync.h and stands behind the last of them: it takes the
  * symbol-timing bank's (symbols, counts) as they are, on the device, and this is where the data rate falls from symbols
- * to packets -- where a receive chain hands over to the CPU.  What it leaves to others: descrambling, bit unstuffing,
- * CRCs and every other word of a protocol; soft outputs; a sync word longer than 64 bits.
+ * to packets -- where a receive chain hands over to the CPU.  What it leaves to others: decoding a convolutionally
+ * coded payload and its CRC (hzsdr_viterbi.h takes `out` and `counts` as they are); descrambling, bit unstuffing and
+ * every other word of a protocol; soft outputs; a sync word longer than 64 bits.
  *
  * The entries live beside hzsdr.h and the other headers (same conventions, same status codes, same context).  The
  * reference has no frame sync: the definition below is the contract, restated under tests/ (tests/host/framesync_ref.cpp
