@@ -3,10 +3,15 @@
 A bank of R streams takes (R, n) rows with unit stride along a row and any row pitch (a view of a wider buffer) and
 writes (R, count) rows likewise; one stream takes (n,) and writes (count,).  numpy in a HOST context, torch tensors on
 the context's device in a DEVICE context.  The errors carry the calling class's noun.
+
+RowWaveBank is what the classes of the four row-wave banks (iir.IirBank, symsync.SymbolSync, carrier.CarrierLoop, agc.Agc)
+are built on: the object's life and the calls around its pushes (csrc/hz_loopbank.h is the same layer in C).
 """
+import ctypes as C
+
 import numpy as np
 
-from . import _is_torch, FMT_C64, FMT_I8, FMT_I16, FMT_U8, MEM_HOST
+from . import _is_torch, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, MEM_HOST, lib
 from ._capi import IIR_REAL_F32
 
 # format -> (numpy dtype of an element, bytes of a sample); beside the four source formats, the IIR bank's real float32 rows
@@ -86,3 +91,72 @@ def rows_output(out, count, like, rows, dtype, noun, unit="stream"):
 def cut(out, rows, got):
     """The written part of a destination of rows_output."""
     return out[:got] if rows == 1 else out[:, :got]
+
+
+class RowWaveBank:
+    """The context, the rows, the handle, and the calls hzsdr_<_c>_plan, _position, _get_state, _set_state, _reset and
+    _free over them.  A subclass names its C prefix `_c`, the noun of its errors `_noun`, the C type of a state word
+    `_state_c` and what a state of another shape is told, `_state_msg`; it gives _state_shape(), creates `_h` behind
+    _open(), and keeps plan() and state() for their doc strings."""
+    _c = _noun = _state_msg = None
+    _state_c = C.c_float
+
+    def _open(self, ctx, rows):
+        self.ctx, self.rows, self._h = ctx, int(rows), C.c_void_p()
+        if self.rows <= 0:
+            raise ErrInvalidArgument(f"{self._noun}: rows is at least 1")
+
+    def _call(self, name, *args):
+        self.ctx._ck(getattr(lib, f"hzsdr_{self._c}_{name}")(self._h, *args))
+
+    def _plan(self):
+        g, t, f = C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
+        self._call("plan", C.byref(g), C.byref(t), C.byref(f))
+        return g.value, t.value, f.value
+
+    def position(self):
+        """Samples consumed per row."""
+        p = C.c_uint64(0)
+        self._call("position", C.byref(p))
+        return p.value
+
+    def _state(self):
+        z = np.empty(self._state_shape(), self._state_c)
+        self._call("get_state", z.ctypes.data_as(C.POINTER(self._state_c)), z.size)
+        return z, self.position()
+
+    def set_state(self, z, position=0):
+        z = np.ascontiguousarray(z, self._state_c)
+        if z.shape != self._state_shape():
+            raise ErrInvalidArgument(f"{self._noun}: {self._state_msg}")
+        self._call("set_state", z.ctypes.data_as(C.POINTER(self._state_c)), z.size, int(position))
+
+    def _push_tracked(self, samples, fmt, dtype, out, track):
+        """The push of a bank with one output per input and an optional float32 track -> the rows, or (rows, track)."""
+        noun = self._noun
+        ptr, n, pitch = rows_input(samples, fmt, self.rows, noun)
+        out, optr, cap, opitch = rows_output(out, n, samples, self.rows, dtype, noun, unit="row")
+        if cap < n:
+            raise ValueError(f"{noun}: the destination is shorter than the rows")
+        if track is None or track is False:
+            self._call("push", ptr, n, pitch, optr if cap else None, opitch, None, 0)
+            return cut(out, self.rows, n)
+        track, tptr, tcap, tpitch = rows_output(None if track is True else track, n, samples, self.rows, np.float32, f"{noun} track", unit="row")
+        if tcap < n:
+            raise ValueError(f"{noun}: the track is shorter than the rows")
+        self._call("push", ptr, n, pitch, optr if cap else None, opitch, tptr if tcap else None, tpitch)
+        return cut(out, self.rows, n), cut(track, self.rows, n)
+
+    def reset(self):
+        self._call("reset")
+
+    def close(self):
+        if self._h:
+            getattr(lib, f"hzsdr_{self._c}_free")(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

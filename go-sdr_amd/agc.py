@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import ErrInvalidArgument, FMT_C64, lib
-from ._rows import cut, rows_input, rows_output
+from ._rows import RowWaveBank
 from ._capi import AGC_FORM_COMPLEX, AGC_FORM_PER_ROW, AGC_MAX_ROWS, AGC_REAL_F32
 
 _PF = C.POINTER(C.c_float)
@@ -51,21 +51,22 @@ def level(track, ref):
     return np.float32(ref) / np.asarray(track, np.float32)
 
 
-class Agc:
+class Agc(RowWaveBank):
     """hzsdr_agc: push(rows) -> the levelled rows.  `kind` is AGC_REAL_F32 (float32 rows) or FMT_C64 (complex64 rows).
     One row takes (n,) samples; `rows` = R > 1 takes (R, n) with unit stride along a row and any row pitch and returns
     (R, n).  `params` is float32 (7,) -- ref, attack, decay, floor, g0, gmin, gmax -- shared by all rows, or (R, 7), one
     set per row.  numpy in a HOST context; torch tensors on the context's device, written on the context's stream, in
     a DEVICE context."""
 
+    _c = _noun = "agc"
+    _state_msg = "the state is float32 (rows,)"
+
     def __init__(self, ctx, kind, params, rows=1, per_row=False):
-        self.ctx, self.kind, self.rows = ctx, int(kind), int(rows)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("agc: rows is at least 1")
+        self.kind = int(kind)
+        self._open(ctx, rows)
         self.per_row = bool(per_row)
         self.params = self._check(params)
         self._dtype = np.complex64 if self.kind == FMT_C64 else np.float32
-        self._h = C.c_void_p()
         ctx._ck(lib.hzsdr_agc_create(ctx._h, self.kind, self.params.ctypes.data_as(_PF), int(self.per_row), self.rows, C.byref(self._h)))
 
     def _check(self, params):
@@ -76,15 +77,7 @@ class Agc:
 
     def plan(self):
         """(rows per wave, samples per tile, form): the form is AGC_FORM_PER_ROW | AGC_FORM_COMPLEX."""
-        g, t, f = C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_agc_plan(self._h, C.byref(g), C.byref(t), C.byref(f)))
-        return g.value, t.value, f.value
-
-    def position(self):
-        """Samples consumed per row."""
-        p = C.c_uint64(0)
-        self.ctx._ck(lib.hzsdr_agc_position(self._h, C.byref(p)))
-        return p.value
+        return self._plan()
 
     def push(self, samples, out=None, track=None):
         """Run every sample of every row of `samples` through the loop -> the levelled rows, or (rows, track) where a
@@ -92,50 +85,23 @@ class Agc:
         pitch; columns past the samples are left as they are); it may be `samples` itself: the rows are levelled in
         place.  `track` is True (a new float32 array) or a float32 buffer of that form: the gain applied to every
         sample (level turns it into the row's level)."""
-        ptr, n, pitch = rows_input(samples, self.kind, self.rows, "agc")
-        out, optr, cap, opitch = rows_output(out, n, samples, self.rows, self._dtype, "agc", unit="row")
-        if cap < n:
-            raise ValueError("agc: the destination is shorter than the rows")
-        if track is None or track is False:
-            self.ctx._ck(lib.hzsdr_agc_push(self._h, ptr, n, pitch, optr if cap else None, opitch, None, 0))
-            return cut(out, self.rows, n)
-        track, tptr, tcap, tpitch = rows_output(None if track is True else track, n, samples, self.rows, np.float32, "agc track", unit="row")
-        if tcap < n:
-            raise ValueError("agc: the track is shorter than the rows")
-        self.ctx._ck(lib.hzsdr_agc_push(self._h, ptr, n, pitch, optr if cap else None, opitch, tptr if tcap else None, tpitch))
-        return cut(out, self.rows, n), cut(track, self.rows, n)
+        return self._push_tracked(samples, self.kind, self._dtype, out, track)
 
     def set_params(self, params):
         """Exchange the parameters (same shape) between two pushes; the gains and the position stay."""
         p = self._check(params)
-        self.ctx._ck(lib.hzsdr_agc_set_params(self._h, p.ctypes.data_as(_PF)))
+        self._call("set_params", p.ctypes.data_as(_PF))
         self.params = p
 
     def state(self):
         """(g, position): g is float32 (rows,), the gain of every row behind every push so far."""
-        z = np.empty(self.rows, np.float32)
-        self.ctx._ck(lib.hzsdr_agc_get_state(self._h, z.ctypes.data_as(_PF), z.size))
-        return z, self.position()
+        return self._state()
+
+    def _state_shape(self):
+        return (self.rows,)
 
     def set_state(self, g, position=0):
-        g = np.ascontiguousarray(g, np.float32)
-        if g.shape != (self.rows,):
-            raise ErrInvalidArgument("agc: the state is float32 (rows,)")
-        self.ctx._ck(lib.hzsdr_agc_set_state(self._h, g.ctypes.data_as(_PF), g.size, int(position)))
-
-    def reset(self):
-        self.ctx._ck(lib.hzsdr_agc_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib.hzsdr_agc_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        super().set_state(g, position)
 
 
 __all__ = ["Agc", "agc_rates", "level", "AGC_REAL_F32", "AGC_FORM_PER_ROW", "AGC_FORM_COMPLEX", "AGC_MAX_ROWS"]

@@ -24,11 +24,10 @@ import math
 import numpy as np
 
 from . import ErrInvalidArgument, FMT_C64, lib
-from ._rows import cut, rows_input, rows_output
+from ._rows import RowWaveBank
 from ._capi import CARRIER_BPSK, CARRIER_FORM_MODE, CARRIER_FORM_PER_ROW, CARRIER_MAX_ROWS, CARRIER_QPSK, CARRIER_TONE
 
 _PF = C.POINTER(C.c_float)
-_PU = C.POINTER(C.c_uint32)
 
 
 def carrier_gains(bandwidth, damping=0.7071):
@@ -43,20 +42,21 @@ def carrier_gains(bandwidth, damping=0.7071):
     return 4.0 * zeta * tn / d / (2.0 * math.pi), 4.0 * tn * tn / d / (2.0 * math.pi)
 
 
-class CarrierLoop:
+class CarrierLoop(RowWaveBank):
     """hzsdr_carrier: push(rows) -> the derotated rows.  `mode` is CARRIER_TONE, CARRIER_BPSK or CARRIER_QPSK.  One row
     takes (n,) complex64 samples; `rows` = R > 1 takes (R, n) with unit stride along a row and any row pitch and returns
     (R, n).  `params` is float32 (5,) -- alpha, beta, f0, fmin, fmax -- shared by all rows, or (R, 5), one set per row.
     numpy in a HOST context; torch tensors on the context's device, written on the context's stream, in a DEVICE
     context."""
 
+    _c, _noun = "carrier", "carrier loop"
+    _state_c, _state_msg = C.c_uint32, "the state is uint32 (rows, 2)"
+
     def __init__(self, ctx, mode, params, rows=1, per_row=False):
-        self.ctx, self.mode, self.rows = ctx, int(mode), int(rows)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("carrier loop: rows is at least 1")
+        self.mode = int(mode)
+        self._open(ctx, rows)
         self.per_row = bool(per_row)
         self.params = self._check(params)
-        self._h = C.c_void_p()
         ctx._ck(lib.hzsdr_carrier_create(ctx._h, self.mode, self.params.ctypes.data_as(_PF), int(self.per_row), self.rows, C.byref(self._h)))
 
     def _check(self, params):
@@ -67,15 +67,7 @@ class CarrierLoop:
 
     def plan(self):
         """(rows per wave, samples per tile, form): the form is CARRIER_FORM_PER_ROW (or 0) plus mode * CARRIER_FORM_MODE."""
-        g, t, f = C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_carrier_plan(self._h, C.byref(g), C.byref(t), C.byref(f)))
-        return g.value, t.value, f.value
-
-    def position(self):
-        """Samples consumed per row."""
-        p = C.c_uint64(0)
-        self.ctx._ck(lib.hzsdr_carrier_position(self._h, C.byref(p)))
-        return p.value
+        return self._plan()
 
     def push(self, samples, out=None, track=None):
         """Run every sample of every row of `samples` through the loop -> the derotated rows, or (rows, track) where a
@@ -83,51 +75,21 @@ class CarrierLoop:
         columns past the samples are left as they are); it may be `samples` itself: the rows are derotated in place.
         `track` is True (a new float32 array) or a float32 buffer of that form: the frequency estimate behind every
         sample, in cycles per sample."""
-        ptr, n, pitch = rows_input(samples, FMT_C64, self.rows, "carrier loop")
-        out, optr, cap, opitch = rows_output(out, n, samples, self.rows, np.complex64, "carrier loop", unit="row")
-        if cap < n:
-            raise ValueError("carrier loop: the destination is shorter than the rows")
-        if track is None or track is False:
-            self.ctx._ck(lib.hzsdr_carrier_push(self._h, ptr, n, pitch, optr if cap else None, opitch, None, 0))
-            return cut(out, self.rows, n)
-        track, tptr, tcap, tpitch = rows_output(None if track is True else track, n, samples, self.rows, np.float32, "carrier loop track", unit="row")
-        if tcap < n:
-            raise ValueError("carrier loop: the track is shorter than the rows")
-        self.ctx._ck(lib.hzsdr_carrier_push(self._h, ptr, n, pitch, optr if cap else None, opitch, tptr if tcap else None, tpitch))
-        return cut(out, self.rows, n), cut(track, self.rows, n)
+        return self._push_tracked(samples, FMT_C64, np.complex64, out, track)
 
     def set_params(self, params):
         """Exchange the parameters (same shape) between two pushes; theta, F and the position stay."""
         p = self._check(params)
-        self.ctx._ck(lib.hzsdr_carrier_set_params(self._h, p.ctypes.data_as(_PF)))
+        self._call("set_params", p.ctypes.data_as(_PF))
         self.params = p
 
     def state(self):
         """(z, position): z is uint32 (rows, 2) -- theta (2^32 to the turn) and F (an int32's bits, phase units per
         sample: z[:, 1].view(int32) * 2^-32 is the measured offset in cycles per sample); behind every push so far."""
-        z = np.empty((self.rows, 2), np.uint32)
-        self.ctx._ck(lib.hzsdr_carrier_get_state(self._h, z.ctypes.data_as(_PU), z.size))
-        return z, self.position()
+        return self._state()
 
-    def set_state(self, z, position=0):
-        z = np.ascontiguousarray(z, np.uint32)
-        if z.shape != (self.rows, 2):
-            raise ErrInvalidArgument("carrier loop: the state is uint32 (rows, 2)")
-        self.ctx._ck(lib.hzsdr_carrier_set_state(self._h, z.ctypes.data_as(_PU), z.size, int(position)))
-
-    def reset(self):
-        self.ctx._ck(lib.hzsdr_carrier_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib.hzsdr_carrier_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    def _state_shape(self):
+        return (self.rows, 2)
 
 
 __all__ = ["CarrierLoop", "carrier_gains", "CARRIER_TONE", "CARRIER_BPSK", "CARRIER_QPSK", "CARRIER_FORM_PER_ROW", "CARRIER_FORM_MODE",

@@ -19,19 +19,13 @@
 #include "../../include/hzsdr_agc.h"
 #include "hz_agc_math.h"
 #include "hz_agc_plan.h"
+#include "hz_loopbank.h"
 #include "hz_rowwave.h"
 
-struct hzsdr_agc {
-    hzsdr_ctx *ctx;
-    int kind;
-    uint32_t R;
-    bool per_row;
+struct hzsdr_agc : hz::lb::LoopBank<hz::am::Loop, float> {  // params: 7 to the set; the state: R gains
+    static constexpr const char *noun = "agc";
+    int kind = 0;
     hz::ap::Geom g{};
-    std::vector<float> params;       // the caller's: 7, or R * 7
-    std::vector<hz::am::Loop> loop;  // derived from them: 1, or R
-    hz::am::Loop *loop_rows = nullptr;  // per_row: `loop` on the device
-    float *state = nullptr;          // R gains
-    uint64_t pos = 0;
 };
 
 namespace hz {
@@ -191,142 +185,60 @@ static int agc_launch(hzsdr_agc *f, const AgcArgs &a) {
     return agc_complex(f->kind) ? agc_launch_kind<float2>(f, a) : agc_launch_kind<float>(f, a);
 }
 
-static size_t agc_param_sets(const hzsdr_agc *f) { return f->per_row ? f->R : 1; }
-
-static int agc_check_params(hzsdr_ctx *ctx, const float *params, size_t sets) {
-    if (!params) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "agc: null params");
-    for (size_t r = 0; r < sets; r++)
-        if (const char *why = ap::check_params(params + r * ap::kParams)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string("agc: ") + why);
-    return HZSDR_OK;
-}
-
-// validated parameters into the object: the host's copy, the derived constants, and the device's rows of constants
-// (per-row parameters; shared ones travel with each launch).  The device's rows go first: a copy that fails leaves the
-// object as it was.
-static int agc_take_params(hzsdr_agc *f, const float *params) {
-    const size_t sets = agc_param_sets(f);
-    std::vector<am::Loop> loop(sets);
-    for (size_t r = 0; r < sets; r++) loop[r] = ap::derive(params + r * ap::kParams);
-    if (f->per_row) HZ_TRY(bank_upload(f->ctx, f->loop_rows, loop.data(), sets * sizeof(am::Loop)));
-    f->params.assign(params, params + sets * ap::kParams);
-    f->loop.swap(loop);
-    return HZSDR_OK;
-}
-
-// the initial state: g = g0 of the row
-static int agc_initial_state(hzsdr_agc *f) {
-    std::vector<float> z(f->R);
-    for (size_t r = 0; r < f->R; r++) z[r] = ap::initial_gain(f->params.data() + (f->per_row ? r : 0) * ap::kParams);
-    HZ_TRY(bank_upload(f->ctx, f->state, z.data(), z.size() * sizeof(float)));
-    f->pos = 0;
-    return HZSDR_OK;
-}
+// what the bank gives hz_loopbank.h
+struct AgcBank {
+    using Obj = hzsdr_agc;
+    static constexpr size_t kParams = ap::kParams;
+    static const char *check_params(const float *p) { return ap::check_params(p); }
+    static am::Loop derive(const float *p) { return ap::derive(p); }
+    static int check_kind(hzsdr_ctx *ctx, int kind) {
+        if (kind != HZSDR_AGC_REAL_F32 && kind != HZSDR_FMT_C64) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "agc: real float32 or complex64 rows");
+        return HZSDR_OK;
+    }
+    static void shape(hzsdr_agc *f, int kind) {
+        f->kind = kind;
+        f->g = ap::agc_geom(f->R, agc_complex(kind));
+        f->words = f->R;
+    }
+    // the initial state: g = g0 of the row
+    static void initial(const hzsdr_agc *f, size_t r, size_t set, float *z) { z[r] = ap::initial_gain(f->params.data() + set * kParams); }
+};
 
 }  // namespace hz
 
 extern "C" {
 
 int hzsdr_agc_create(hzsdr_ctx *ctx, int kind, const float *params, int per_row, size_t rows, hzsdr_agc **out) {
-    using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (kind != HZSDR_AGC_REAL_F32 && kind != HZSDR_FMT_C64) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "agc: real float32 or complex64 rows");
-    if (rows == 0 || rows > ap::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "agc: 1 ... 8192 rows");
-    hzsdr_agc *f = new hzsdr_agc{ctx, kind, (uint32_t)rows, per_row != 0};
-    auto undo = [&](int rc) {
-        hzsdr_agc_free(f);
-        return rc;
-    };
-    int rc = agc_check_params(ctx, params, agc_param_sets(f));
-    if (rc == HZSDR_OK) rc = enter(ctx);
-    if (rc != HZSDR_OK) {
-        delete f;
-        return rc;
-    }
-    f->g = ap::agc_geom(f->R, agc_complex(kind));
-    hipError_t e = hipMalloc((void **)&f->state, (size_t)f->R * sizeof(float));
-    if (e == hipSuccess && f->per_row) e = hipMalloc((void **)&f->loop_rows, (size_t)f->R * sizeof(am::Loop));
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "agc_create", __FILE__, __LINE__));
-    rc = agc_take_params(f, params);
-    if (rc == HZSDR_OK) rc = agc_initial_state(f);
-    if (rc != HZSDR_OK) return undo(rc);
-    *out = f;
-    return HZSDR_OK;
+    return hz::lb::create<hz::AgcBank>(ctx, kind, params, per_row, rows, out);
 }
 
 int hzsdr_agc_push(hzsdr_agc *f, const void *in, size_t n, size_t in_stride, void *out, size_t out_stride, float *track, size_t track_stride) {
     using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    hzsdr_ctx *ctx = f->ctx;
-    const size_t R = f->R;
-    if (n && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "agc: null input");
-    if (R > 1 && in_stride < n) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "agc: in_stride is below the samples of the push");
-    if (f->pos + n < f->pos) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "agc: the push is too long");
-    HZ_TRY(check_rows_out(ctx, "agc", R, out, n, out_stride, n, 0));
-    if (track) HZ_TRY(check_rows_out(ctx, "agc track", R, track, n, track_stride, n, 0));
-    if (n && in == out && R > 1 && in_stride != out_stride) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "agc: in place needs equal strides");
-    HZ_TRY(enter(ctx));
-    if (n == 0) return HZSDR_OK;
-    Stage st(ctx);
-    const void *din;
-    void *dout, *dtrack = nullptr;
-    size_t dstride, ostride, tstride = 0;
-    const size_t size = agc_size(f->kind);
-    HZ_TRY(st.in_rows(0, in, R, n, in_stride, size, &din, &dstride));
-    HZ_TRY(st.out_rows(1, out, R, n, out_stride, size, &dout, &ostride));
-    if (track) HZ_TRY(st.out_rows(2, track, R, n, track_stride, sizeof(float), &dtrack, &tstride));
-    AgcArgs a{din, dstride, dout, ostride, (float *)dtrack, tstride, n, f->loop_rows, f->state, f->R, f->g.G, f->g.P, f->loop[0]};
-    HZ_TRY(agc_launch(f, a));
-    f->pos += n;
-    return st.finish();
+    const size_t size = f ? agc_size(f->kind) : 0;
+    return lb::push_rows(f, n, {in, in_stride, size}, {out, n, out_stride, size}, {track, n, track_stride, sizeof(float)}, [&](const lb::DevRows &d) {
+        AgcArgs a{d.in, d.in_stride, d.out, d.out_stride, d.track, d.track_stride, n, f->loop_rows, f->state, f->R, f->g.G, f->g.P, f->loop[0]};
+        return agc_launch(f, a);
+    });
 }
 
-int hzsdr_agc_set_params(hzsdr_agc *f, const float *params) {
-    using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(agc_check_params(f->ctx, params, agc_param_sets(f)));
-    HZ_TRY(enter(f->ctx));
-    return agc_take_params(f, params);  // (behind the pushes so far on the context's stream)
-}
+int hzsdr_agc_set_params(hzsdr_agc *f, const float *params) { return hz::lb::set_params<hz::AgcBank>(f, params); }
 
-int hzsdr_agc_get_state(hzsdr_agc *f, float *state, size_t cap) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    return hz::bank_state_get(f->ctx, "agc", state, cap, f->state, f->R);
-}
+int hzsdr_agc_get_state(hzsdr_agc *f, float *state, size_t cap) { return hz::lb::get_state(f, state, cap); }
 
 int hzsdr_agc_set_state(hzsdr_agc *f, const float *state, size_t count, uint64_t position) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(hz::bank_state_set(f->ctx, "agc", f->state, state, count, f->R, "the state has one float per row"));
-    f->pos = position;
-    return HZSDR_OK;
+    return hz::lb::set_state(f, state, count, position, "the state has one float per row");
 }
 
-int hzsdr_agc_position(const hzsdr_agc *f, uint64_t *position) {
-    if (!f || !position) return HZSDR_ERR_INVALID_ARGUMENT;
-    *position = f->pos;
-    return HZSDR_OK;
-}
+int hzsdr_agc_position(const hzsdr_agc *f, uint64_t *position) { return hz::lb::position(f, position); }
 
 int hzsdr_agc_plan(const hzsdr_agc *f, size_t *rows_per_wave, size_t *tile_samples, int *form) {
     if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (rows_per_wave) *rows_per_wave = f->g.G;
-    if (tile_samples) *tile_samples = f->g.T;
-    if (form) *form = (f->per_row ? HZSDR_AGC_FORM_PER_ROW : 0) | (hz::agc_complex(f->kind) ? HZSDR_AGC_FORM_COMPLEX : 0);
-    return HZSDR_OK;
+    return hz::lb::plan(f, rows_per_wave, tile_samples, form,
+                        (f->per_row ? HZSDR_AGC_FORM_PER_ROW : 0) | (hz::agc_complex(f->kind) ? HZSDR_AGC_FORM_COMPLEX : 0));
 }
 
-int hzsdr_agc_reset(hzsdr_agc *f) {
-    using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(enter(f->ctx));
-    return agc_initial_state(f);
-}
+int hzsdr_agc_reset(hzsdr_agc *f) { return hz::lb::reset<hz::AgcBank>(f); }
 
-int hzsdr_agc_free(hzsdr_agc *f) {
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(f->ctx, {f->loop_rows, f->state});
-    delete f;
-    return HZSDR_OK;
-}
+int hzsdr_agc_free(hzsdr_agc *f) { return f ? hz::lb::destroy(f, {f->loop_rows}) : HZSDR_ERR_INVALID_ARGUMENT; }
 
 }  // extern "C"

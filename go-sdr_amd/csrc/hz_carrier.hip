@@ -17,19 +17,13 @@
 #include "../../include/hzsdr_carrier.h"
 #include "hz_carrier_math.h"
 #include "hz_carrier_plan.h"
+#include "hz_loopbank.h"
 #include "hz_rowwave.h"
 
-struct hzsdr_carrier {
-    hzsdr_ctx *ctx;
-    int mode;
-    uint32_t R;
-    bool per_row;
+struct hzsdr_carrier : hz::lb::LoopBank<hz::cm::Loop, uint32_t> {  // params: 5 to the set; the state: cp::state_words, cp::state_index
+    static constexpr const char *noun = "carrier";
+    int mode = 0;
     hz::cp::Geom g{};
-    std::vector<float> params;       // the caller's: 5, or R * 5
-    std::vector<hz::cm::Loop> loop;  // derived from them: 1, or R
-    hz::cm::Loop *loop_rows = nullptr;  // per_row: `loop` on the device
-    uint32_t *state = nullptr;       // cp::state_words, cp::state_index
-    uint64_t pos = 0;
 };
 
 namespace hz {
@@ -175,147 +169,62 @@ static int car_launch(hzsdr_carrier *f, const CarArgs &a) {
     }
 }
 
-static size_t car_param_sets(const hzsdr_carrier *f) { return f->per_row ? f->R : 1; }
-static size_t car_state_bytes(const hzsdr_carrier *f) { return cp::state_words(f->R) * sizeof(uint32_t); }
-
-static int car_check_params(hzsdr_ctx *ctx, const float *params, size_t sets) {
-    if (!params) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: null params");
-    for (size_t r = 0; r < sets; r++)
-        if (const char *why = cp::check_params(params + r * cp::kParams)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string("carrier: ") + why);
-    return HZSDR_OK;
-}
-
-// validated parameters into the object: the host's copy, the derived constants, and the device's rows of constants
-// (per-row parameters; shared ones travel with each launch).  The device's rows go first: a copy that fails leaves the
-// object as it was.
-static int car_take_params(hzsdr_carrier *f, const float *params) {
-    const size_t sets = car_param_sets(f);
-    std::vector<cm::Loop> loop(sets);
-    for (size_t r = 0; r < sets; r++) loop[r] = cp::derive(params + r * cp::kParams);
-    if (f->per_row) HZ_TRY(bank_upload(f->ctx, f->loop_rows, loop.data(), sets * sizeof(cm::Loop)));
-    f->params.assign(params, params + sets * cp::kParams);
-    f->loop.swap(loop);
-    return HZSDR_OK;
-}
-
-// the initial state: theta = 0, F = F0 of the row
-static int car_initial_state(hzsdr_carrier *f) {
-    std::vector<uint32_t> z(cp::state_words(f->R), 0u);
-    for (size_t r = 0; r < f->R; r++) z[cp::state_index(r, 1)] = (uint32_t)f->loop[f->per_row ? r : 0].f0;
-    HZ_TRY(bank_upload(f->ctx, f->state, z.data(), car_state_bytes(f)));
-    f->pos = 0;
-    return HZSDR_OK;
-}
+// what the bank gives hz_loopbank.h
+struct CarBank {
+    using Obj = hzsdr_carrier;
+    static constexpr size_t kParams = cp::kParams;
+    static const char *check_params(const float *p) { return cp::check_params(p); }
+    static cm::Loop derive(const float *p) { return cp::derive(p); }
+    static int check_kind(hzsdr_ctx *ctx, int mode) {
+        if (mode != HZSDR_CARRIER_TONE && mode != HZSDR_CARRIER_BPSK && mode != HZSDR_CARRIER_QPSK)
+            return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: the mode is HZSDR_CARRIER_TONE, _BPSK or _QPSK");
+        return HZSDR_OK;
+    }
+    static void shape(hzsdr_carrier *f, int mode) {
+        f->mode = mode;
+        f->g = cp::carrier_geom(f->R, true);
+        f->words = cp::state_words(f->R);
+    }
+    // the initial state: theta = 0, F = F0 of the row
+    static void initial(const hzsdr_carrier *f, size_t r, size_t set, uint32_t *z) { z[cp::state_index(r, 1)] = (uint32_t)f->loop[set].f0; }
+};
 
 }  // namespace hz
 
 extern "C" {
 
 int hzsdr_carrier_create(hzsdr_ctx *ctx, int mode, const float *params, int per_row, size_t rows, hzsdr_carrier **out) {
-    using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (mode != HZSDR_CARRIER_TONE && mode != HZSDR_CARRIER_BPSK && mode != HZSDR_CARRIER_QPSK)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: the mode is HZSDR_CARRIER_TONE, _BPSK or _QPSK");
-    if (rows == 0 || rows > cp::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: 1 ... 8192 rows");
-    hzsdr_carrier *f = new hzsdr_carrier{ctx, mode, (uint32_t)rows, per_row != 0};
-    auto undo = [&](int rc) {
-        hzsdr_carrier_free(f);
-        return rc;
-    };
-    int rc = car_check_params(ctx, params, car_param_sets(f));
-    if (rc == HZSDR_OK) rc = enter(ctx);
-    if (rc != HZSDR_OK) {
-        delete f;
-        return rc;
-    }
-    f->g = cp::carrier_geom(f->R, true);
-    hipError_t e = hipMalloc((void **)&f->state, car_state_bytes(f));
-    if (e == hipSuccess && f->per_row) e = hipMalloc((void **)&f->loop_rows, (size_t)f->R * sizeof(cm::Loop));
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "carrier_create", __FILE__, __LINE__));
-    rc = car_take_params(f, params);
-    if (rc == HZSDR_OK) rc = car_initial_state(f);
-    if (rc != HZSDR_OK) return undo(rc);
-    *out = f;
-    return HZSDR_OK;
+    return hz::lb::create<hz::CarBank>(ctx, mode, params, per_row, rows, out);
 }
 
 int hzsdr_carrier_push(hzsdr_carrier *f, const void *in, size_t n, size_t in_stride, void *out, size_t out_stride, float *track,
                        size_t track_stride) {
     using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    hzsdr_ctx *ctx = f->ctx;
-    const size_t R = f->R;
-    if (n && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: null input");
-    if (R > 1 && in_stride < n) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: in_stride is below the samples of the push");
-    if (f->pos + n < f->pos) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: the push is too long");
-    HZ_TRY(check_rows_out(ctx, "carrier", R, out, n, out_stride, n, 0));
-    if (track) HZ_TRY(check_rows_out(ctx, "carrier track", R, track, n, track_stride, n, 0));
-    if (n && in == out && R > 1 && in_stride != out_stride) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "carrier: in place needs equal strides");
-    HZ_TRY(enter(ctx));
-    if (n == 0) return HZSDR_OK;
-    Stage st(ctx);
-    const void *din;
-    void *dout, *dtrack = nullptr;
-    size_t dstride, ostride, tstride = 0;
-    HZ_TRY(st.in_rows(0, in, R, n, in_stride, sizeof(float2), &din, &dstride));
-    HZ_TRY(st.out_rows(1, out, R, n, out_stride, sizeof(float2), &dout, &ostride));
-    if (track) HZ_TRY(st.out_rows(2, track, R, n, track_stride, sizeof(float), &dtrack, &tstride));
-    CarArgs a{(const float2 *)din, dstride, (float2 *)dout, ostride, (float *)dtrack, tstride, n, f->loop_rows, f->state, f->R, f->g.G, f->g.P,
-              f->loop[0]};
-    HZ_TRY(car_launch(f, a));
-    f->pos += n;
-    return st.finish();
+    return lb::push_rows(f, n, {in, in_stride, sizeof(float2)}, {out, n, out_stride, sizeof(float2)}, {track, n, track_stride, sizeof(float)},
+                         [&](const lb::DevRows &d) {
+                             CarArgs a{(const float2 *)d.in, d.in_stride, (float2 *)d.out, d.out_stride, d.track, d.track_stride, n, f->loop_rows,
+                                       f->state, f->R, f->g.G, f->g.P, f->loop[0]};
+                             return car_launch(f, a);
+                         });
 }
 
-int hzsdr_carrier_set_params(hzsdr_carrier *f, const float *params) {
-    using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(car_check_params(f->ctx, params, car_param_sets(f)));
-    HZ_TRY(enter(f->ctx));
-    return car_take_params(f, params);  // (behind the pushes so far on the context's stream)
-}
+int hzsdr_carrier_set_params(hzsdr_carrier *f, const float *params) { return hz::lb::set_params<hz::CarBank>(f, params); }
 
-int hzsdr_carrier_get_state(hzsdr_carrier *f, uint32_t *state, size_t cap) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    static_assert(sizeof(uint32_t) == sizeof(float), "the state's words move as the sibling banks' floats do");
-    return hz::bank_state_get(f->ctx, "carrier", (float *)state, cap, (const float *)f->state, hz::cp::state_words(f->R));
-}
+int hzsdr_carrier_get_state(hzsdr_carrier *f, uint32_t *state, size_t cap) { return hz::lb::get_state(f, state, cap); }
 
 int hzsdr_carrier_set_state(hzsdr_carrier *f, const uint32_t *state, size_t count, uint64_t position) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(hz::bank_state_set(f->ctx, "carrier", (float *)f->state, (const float *)state, count, hz::cp::state_words(f->R),
-                              "the state has rows * 2 words"));
-    f->pos = position;
-    return HZSDR_OK;
+    return hz::lb::set_state(f, state, count, position, "the state has rows * 2 words");
 }
 
-int hzsdr_carrier_position(const hzsdr_carrier *f, uint64_t *position) {
-    if (!f || !position) return HZSDR_ERR_INVALID_ARGUMENT;
-    *position = f->pos;
-    return HZSDR_OK;
-}
+int hzsdr_carrier_position(const hzsdr_carrier *f, uint64_t *position) { return hz::lb::position(f, position); }
 
 int hzsdr_carrier_plan(const hzsdr_carrier *f, size_t *rows_per_wave, size_t *tile_samples, int *form) {
     if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (rows_per_wave) *rows_per_wave = f->g.G;
-    if (tile_samples) *tile_samples = f->g.T;
-    if (form) *form = (f->per_row ? HZSDR_CARRIER_FORM_PER_ROW : 0) + f->mode * HZSDR_CARRIER_FORM_MODE;
-    return HZSDR_OK;
+    return hz::lb::plan(f, rows_per_wave, tile_samples, form, (f->per_row ? HZSDR_CARRIER_FORM_PER_ROW : 0) + f->mode * HZSDR_CARRIER_FORM_MODE);
 }
 
-int hzsdr_carrier_reset(hzsdr_carrier *f) {
-    using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(enter(f->ctx));
-    return car_initial_state(f);
-}
+int hzsdr_carrier_reset(hzsdr_carrier *f) { return hz::lb::reset<hz::CarBank>(f); }
 
-int hzsdr_carrier_free(hzsdr_carrier *f) {
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(f->ctx, {f->loop_rows, f->state});
-    delete f;
-    return HZSDR_OK;
-}
+int hzsdr_carrier_free(hzsdr_carrier *f) { return f ? hz::lb::destroy(f, {f->loop_rows}) : HZSDR_ERR_INVALID_ARGUMENT; }
 
 }  // extern "C"

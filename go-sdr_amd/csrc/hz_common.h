@@ -182,7 +182,7 @@ struct Stage {
 };
 
 // ---- what the bank objects (spectrum, channelizer, synthesizer, resampler, demodulator, tuner, channel bank,
-// covariance, IIR, symbol timing) share on the host ----
+// covariance, IIR, symbol timing, carrier recovery, AGC, frame sync, Viterbi) share on the host ----
 
 // The checks of a call that writes `count` outputs into each of `rows` rows, before anything is launched; tile: outputs
 // per workgroup of the kernel whose grid the count sets (0: no such limit).
@@ -209,9 +209,6 @@ inline void bank_release(hzsdr_ctx *ctx, std::initializer_list<void *> ptrs) {
         if (p) (void)hipFree(p);
 }
 
-// ---- and what the two row-wave banks (IIR, symbol timing) share on top: a state array of `floats` floats on the
-// device that the caller may read and replace, and tables with a row per row ----
-
 // host memory onto the device behind the calls so far on the context's stream; on return `src` is free to go
 inline int bank_upload(hzsdr_ctx *ctx, void *dst_dev, const void *src, size_t bytes) {
     HZ_HIP(ctx, hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -219,19 +216,7 @@ inline int bank_upload(hzsdr_ctx *ctx, void *dst_dev, const void *src, size_t by
     return HZSDR_OK;
 }
 
-inline int bank_state_get(hzsdr_ctx *ctx, const char *who, float *dst, size_t cap, const float *src_dev, size_t floats) {
-    if (cap < floats) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, std::string(who) + ": the state array is too small");
-    HZ_TRY(enter(ctx));
-    HZ_HIP(ctx, hipMemcpyAsync(dst, src_dev, floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return HZSDR_OK;
-}
-
-// msg: what the state has, behind "who: "
-inline int bank_state_set(hzsdr_ctx *ctx, const char *who, float *dst_dev, const float *src, size_t count, size_t floats, const char *msg) {
-    if (count != floats) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string(who) + ": " + msg);
-    HZ_TRY(enter(ctx));
-    return bank_upload(ctx, dst_dev, src, floats * sizeof(float));  // (the caller's array is free to go)
-}
+// (what the four row-wave banks -- IIR, symbol timing, carrier recovery, AGC -- share on top, a state array that the
+// caller may read and replace and parameter sets with a row per row, is hz_loopbank.h)
 
 }  // namespace hz

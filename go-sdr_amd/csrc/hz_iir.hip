@@ -15,18 +15,16 @@
 #include "../../include/hzsdr_iir.h"
 #include "hz_iir_math.h"
 #include "hz_iir_plan.h"
+#include "hz_loopbank.h"
 #include "hz_rowwave.h"
 
-struct hzsdr_iir {
-    hzsdr_ctx *ctx;
-    int kind;
-    uint32_t S, R;
-    bool per_row;
+struct hzsdr_iir : hz::lb::Bank<float> {  // the state: ip::state_floats, ip::state_index
+    static constexpr const char *noun = "iir";
+    int kind = 0;
+    uint32_t S = 0;
     hz::ip::Geom g{};
     std::vector<float> coef;     // the host's copy: S * 5, or R * S * 5
     float *coef_rows = nullptr;  // per_row: the same on the device
-    float *state = nullptr;      // ip::state_floats, ip::state_index
-    uint64_t pos = 0;
 };
 
 namespace hz {
@@ -237,8 +235,7 @@ static int iir_launch(hzsdr_iir *f, const IirArgs &a) {
 }
 
 static size_t iir_coefs(const hzsdr_iir *f) { return (size_t)(f->per_row ? f->R : 1) * f->S * im::kCoefs; }
-static size_t iir_state_floats(const hzsdr_iir *f) { return ip::state_floats(f->R, f->S, f->g.planes); }
-static size_t iir_state_bytes(const hzsdr_iir *f) { return iir_state_floats(f) * sizeof(float); }
+static size_t iir_state_bytes(const hzsdr_iir *f) { return f->words * sizeof(float); }
 
 static int iir_check_sections(hzsdr_ctx *ctx, const float *sections, size_t count) {
     if (!sections) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: null sections");
@@ -264,7 +261,8 @@ int hzsdr_iir_create(hzsdr_ctx *ctx, int kind_or_format, const float *sections, 
     if (kind_or_format != HZSDR_IIR_REAL_F32 && format_size(kind_or_format) == 0) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "iir: unknown input kind");
     if (n_sections == 0 || n_sections > ip::kMaxSections) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: 1 ... 8 sections");
     if (rows == 0 || rows > ip::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: 1 ... 8192 rows");
-    hzsdr_iir *f = new hzsdr_iir{ctx, kind_or_format, (uint32_t)n_sections, (uint32_t)rows, per_row != 0};
+    hzsdr_iir *f = new hzsdr_iir{};
+    f->ctx = ctx, f->R = (uint32_t)rows, f->per_row = per_row != 0, f->kind = kind_or_format, f->S = (uint32_t)n_sections;
     auto undo = [&](int rc) {
         hzsdr_iir_free(f);
         return rc;
@@ -276,6 +274,7 @@ int hzsdr_iir_create(hzsdr_ctx *ctx, int kind_or_format, const float *sections, 
         return rc;
     }
     f->g = ip::iir_geom(f->R, (uint32_t)iir_in_size(f->kind), iir_complex(f->kind));
+    f->words = ip::state_floats(f->R, f->S, f->g.planes);
     f->coef.assign(sections, sections + iir_coefs(f));
     hipError_t e = hipMalloc((void **)&f->state, iir_state_bytes(f));
     if (e == hipSuccess && f->per_row) e = hipMalloc((void **)&f->coef_rows, f->coef.size() * sizeof(float));
@@ -292,30 +291,12 @@ int hzsdr_iir_push(hzsdr_iir *f, const void *in, size_t n, size_t in_stride, voi
     using namespace hz;
     if (written) *written = 0;
     if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    hzsdr_ctx *ctx = f->ctx;
-    const size_t R = f->R;
-    if (n && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: null input");
-    if (R > 1 && in_stride < n) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: in_stride is below the samples of the push");
-    if (f->pos + n < f->pos) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: the push is too long");
-    HZ_TRY(check_rows_out(ctx, "iir", R, out, out_cap, out_stride, n, 0));
-    if (n && in == out) {
-        if (iir_in_size(f->kind) != iir_out_size(f->kind)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: in place is for float32 and complex64 rows");
-        if (R > 1 && in_stride != out_stride) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "iir: in place needs equal strides");
-    }
-    HZ_TRY(enter(ctx));
-    if (n == 0) return HZSDR_OK;
-    Stage st(ctx);
-    const void *din;
-    void *dout;
-    size_t dstride, ostride;
-    HZ_TRY(st.in_rows(0, in, R, n, in_stride, iir_in_size(f->kind), &din, &dstride));
-    HZ_TRY(st.out_rows(1, out, R, n, out_stride, iir_out_size(f->kind), &dout, &ostride));
-    IirArgs a{din, dstride, dout, ostride, n, f->coef_rows, f->state, f->R, f->S, f->g.G, f->g.P, {}};
-    if (!f->per_row)
-        for (size_t k = 0; k < f->coef.size(); k++) a.coef[k] = f->coef[k];
-    HZ_TRY(iir_launch(f, a));
-    f->pos += n;
-    HZ_TRY(st.finish());
+    HZ_TRY(lb::push_rows(f, n, {in, in_stride, iir_in_size(f->kind)}, {out, out_cap, out_stride, iir_out_size(f->kind)}, {}, [&](const lb::DevRows &d) {
+        IirArgs a{d.in, d.in_stride, d.out, d.out_stride, n, f->coef_rows, f->state, f->R, f->S, f->g.G, f->g.P, {}};
+        if (!f->per_row)
+            for (size_t k = 0; k < f->coef.size(); k++) a.coef[k] = f->coef[k];
+        return iir_launch(f, a);
+    }));
     if (written) *written = n;
     return HZSDR_OK;
 }
@@ -330,30 +311,17 @@ int hzsdr_iir_set_sections(hzsdr_iir *f, const float *sections, size_t n_section
     return iir_upload(f);  // (behind the pushes so far on the context's stream)
 }
 
-int hzsdr_iir_get_state(hzsdr_iir *f, float *state, size_t cap) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    return hz::bank_state_get(f->ctx, "iir", state, cap, f->state, hz::iir_state_floats(f));
-}
+int hzsdr_iir_get_state(hzsdr_iir *f, float *state, size_t cap) { return hz::lb::get_state(f, state, cap); }
 
 int hzsdr_iir_set_state(hzsdr_iir *f, const float *state, size_t count, uint64_t position) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(hz::bank_state_set(f->ctx, "iir", f->state, state, count, hz::iir_state_floats(f), "the state has rows * sections * 2 (* 2) floats"));
-    f->pos = position;
-    return HZSDR_OK;
+    return hz::lb::set_state(f, state, count, position, "the state has rows * sections * 2 (* 2) floats");
 }
 
-int hzsdr_iir_position(const hzsdr_iir *f, uint64_t *position) {
-    if (!f || !position) return HZSDR_ERR_INVALID_ARGUMENT;
-    *position = f->pos;
-    return HZSDR_OK;
-}
+int hzsdr_iir_position(const hzsdr_iir *f, uint64_t *position) { return hz::lb::position(f, position); }
 
 int hzsdr_iir_plan(const hzsdr_iir *f, size_t *rows_per_wave, size_t *tile_samples, int *form) {
     if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (rows_per_wave) *rows_per_wave = f->g.G;
-    if (tile_samples) *tile_samples = f->g.T;
-    if (form) *form = (f->per_row ? HZSDR_IIR_FORM_PER_ROW : 0) | (f->g.planes == 2 ? HZSDR_IIR_FORM_COMPLEX : 0);
-    return HZSDR_OK;
+    return hz::lb::plan(f, rows_per_wave, tile_samples, form, (f->per_row ? HZSDR_IIR_FORM_PER_ROW : 0) | (f->g.planes == 2 ? HZSDR_IIR_FORM_COMPLEX : 0));
 }
 
 int hzsdr_iir_reset(hzsdr_iir *f) {
@@ -365,11 +333,6 @@ int hzsdr_iir_reset(hzsdr_iir *f) {
     return HZSDR_OK;
 }
 
-int hzsdr_iir_free(hzsdr_iir *f) {
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(f->ctx, {f->coef_rows, f->state});
-    delete f;
-    return HZSDR_OK;
-}
+int hzsdr_iir_free(hzsdr_iir *f) { return f ? hz::lb::destroy(f, {f->coef_rows}) : HZSDR_ERR_INVALID_ARGUMENT; }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// hz_rowwave.h -- the device side of the row-wave banks (hz_iir.hip, hz_symsync.hip): what a kernel of the shape
-// "a workgroup is ONE wave, it owns G consecutive rows for the whole push, lane = row walks time" is made of, apart
-// from its walk and its state.  The host arithmetic and the reasons for the shape are hz_rowwave_plan.h.
+// hz_rowwave.h -- the device side of the row-wave banks (hz_iir.hip, hz_symsync.hip, hz_carrier.hip, hz_agc.hip): what a
+// kernel of the shape "a workgroup is ONE wave, it owns G consecutive rows for the whole push, lane = row walks time" is
+// made of, apart from its walk and its state.  The host arithmetic and the reasons for the shape are
+// hz_rowwave_plan.h; the host side of the banks' objects is hz_loopbank.h.
 //
 // Time goes by in tiles of T = 64 K samples through the wave's own LDS, so nothing ever waits for another wave:
 //   1. the tile's raw samples, fetched a tile ahead into registers by all 64 lanes (row fixed, lane = sample: K
@@ -12,8 +13,9 @@
 //      what the walk leaves is not one value per sample;
 // with a wave_sync between the steps.  The loop, and steps 1 and 4 in it, stay written out in each kernel: as helpers
 // (tile_put / tile_get over a conversion) they reach the kernel optimised on their own first, which reorders the
-// instructions of every kernel of both banks; measured so, the symbol-timing bank's complex rows were 1.9 % slower at
-// R = 100 and the IIR bank 1 to 3 % faster (profiles/rowwave_time.txt), and this header is to change no kernel.
+// instructions of every kernel of the two banks there were then; measured so, the symbol-timing bank's complex rows
+// were 1.9 % slower at R = 100 and the IIR bank 1 to 3 % faster (profiles/rowwave_time.txt), and this header is to
+// change no kernel.
 #pragma once
 #include "hz_rowwave_plan.h"
 

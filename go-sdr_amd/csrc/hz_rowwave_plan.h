@@ -1,5 +1,6 @@
 // hz_rowwave_plan.h -- the host arithmetic that the row-wave banks share (the IIR bank, hz_iir_plan.h; the symbol-timing
-// recovery bank, hz_symsync_plan.h), HIP-free so that tests/host/ can run it under the sanitizers: how the rows are dealt
+// recovery bank, hz_symsync_plan.h; the carrier recovery bank, hz_carrier_plan.h; the AGC bank, hz_agc_plan.h), HIP-free
+// so that tests/host/ can run it under the sanitizers: how the rows are dealt
 // to waves, the sample tile, and the address maps of the tile that the kernels themselves use (a host program counts
 // bank conflicts from the same functions).  The device side of the shape is hz_rowwave.h.
 //

@@ -21,21 +21,15 @@
 #include "../../include/hzsdr_symsync.h"
 #include "hz_symsync_math.h"
 #include "hz_symsync_plan.h"
+#include "hz_loopbank.h"
 #include "hz_rowwave.h"
 
-struct hzsdr_symsync {
-    hzsdr_ctx *ctx;
-    int kind;
-    uint32_t R;
-    bool per_row;
+struct hzsdr_symsync : hz::lb::LoopBank<hz::sm::Loop, float> {  // params: 4 to the set; the state: sp::state_floats, sp::state_index
+    static constexpr const char *noun = "symsync";
+    int kind = 0;
     hz::sp::Geom g{};
-    std::vector<float> params;      // the caller's: 4, or R * 4
-    std::vector<hz::sm::Loop> loop;  // derived from them: 1, or R
-    double amin = 1.0;               // the smallest hmin - g_mu over the rows
-    hz::sm::Loop *loop_rows = nullptr;  // per_row: `loop` on the device
-    float *state = nullptr;          // sp::state_floats, sp::state_index
-    uint32_t *maxw = nullptr;        // the largest count of a push, for a caller who asks
-    uint64_t pos = 0;
+    double amin = 1.0;         // the smallest hmin - g_mu over the rows
+    uint32_t *maxw = nullptr;  // the largest count of a push, for a caller who asks
 };
 
 namespace hz {
@@ -237,44 +231,35 @@ static int sym_launch_kind(hzsdr_symsync *f, const SymArgs &a) {
     return HZSDR_OK;
 }
 
-static size_t sym_param_sets(const hzsdr_symsync *f) { return f->per_row ? f->R : 1; }
-static size_t sym_state_floats(const hzsdr_symsync *f) { return sp::state_floats(f->R, f->g.planes); }
-static size_t sym_state_bytes(const hzsdr_symsync *f) { return sym_state_floats(f) * sizeof(float); }
+// what the bank gives hz_loopbank.h
+struct SymBank {
+    using Obj = hzsdr_symsync;
+    static constexpr size_t kParams = sp::kParams;
+    static const char *check_params(const float *p) { return sp::check_params(p); }
+    static sm::Loop derive(const float *p) { return sp::derive(p).loop; }
+    static int check_kind(hzsdr_ctx *ctx, int kind) {
+        if (kind != HZSDR_SYMSYNC_REAL_F32 && kind != HZSDR_FMT_C64) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "symsync: real float32 or complex64 rows");
+        return HZSDR_OK;
+    }
+    static void shape(hzsdr_symsync *f, int kind) {
+        f->kind = kind;
+        f->g = sp::symsync_geom(f->R, sym_complex(kind));
+        f->words = sp::state_floats(f->R, f->g.planes);
+    }
+    // the initial state: c = 0, h = h0 of the row, flag = 0, everything else +0
+    static void initial(const hzsdr_symsync *f, size_t r, size_t set, float *z) {
+        z[r * sp::state_row_floats(f->g.planes) + sp::kStH] = sp::derive(f->params.data() + set * kParams).h0;
+    }
+};
 
-static int sym_check_params(hzsdr_ctx *ctx, const float *params, size_t sets) {
-    if (!params) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: null params");
-    for (size_t r = 0; r < sets; r++)
-        if (const char *why = sp::check_params(params + r * sp::kParams)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string("symsync: ") + why);
-    return HZSDR_OK;
-}
-
-// validated parameters into the object: the host's copy, the derived constants, the smallest advance, and the device's
-// rows of constants (per-row parameters; shared ones travel with each launch).  The device's rows go first: a copy
-// that fails leaves the object as it was.
-static int sym_take_params(hzsdr_symsync *f, const float *params) {
-    const size_t sets = sym_param_sets(f);
-    std::vector<sm::Loop> loop(sets);
+// the bank's own beside its parameters: the smallest advance over the sets the object holds
+static void sym_least_advance(hzsdr_symsync *f) {
     double amin = 0.0;
-    for (size_t r = 0; r < sets; r++) {
-        loop[r] = sp::derive(params + r * sp::kParams).loop;
-        const double a = sp::least_advance(params + r * sp::kParams);
+    for (size_t r = 0; r < f->sets(); r++) {
+        const double a = sp::least_advance(f->params.data() + r * sp::kParams);
         if (r == 0 || a < amin) amin = a;
     }
-    if (f->per_row) HZ_TRY(bank_upload(f->ctx, f->loop_rows, loop.data(), sets * sizeof(sm::Loop)));
-    f->params.assign(params, params + sets * sp::kParams);
-    f->loop.swap(loop);
     f->amin = amin;
-    return HZSDR_OK;
-}
-
-// the initial state: c = 0, h = h0 of the row, flag = 0, everything else +0
-static int sym_initial_state(hzsdr_symsync *f) {
-    const uint32_t per = sp::state_row_floats(f->g.planes);
-    std::vector<float> z(sym_state_floats(f), 0.0f);
-    for (size_t r = 0; r < f->R; r++) z[r * per + sp::kStH] = sp::derive(f->params.data() + (f->per_row ? r : 0) * sp::kParams).h0;
-    HZ_TRY(bank_upload(f->ctx, f->state, z.data(), sym_state_bytes(f)));
-    f->pos = 0;
-    return HZSDR_OK;
 }
 
 }  // namespace hz
@@ -283,31 +268,14 @@ extern "C" {
 
 int hzsdr_symsync_create(hzsdr_ctx *ctx, int kind, const float *params, int per_row, size_t rows, hzsdr_symsync **out) {
     using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
+    HZ_TRY(lb::create<SymBank>(ctx, kind, params, per_row, rows, out));
+    hzsdr_symsync *f = *out;
+    sym_least_advance(f);
+    const hipError_t e = hipMalloc((void **)&f->maxw, sizeof(uint32_t));
+    if (e == hipSuccess) return HZSDR_OK;
     *out = nullptr;
-    if (kind != HZSDR_SYMSYNC_REAL_F32 && kind != HZSDR_FMT_C64) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "symsync: real float32 or complex64 rows");
-    if (rows == 0 || rows > sp::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "symsync: 1 ... 8192 rows");
-    hzsdr_symsync *f = new hzsdr_symsync{ctx, kind, (uint32_t)rows, per_row != 0};
-    auto undo = [&](int rc) {
-        hzsdr_symsync_free(f);
-        return rc;
-    };
-    int rc = sym_check_params(ctx, params, sym_param_sets(f));
-    if (rc == HZSDR_OK) rc = enter(ctx);
-    if (rc != HZSDR_OK) {
-        delete f;
-        return rc;
-    }
-    f->g = sp::symsync_geom(f->R, sym_complex(kind));
-    hipError_t e = hipMalloc((void **)&f->state, sym_state_bytes(f));
-    if (e == hipSuccess) e = hipMalloc((void **)&f->maxw, sizeof(uint32_t));
-    if (e == hipSuccess && f->per_row) e = hipMalloc((void **)&f->loop_rows, (size_t)f->R * sizeof(sm::Loop));
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "symsync_create", __FILE__, __LINE__));
-    rc = sym_take_params(f, params);
-    if (rc == HZSDR_OK) rc = sym_initial_state(f);
-    if (rc != HZSDR_OK) return undo(rc);
-    *out = f;
-    return HZSDR_OK;
+    hzsdr_symsync_free(f);
+    return hip_fail(ctx, e, "symsync_create", __FILE__, __LINE__);
 }
 
 int hzsdr_symsync_max_symbols(const hzsdr_symsync *f, size_t n, size_t *bound) {
@@ -365,51 +333,27 @@ int hzsdr_symsync_push(hzsdr_symsync *f, const void *in, size_t n, size_t in_str
 }
 
 int hzsdr_symsync_set_params(hzsdr_symsync *f, const float *params) {
-    using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(sym_check_params(f->ctx, params, sym_param_sets(f)));
-    HZ_TRY(enter(f->ctx));
-    return sym_take_params(f, params);  // (behind the pushes so far on the context's stream)
+    HZ_TRY(hz::lb::set_params<hz::SymBank>(f, params));
+    hz::sym_least_advance(f);
+    return HZSDR_OK;
 }
 
-int hzsdr_symsync_get_state(hzsdr_symsync *f, float *state, size_t cap) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    return hz::bank_state_get(f->ctx, "symsync", state, cap, f->state, hz::sym_state_floats(f));
-}
+int hzsdr_symsync_get_state(hzsdr_symsync *f, float *state, size_t cap) { return hz::lb::get_state(f, state, cap); }
 
 int hzsdr_symsync_set_state(hzsdr_symsync *f, const float *state, size_t count, uint64_t position) {
-    if (!f || !state) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(hz::bank_state_set(f->ctx, "symsync", f->state, state, count, hz::sym_state_floats(f), "the state has rows * 8 (complex rows: 13) floats"));
-    f->pos = position;
-    return HZSDR_OK;
+    return hz::lb::set_state(f, state, count, position, "the state has rows * 8 (complex rows: 13) floats");
 }
 
-int hzsdr_symsync_position(const hzsdr_symsync *f, uint64_t *position) {
-    if (!f || !position) return HZSDR_ERR_INVALID_ARGUMENT;
-    *position = f->pos;
-    return HZSDR_OK;
-}
+int hzsdr_symsync_position(const hzsdr_symsync *f, uint64_t *position) { return hz::lb::position(f, position); }
 
 int hzsdr_symsync_plan(const hzsdr_symsync *f, size_t *rows_per_wave, size_t *tile_samples, int *form) {
     if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (rows_per_wave) *rows_per_wave = f->g.G;
-    if (tile_samples) *tile_samples = f->g.T;
-    if (form) *form = (f->per_row ? HZSDR_SYMSYNC_FORM_PER_ROW : 0) | (f->g.planes == 2 ? HZSDR_SYMSYNC_FORM_COMPLEX : 0);
-    return HZSDR_OK;
+    return hz::lb::plan(f, rows_per_wave, tile_samples, form,
+                        (f->per_row ? HZSDR_SYMSYNC_FORM_PER_ROW : 0) | (f->g.planes == 2 ? HZSDR_SYMSYNC_FORM_COMPLEX : 0));
 }
 
-int hzsdr_symsync_reset(hzsdr_symsync *f) {
-    using namespace hz;
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    HZ_TRY(enter(f->ctx));
-    return sym_initial_state(f);
-}
+int hzsdr_symsync_reset(hzsdr_symsync *f) { return hz::lb::reset<hz::SymBank>(f); }
 
-int hzsdr_symsync_free(hzsdr_symsync *f) {
-    if (!f) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(f->ctx, {f->loop_rows, f->state, f->maxw});
-    delete f;
-    return HZSDR_OK;
-}
+int hzsdr_symsync_free(hzsdr_symsync *f) { return f ? hz::lb::destroy(f, {f->loop_rows, f->maxw}) : HZSDR_ERR_INVALID_ARGUMENT; }
 
 }  // extern "C"

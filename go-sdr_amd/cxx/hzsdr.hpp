@@ -1210,87 +1210,109 @@ private:
     hzsdr_demod *d_ = nullptr;
 };
 
+// What the four row-wave bank classes below share: the handle and its life, and the calls that differ from bank to bank
+// only in the C function's name.  H is the handle, Z a word of the state; the functions are hzsdr_<bank>_free, _position,
+// _plan, _reset, _get_state and _set_state.  State() is the bank's state array as its header lays it out, SetState() puts
+// one back, Plan() is (rows per wave, samples per tile, HZSDR_<BANK>_FORM_*).
+template <class H, class Z, auto Free, auto PositionFn, auto PlanFn, auto ResetFn, auto GetState, auto SetStateFn>
+class RowWaveBank {
+public:
+    RowWaveBank(const RowWaveBank &) = delete;
+    RowWaveBank &operator=(const RowWaveBank &) = delete;
+    std::vector<Z> State() const {
+        std::vector<Z> z(state_words_);
+        check(x_.raw(), GetState(h_, z.data(), z.size()));
+        return z;
+    }
+    void SetState(const std::vector<Z> &z, uint64_t position = 0) { check(x_.raw(), SetStateFn(h_, z.data(), z.size(), position)); }
+    uint64_t Position() const {
+        uint64_t p = 0;
+        check(x_.raw(), PositionFn(h_, &p));
+        return p;
+    }
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0;
+        int f = 0;
+        check(x_.raw(), PlanFn(h_, &g, &t, &f));
+        return {g, t, f};
+    }
+    void Reset() { check(x_.raw(), ResetFn(h_)); }
+    size_t Rows() const { return rows_; }
+
+protected:
+    RowWaveBank(const Context &x, size_t rows, size_t state_words = 0) : x_(x), rows_(rows), state_words_(state_words) {}
+    ~RowWaveBank() { if (h_) Free(h_); }
+    // one output per input and, where `track` is given, dense rows of n track values (Push: hzsdr_<bank>_push)
+    template <auto Push, typename S> std::vector<S> push_tracked(const void *in, size_t n, size_t in_stride, std::vector<float> *track) {
+        std::vector<S> out(rows_ * n);
+        if (track) track->assign(rows_ * n, 0.0f);
+        check(x_.raw(), Push(h_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n, track && n ? track->data() : nullptr, n));
+        return out;
+    }
+    template <auto Push> void push_in_place(void *rows, size_t n, size_t pitch) {
+        check(x_.raw(), Push(h_, n ? rows : nullptr, n, pitch ? pitch : n, n ? rows : nullptr, pitch ? pitch : n, nullptr, 0));
+    }
+    const Context &x_;
+    size_t rows_, state_words_;
+    H *h_ = nullptr;
+};
+
 // The IIR bank (include/hzsdr_iir.h): the cascade `sections` -- (b0, b1, b2, a1, a2) per section, one cascade shared by
 // all rows, or rows of them when per_row -- over `rows` rows of HZSDR_IIR_REAL_F32 samples (float32 out: Push) or of a
 // source format (complex64 out: PushComplex).  Push filters `n` samples of every row (row r starts r * in_stride
 // samples into `in`; dense rows when in_stride is 0) and returns dense rows of n; one output per input, no flush.
-class IirBank {
+// The state: row, section, z1 / z2, re / im.
+class IirBank : public RowWaveBank<hzsdr_iir, float, hzsdr_iir_free, hzsdr_iir_position, hzsdr_iir_plan, hzsdr_iir_reset, hzsdr_iir_get_state,
+                                   hzsdr_iir_set_state> {
 public:
     IirBank(const Context &x, int kind_or_format, const std::vector<float> &sections, size_t rows = 1, bool per_row = false)
-        : x_(x), rows_(rows), complex_(kind_or_format != HZSDR_IIR_REAL_F32) {
+        : RowWaveBank(x, rows), complex_(kind_or_format != HZSDR_IIR_REAL_F32) {
         const size_t per = 5 * (per_row && rows ? rows : 1);
         sections_ = sections.size() / per;
         if (sections_ * per != sections.size()) throw std::invalid_argument("IirBank: sections are S * 5, or rows * S * 5 values");
-        check(x_.raw(), hzsdr_iir_create(x_.raw(), kind_or_format, sections.data(), sections_, per_row ? 1 : 0, rows, &f_));
+        state_words_ = rows_ * sections_ * 2 * (complex_ ? 2 : 1);
+        check(x_.raw(), hzsdr_iir_create(x_.raw(), kind_or_format, sections.data(), sections_, per_row ? 1 : 0, rows, &h_));
     }
-    ~IirBank() { if (f_) hzsdr_iir_free(f_); }
-    IirBank(const IirBank &) = delete;
-    IirBank &operator=(const IirBank &) = delete;
     // real rows (row r of the result is [r * n, (r + 1) * n))
     std::vector<float> Push(const void *in, size_t n, size_t in_stride = 0) {
         if (complex_) throw std::invalid_argument("IirBank: complex rows go through PushComplex");
-        std::vector<float> out(rows_ * n);
-        size_t w = 0;
-        check(x_.raw(), hzsdr_iir_push(f_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n, n, &w));
-        return out;
+        return push<float>(in, n, in_stride);
     }
     std::vector<std::complex<float>> PushComplex(const void *in, size_t n, size_t in_stride = 0) {
         if (!complex_) throw std::invalid_argument("IirBank: real rows go through Push");
-        std::vector<std::complex<float>> out(rows_ * n);
-        size_t w = 0;
-        check(x_.raw(), hzsdr_iir_push(f_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n, n, &w));
-        return out;
+        return push<std::complex<float>>(in, n, in_stride);
     }
     // the same count and form; the state and the position stay
     void SetSections(const std::vector<float> &sections) {
         if (sections.size() % 5) throw std::invalid_argument("IirBank: sections are S * 5, or rows * S * 5 values");
-        check(x_.raw(), hzsdr_iir_set_sections(f_, sections.data(), sections_));
+        check(x_.raw(), hzsdr_iir_set_sections(h_, sections.data(), sections_));
     }
-    // row, section, z1 / z2, re / im (hzsdr_iir.h)
-    std::vector<float> State() const {
-        std::vector<float> z(rows_ * sections_ * 2 * (complex_ ? 2 : 1));
-        check(x_.raw(), hzsdr_iir_get_state(f_, z.data(), z.size()));
-        return z;
-    }
-    void SetState(const std::vector<float> &z, uint64_t position = 0) { check(x_.raw(), hzsdr_iir_set_state(f_, z.data(), z.size(), position)); }
-    uint64_t Position() const {
-        uint64_t p = 0;
-        check(x_.raw(), hzsdr_iir_position(f_, &p));
-        return p;
-    }
-    // -> (rows per wave, samples per tile, HZSDR_IIR_FORM_*)
-    std::tuple<size_t, size_t, int> Plan() const {
-        size_t g = 0, t = 0;
-        int f = 0;
-        check(x_.raw(), hzsdr_iir_plan(f_, &g, &t, &f));
-        return {g, t, f};
-    }
-    void Reset() { check(x_.raw(), hzsdr_iir_reset(f_)); }
-    size_t Rows() const { return rows_; }
     size_t Sections() const { return sections_; }
 
 private:
-    const Context &x_;
-    size_t rows_, sections_ = 0;
+    template <class V> std::vector<V> push(const void *in, size_t n, size_t in_stride) {
+        std::vector<V> out(rows_ * n);
+        size_t w = 0;
+        check(x_.raw(), hzsdr_iir_push(h_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n, n, &w));
+        return out;
+    }
+    size_t sections_ = 0;
     bool complex_;
-    hzsdr_iir *f_ = nullptr;
 };
 
 // The symbol-timing recovery bank (include/hzsdr_symsync.h): a Gardner loop around a cubic interpolator over `rows` rows
 // of HZSDR_SYMSYNC_REAL_F32 samples (float32 symbols: Push) or HZSDR_FMT_C64 ones (complex64 symbols: PushComplex), with
 // the parameters sps, limit, g_mu, g_omega shared by all rows, or rows of them when per_row.  Push runs `n` samples of
 // every row (row r starts r * in_stride samples into `in`; dense rows when in_stride is 0) and returns the rows' symbols,
-// each row cut to its own count; nothing to flush.
-class SymbolSync {
+// each row cut to its own count; nothing to flush.  The state: per row c, h, flag, y_prev, y_mid, x1, x2, x3.
+class SymbolSync : public RowWaveBank<hzsdr_symsync, float, hzsdr_symsync_free, hzsdr_symsync_position, hzsdr_symsync_plan, hzsdr_symsync_reset,
+                                      hzsdr_symsync_get_state, hzsdr_symsync_set_state> {
 public:
     SymbolSync(const Context &x, int kind, const std::vector<float> &params, size_t rows = 1, bool per_row = false)
-        : x_(x), rows_(rows), complex_(kind != HZSDR_SYMSYNC_REAL_F32) {
+        : RowWaveBank(x, rows, rows * (kind != HZSDR_SYMSYNC_REAL_F32 ? 13 : 8)), complex_(kind != HZSDR_SYMSYNC_REAL_F32) {
         if (params.size() != 4 * (per_row ? rows : 1)) throw std::invalid_argument("SymbolSync: params are 4, or rows * 4 values");
-        check(x_.raw(), hzsdr_symsync_create(x_.raw(), kind, params.data(), per_row ? 1 : 0, rows, &s_));
+        check(x_.raw(), hzsdr_symsync_create(x_.raw(), kind, params.data(), per_row ? 1 : 0, rows, &h_));
     }
-    ~SymbolSync() { if (s_) hzsdr_symsync_free(s_); }
-    SymbolSync(const SymbolSync &) = delete;
-    SymbolSync &operator=(const SymbolSync &) = delete;
     std::vector<std::vector<float>> Push(const void *in, size_t n, size_t in_stride = 0) {
         if (complex_) throw std::invalid_argument("SymbolSync: complex rows go through PushComplex");
         return push<float>(in, n, in_stride);
@@ -1301,32 +1323,11 @@ public:
     }
     size_t MaxSymbols(size_t n) const {
         size_t b = 0;
-        check(x_.raw(), hzsdr_symsync_max_symbols(s_, n, &b));
+        check(x_.raw(), hzsdr_symsync_max_symbols(h_, n, &b));
         return b;
     }
     // the same form; the state and the position stay
-    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_symsync_set_params(s_, params.data())); }
-    // per row c, h, flag, y_prev, y_mid, x1, x2, x3 (hzsdr_symsync.h)
-    std::vector<float> State() const {
-        std::vector<float> z(rows_ * (complex_ ? 13 : 8));
-        check(x_.raw(), hzsdr_symsync_get_state(s_, z.data(), z.size()));
-        return z;
-    }
-    void SetState(const std::vector<float> &z, uint64_t position = 0) { check(x_.raw(), hzsdr_symsync_set_state(s_, z.data(), z.size(), position)); }
-    uint64_t Position() const {
-        uint64_t p = 0;
-        check(x_.raw(), hzsdr_symsync_position(s_, &p));
-        return p;
-    }
-    // -> (rows per wave, samples per tile, HZSDR_SYMSYNC_FORM_*)
-    std::tuple<size_t, size_t, int> Plan() const {
-        size_t g = 0, t = 0;
-        int f = 0;
-        check(x_.raw(), hzsdr_symsync_plan(s_, &g, &t, &f));
-        return {g, t, f};
-    }
-    void Reset() { check(x_.raw(), hzsdr_symsync_reset(s_)); }
-    size_t Rows() const { return rows_; }
+    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_symsync_set_params(h_, params.data())); }
 
 private:
     template <class V> std::vector<std::vector<V>> push(const void *in, size_t n, size_t in_stride) {
@@ -1334,15 +1335,12 @@ private:
         std::vector<V> out(rows_ * bound);
         std::vector<uint32_t> counts(rows_, 0);
         size_t most = 0;
-        check(x_.raw(), hzsdr_symsync_push(s_, n ? in : nullptr, n, in_stride ? in_stride : n, bound ? out.data() : nullptr, bound, bound, counts.data(), &most));
+        check(x_.raw(), hzsdr_symsync_push(h_, n ? in : nullptr, n, in_stride ? in_stride : n, bound ? out.data() : nullptr, bound, bound, counts.data(), &most));
         std::vector<std::vector<V>> rows(rows_);
         for (size_t r = 0; r < rows_; r++) rows[r].assign(out.begin() + r * bound, out.begin() + r * bound + counts[r]);
         return rows;
     }
-    const Context &x_;
-    size_t rows_;
     bool complex_;
-    hzsdr_symsync *s_ = nullptr;
 };
 
 // The carrier recovery bank (include/hzsdr_carrier.h): a second-order loop around a numerically controlled oscillator over
@@ -1350,54 +1348,21 @@ private:
 // fmin, fmax shared by all rows, or rows of them when per_row.  Push runs `n` samples of every row (row r starts
 // r * in_stride samples into `in`; dense rows when in_stride is 0) and returns dense rows of n derotated samples; where
 // `track` is given it takes dense rows of n frequency estimates, in cycles per sample.  One output per input, no flush.
-class CarrierLoop {
+// The state: per row theta, F.
+class CarrierLoop : public RowWaveBank<hzsdr_carrier, uint32_t, hzsdr_carrier_free, hzsdr_carrier_position, hzsdr_carrier_plan, hzsdr_carrier_reset,
+                                       hzsdr_carrier_get_state, hzsdr_carrier_set_state> {
 public:
-    CarrierLoop(const Context &x, int mode, const std::vector<float> &params, size_t rows = 1, bool per_row = false) : x_(x), rows_(rows) {
+    CarrierLoop(const Context &x, int mode, const std::vector<float> &params, size_t rows = 1, bool per_row = false) : RowWaveBank(x, rows, rows * 2) {
         if (params.size() != 5 * (per_row ? rows : 1)) throw std::invalid_argument("CarrierLoop: params are 5, or rows * 5 values");
-        check(x_.raw(), hzsdr_carrier_create(x_.raw(), mode, params.data(), per_row ? 1 : 0, rows, &c_));
+        check(x_.raw(), hzsdr_carrier_create(x_.raw(), mode, params.data(), per_row ? 1 : 0, rows, &h_));
     }
-    ~CarrierLoop() { if (c_) hzsdr_carrier_free(c_); }
-    CarrierLoop(const CarrierLoop &) = delete;
-    CarrierLoop &operator=(const CarrierLoop &) = delete;
     std::vector<std::complex<float>> Push(const void *in, size_t n, size_t in_stride = 0, std::vector<float> *track = nullptr) {
-        std::vector<std::complex<float>> out(rows_ * n);
-        if (track) track->assign(rows_ * n, 0.0f);
-        check(x_.raw(), hzsdr_carrier_push(c_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n,
-                                           track && n ? track->data() : nullptr, n));
-        return out;
+        return push_tracked<hzsdr_carrier_push, std::complex<float>>(in, n, in_stride, track);
     }
     // the rows derotated where they lie (pitch: samples from one row's start to the next; n when 0)
-    void PushInPlace(std::complex<float> *rows, size_t n, size_t pitch = 0) {
-        check(x_.raw(), hzsdr_carrier_push(c_, n ? rows : nullptr, n, pitch ? pitch : n, n ? rows : nullptr, pitch ? pitch : n, nullptr, 0));
-    }
+    void PushInPlace(std::complex<float> *rows, size_t n, size_t pitch = 0) { push_in_place<hzsdr_carrier_push>(rows, n, pitch); }
     // the same form; theta, F and the position stay
-    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_carrier_set_params(c_, params.data())); }
-    // per row theta, F (hzsdr_carrier.h)
-    std::vector<uint32_t> State() const {
-        std::vector<uint32_t> z(rows_ * 2);
-        check(x_.raw(), hzsdr_carrier_get_state(c_, z.data(), z.size()));
-        return z;
-    }
-    void SetState(const std::vector<uint32_t> &z, uint64_t position = 0) { check(x_.raw(), hzsdr_carrier_set_state(c_, z.data(), z.size(), position)); }
-    uint64_t Position() const {
-        uint64_t p = 0;
-        check(x_.raw(), hzsdr_carrier_position(c_, &p));
-        return p;
-    }
-    // -> (rows per wave, samples per tile, HZSDR_CARRIER_FORM_*)
-    std::tuple<size_t, size_t, int> Plan() const {
-        size_t g = 0, t = 0;
-        int f = 0;
-        check(x_.raw(), hzsdr_carrier_plan(c_, &g, &t, &f));
-        return {g, t, f};
-    }
-    void Reset() { check(x_.raw(), hzsdr_carrier_reset(c_)); }
-    size_t Rows() const { return rows_; }
-
-private:
-    const Context &x_;
-    size_t rows_;
-    hzsdr_carrier *c_ = nullptr;
+    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_carrier_set_params(h_, params.data())); }
 };
 
 // The AGC bank (include/hzsdr_agc.h): a multiplicative gain loop over `rows` rows of `kind` (HZSDR_AGC_REAL_F32: float
@@ -1405,58 +1370,31 @@ private:
 // all rows, or rows of them when per_row.  Push runs `n` samples of every row (row r starts r * in_stride samples into
 // `in`; dense rows when in_stride is 0) and returns dense rows of n levelled samples of the input's type (S is float or
 // std::complex<float>, as the kind says); where `track` is given it takes dense rows of n applied gains.  One output per
-// input, no flush.
-class Agc {
+// input, no flush.  The state: per row the gain; ref / gain is the row's level.
+class Agc : public RowWaveBank<hzsdr_agc, float, hzsdr_agc_free, hzsdr_agc_position, hzsdr_agc_plan, hzsdr_agc_reset, hzsdr_agc_get_state,
+                               hzsdr_agc_set_state> {
 public:
-    Agc(const Context &x, int kind, const std::vector<float> &params, size_t rows = 1, bool per_row = false) : x_(x), kind_(kind), rows_(rows) {
+    Agc(const Context &x, int kind, const std::vector<float> &params, size_t rows = 1, bool per_row = false) : RowWaveBank(x, rows, rows), kind_(kind) {
         if (params.size() != 7 * (per_row ? rows : 1)) throw std::invalid_argument("Agc: params are 7, or rows * 7 values");
-        check(x_.raw(), hzsdr_agc_create(x_.raw(), kind, params.data(), per_row ? 1 : 0, rows, &a_));
+        check(x_.raw(), hzsdr_agc_create(x_.raw(), kind, params.data(), per_row ? 1 : 0, rows, &h_));
     }
-    ~Agc() { if (a_) hzsdr_agc_free(a_); }
-    Agc(const Agc &) = delete;
-    Agc &operator=(const Agc &) = delete;
     template <typename S> std::vector<S> Push(const S *in, size_t n, size_t in_stride = 0, std::vector<float> *track = nullptr) {
-        if (sizeof(S) != (kind_ == HZSDR_FMT_C64 ? 8u : 4u)) throw std::invalid_argument("Agc: samples are not of the bank's kind");
-        std::vector<S> out(rows_ * n);
-        if (track) track->assign(rows_ * n, 0.0f);
-        check(x_.raw(), hzsdr_agc_push(a_, n ? in : nullptr, n, in_stride ? in_stride : n, n ? out.data() : nullptr, n,
-                                       track && n ? track->data() : nullptr, n));
-        return out;
+        of_kind(sizeof(S));
+        return push_tracked<hzsdr_agc_push, S>(in, n, in_stride, track);
     }
     // the rows levelled where they lie (pitch: samples from one row's start to the next; n when 0)
     template <typename S> void PushInPlace(S *rows, size_t n, size_t pitch = 0) {
-        if (sizeof(S) != (kind_ == HZSDR_FMT_C64 ? 8u : 4u)) throw std::invalid_argument("Agc: samples are not of the bank's kind");
-        check(x_.raw(), hzsdr_agc_push(a_, n ? rows : nullptr, n, pitch ? pitch : n, n ? rows : nullptr, pitch ? pitch : n, nullptr, 0));
+        of_kind(sizeof(S));
+        push_in_place<hzsdr_agc_push>(rows, n, pitch);
     }
     // the same form; the gains and the position stay
-    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_agc_set_params(a_, params.data())); }
-    // per row the gain (hzsdr_agc.h); ref / gain is the row's level
-    std::vector<float> State() const {
-        std::vector<float> g(rows_);
-        check(x_.raw(), hzsdr_agc_get_state(a_, g.data(), g.size()));
-        return g;
-    }
-    void SetState(const std::vector<float> &g, uint64_t position = 0) { check(x_.raw(), hzsdr_agc_set_state(a_, g.data(), g.size(), position)); }
-    uint64_t Position() const {
-        uint64_t p = 0;
-        check(x_.raw(), hzsdr_agc_position(a_, &p));
-        return p;
-    }
-    // -> (rows per wave, samples per tile, HZSDR_AGC_FORM_*)
-    std::tuple<size_t, size_t, int> Plan() const {
-        size_t g = 0, t = 0;
-        int f = 0;
-        check(x_.raw(), hzsdr_agc_plan(a_, &g, &t, &f));
-        return {g, t, f};
-    }
-    void Reset() { check(x_.raw(), hzsdr_agc_reset(a_)); }
-    size_t Rows() const { return rows_; }
+    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_agc_set_params(h_, params.data())); }
 
 private:
-    const Context &x_;
+    void of_kind(size_t size) const {
+        if (size != (kind_ == HZSDR_FMT_C64 ? 8u : 4u)) throw std::invalid_argument("Agc: samples are not of the bank's kind");
+    }
     int kind_;
-    size_t rows_;
-    hzsdr_agc *a_ = nullptr;
 };
 
 // The frame sync bank (include/hzsdr_framesync.h): hard decisions, a search for a sync word of `word_bits` bits under the

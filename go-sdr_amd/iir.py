@@ -21,7 +21,7 @@ import math
 import numpy as np
 
 from . import ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib  # noqa: F401
-from ._rows import cut, rows_input, rows_output
+from ._rows import RowWaveBank, cut, rows_input, rows_output
 from ._capi import IIR_FORM_COMPLEX, IIR_FORM_PER_ROW, IIR_MAX_ROWS, IIR_MAX_SECTIONS, IIR_REAL_F32
 
 _PF = C.POINTER(C.c_float)
@@ -124,22 +124,23 @@ def response(sections, f, fs):
     return h
 
 
-class IirBank:
+class IirBank(RowWaveBank):
     """hzsdr_iir: push(samples) -> the filtered rows.  `kind` is IIR_REAL_F32 (float32 in and out) or a source format
     (u8 / i8 / i16 / c64 in, complex64 out).  One row takes (n,) samples ((n, 2) for the byte and int16 formats);
     `rows` = R > 1 takes (R, n) with unit stride along a row and any row pitch and returns (R, n).  `sections` is
     (S, 5) shared by all rows, or (R, S, 5), one cascade per row.  numpy in a HOST context; torch tensors on the
     context's device, written on the context's stream, in a DEVICE context."""
 
+    _c, _noun = "iir", "iir bank"
+    _state_msg = "the state is (rows, S, 2), with a last axis (re, im) for complex rows"
+
     def __init__(self, ctx, kind, sections, rows=1):
-        self.ctx, self.kind, self.rows = ctx, int(kind), int(rows)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("iir bank: rows is at least 1")
+        self.kind = int(kind)
+        self._open(ctx, rows)
         self.sections = self._check(sections, None)
         self.per_row = self.sections.ndim == 3
         self.n_sections = int(self.sections.shape[-2])
         self.complex = self.kind != IIR_REAL_F32
-        self._h = C.c_void_p()
         ctx._ck(lib.hzsdr_iir_create(ctx._h, self.kind, self.sections.ctypes.data_as(_PF), self.n_sections, int(self.per_row), self.rows,
                                      C.byref(self._h)))
 
@@ -153,15 +154,7 @@ class IirBank:
 
     def plan(self):
         """(rows per wave, samples per tile, form): the form is a sum of IIR_FORM_PER_ROW and IIR_FORM_COMPLEX."""
-        g, t, f = C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_iir_plan(self._h, C.byref(g), C.byref(t), C.byref(f)))
-        return g.value, t.value, f.value
-
-    def position(self):
-        """Samples consumed per row."""
-        p = C.c_uint64(0)
-        self.ctx._ck(lib.hzsdr_iir_position(self._h, C.byref(p)))
-        return p.value
+        return self._plan()
 
     def push(self, samples, out=None):
         """Filter every sample of every row of `samples`.  `out`, when given, is a float32 (real rows) or complex64
@@ -170,13 +163,13 @@ class IirBank:
         ptr, n, pitch = rows_input(samples, self.kind, self.rows, "iir bank")
         out, optr, cap, opitch = rows_output(out, n, samples, self.rows, np.complex64 if self.complex else np.float32, "iir bank", unit="row")
         got = C.c_size_t(0)
-        self.ctx._ck(lib.hzsdr_iir_push(self._h, ptr, n, pitch, optr if cap else None, cap, opitch, C.byref(got)))
+        self._call("push", ptr, n, pitch, optr if cap else None, cap, opitch, C.byref(got))
         return cut(out, self.rows, got.value)
 
     def set_sections(self, sections):
         """Exchange the coefficients (same shape) between two pushes; the state and the position stay."""
         s = self._check(sections, self.sections)
-        self.ctx._ck(lib.hzsdr_iir_set_sections(self._h, s.ctypes.data_as(_PF), self.n_sections))
+        self._call("set_sections", s.ctypes.data_as(_PF), self.n_sections)
         self.sections = s
 
     def _state_shape(self):
@@ -185,29 +178,7 @@ class IirBank:
     def state(self):
         """(z, position): z is float32 (rows, S, 2) for real rows -- z1, z2 -- and (rows, S, 2, 2) for complex rows,
         the last axis re, im; behind every push so far."""
-        z = np.empty(self._state_shape(), np.float32)
-        self.ctx._ck(lib.hzsdr_iir_get_state(self._h, z.ctypes.data_as(_PF), z.size))
-        return z, self.position()
-
-    def set_state(self, z, position=0):
-        z = np.ascontiguousarray(z, np.float32)
-        if z.shape != self._state_shape():
-            raise ErrInvalidArgument("iir bank: the state is (rows, S, 2), with a last axis (re, im) for complex rows")
-        self.ctx._ck(lib.hzsdr_iir_set_state(self._h, z.ctypes.data_as(_PF), z.size, int(position)))
-
-    def reset(self):
-        self.ctx._ck(lib.hzsdr_iir_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib.hzsdr_iir_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        return self._state()
 
 
 __all__ = ["IirBank", "one_pole", "dc_block", "deemphasis", "notch", "lowpass", "highpass", "butterworth", "response", "IIR_REAL_F32",

@@ -953,16 +953,13 @@ def demodulator_blocks(r, demodulator, block=READER_BLOCK):
         yield tail
 
 
-# ---- a Reader, or a demodulator's blocks, through the IIR bank (include/hzsdr_iir.h) ------------
+# ---- the row-wave banks behind a Reader or a chain's blocks: what iir_rows, symbol_rows, carrier_rows and agc_rows do alike ----
 
-def iir_rows(src, bank, block=READER_BLOCK):
-    """Push `src` through `bank` (an iir.IirBank on a HOST context) and yield each push's rows.  `src` is a Reader of
-    the bank's source format, read to its end in blocks of `block` samples (a one-row bank: a DC blocker in front of a
-    detector), or any iterable of blocks the bank takes as they are -- demodulator_blocks(...) into a bank of
-    IIR_REAL_F32 rows (de-emphasis, a squelch smoother).  One output per input and nothing to flush: concatenated
-    along the last axis, the whole filtered stream at the input's rate."""
+def _pushed_rows(src, bank, block, mismatch):
+    """Each push's result of `src` through `bank`: a Reader read to its end in blocks of `block` samples, refused where
+    mismatch(its format) holds, or an iterable of blocks pushed as they are; empty reads and blocks are passed over."""
     if isinstance(src, Reader):
-        if bank.kind != src.sample_format():
+        if mismatch(src.sample_format()):
             raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
         buf = make_samples(src.sample_format(), block)
         while True:
@@ -976,6 +973,17 @@ def iir_rows(src, bank, block=READER_BLOCK):
     for b in src:
         if b.shape[-1]:
             yield bank.push(b)
+
+
+# ---- a Reader, or a demodulator's blocks, through the IIR bank (include/hzsdr_iir.h) ------------
+
+def iir_rows(src, bank, block=READER_BLOCK):
+    """Push `src` through `bank` (an iir.IirBank on a HOST context) and yield each push's rows.  `src` is a Reader of
+    the bank's source format, read to its end in blocks of `block` samples (a one-row bank: a DC blocker in front of a
+    detector), or any iterable of blocks the bank takes as they are -- demodulator_blocks(...) into a bank of
+    IIR_REAL_F32 rows (de-emphasis, a squelch smoother).  One output per input and nothing to flush: concatenated
+    along the last axis, the whole filtered stream at the input's rate."""
+    yield from _pushed_rows(src, bank, block, lambda fmt: bank.kind != fmt)
 
 
 # ---- a Reader, or a chain's blocks, through the symbol-timing recovery bank (include/hzsdr_symsync.h) ----
@@ -986,21 +994,7 @@ def symbol_rows(src, bank, block=READER_BLOCK):
     QPSK carrier), or any iterable of blocks the bank takes as they are -- iir_rows(demodulator_blocks(...)) into a bank
     of SYMSYNC_REAL_F32 rows.  Row r of a push holds counts[r] symbols; bank.ragged(symbols, counts) cuts them.  The
     loop's state carries from block to block and there is nothing to flush."""
-    if isinstance(src, Reader):
-        if bank.kind != src.sample_format():
-            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
-        buf = make_samples(src.sample_format(), block)
-        while True:
-            try:
-                k = src.read(buf)
-            except EOF:
-                break
-            if k:
-                yield bank.push(buf[:k])
-        return
-    for b in src:
-        if b.shape[-1]:
-            yield bank.push(b)
+    yield from _pushed_rows(src, bank, block, lambda fmt: bank.kind != fmt)
 
 
 # ---- a Reader, or a tuner's blocks, through the carrier recovery bank (include/hzsdr_carrier.h) ----
@@ -1011,21 +1005,7 @@ def carrier_rows(src, bank, block=READER_BLOCK):
     pilot), or any iterable of complex64 blocks the bank takes as they are -- the rows of tuner_rows(...), say; the
     blocks go on into symbol_rows(...).  One output per input; the loop's state carries from block to block and there is
     nothing to flush."""
-    if isinstance(src, Reader):
-        if src.sample_format() != FMT_C64:
-            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
-        buf = make_samples(src.sample_format(), block)
-        while True:
-            try:
-                k = src.read(buf)
-            except EOF:
-                break
-            if k:
-                yield bank.push(buf[:k])
-        return
-    for b in src:
-        if b.shape[-1]:
-            yield bank.push(b)
+    yield from _pushed_rows(src, bank, block, lambda fmt: fmt != FMT_C64)
 
 
 # ---- a Reader, or a tuner's blocks, through the AGC bank (include/hzsdr_agc.h) ----
@@ -1036,21 +1016,7 @@ def agc_rows(src, bank, block=READER_BLOCK):
     blocks the bank takes as they are -- the rows of tuner_rows(...) or demod_rows(...), say; the blocks go on into
     carrier_rows(...) and symbol_rows(...).  One output per input; the gains carry from block to block and there is
     nothing to flush."""
-    if isinstance(src, Reader):
-        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
-            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
-        buf = make_samples(src.sample_format(), block)
-        while True:
-            try:
-                k = src.read(buf)
-            except EOF:
-                break
-            if k:
-                yield bank.push(buf[:k])
-        return
-    for b in src:
-        if b.shape[-1]:
-            yield bank.push(b)
+    yield from _pushed_rows(src, bank, block, lambda fmt: fmt != FMT_C64 or bank.kind != FMT_C64)
 
 
 # ---- a Reader, or a symbol-timing bank's pushes, through the frame sync bank (include/hzsdr_framesync.h) ----

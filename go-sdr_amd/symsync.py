@@ -24,7 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import ErrInvalidArgument, _is_torch, lib
-from ._rows import cut, rows_input, rows_output
+from ._rows import RowWaveBank, cut, rows_input, rows_output
 from ._capi import SYMSYNC_FORM_COMPLEX, SYMSYNC_FORM_PER_ROW, SYMSYNC_MAX_ROWS, SYMSYNC_REAL_F32
 
 _PF = C.POINTER(C.c_float)
@@ -44,21 +44,22 @@ def loop_gains(sps, alpha=0.06, ted_gain=2.7):
     return g_mu, g_mu * alpha / 4.0
 
 
-class SymbolSync:
+class SymbolSync(RowWaveBank):
     """hzsdr_symsync: push(rows) -> (symbols, counts).  `kind` is SYMSYNC_REAL_F32 (float32 in and out) or FMT_C64
     (complex64 in and out).  One row takes (n,) samples; `rows` = R > 1 takes (R, n) with unit stride along a row and
     any row pitch.  `params` is float32 (4,) -- sps, limit, g_mu, g_omega -- shared by all rows, or (R, 4), one set per
     row.  numpy in a HOST context; torch tensors on the context's device, written on the context's stream, in a DEVICE
     context (counts are int32 there: the same bits as the ABI's uint32)."""
 
+    _c, _noun = "symsync", "symbol sync"
+    _state_msg = "the state is (rows, 8), or (rows, 13) for complex rows"
+
     def __init__(self, ctx, kind, params, rows=1):
-        self.ctx, self.kind, self.rows = ctx, int(kind), int(rows)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("symbol sync: rows is at least 1")
+        self.kind = int(kind)
+        self._open(ctx, rows)
         self.params = self._check(params, None)
         self.per_row = self.params.ndim == 2
         self.complex = self.kind != SYMSYNC_REAL_F32
-        self._h = C.c_void_p()
         ctx._ck(lib.hzsdr_symsync_create(ctx._h, self.kind, self.params.ctypes.data_as(_PF), int(self.per_row), self.rows, C.byref(self._h)))
 
     def _check(self, params, like):
@@ -71,20 +72,12 @@ class SymbolSync:
 
     def plan(self):
         """(rows per wave, samples per tile, form): the form is a sum of SYMSYNC_FORM_PER_ROW and SYMSYNC_FORM_COMPLEX."""
-        g, t, f = C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_symsync_plan(self._h, C.byref(g), C.byref(t), C.byref(f)))
-        return g.value, t.value, f.value
-
-    def position(self):
-        """Samples consumed per row."""
-        p = C.c_uint64(0)
-        self.ctx._ck(lib.hzsdr_symsync_position(self._h, C.byref(p)))
-        return p.value
+        return self._plan()
 
     def max_symbols(self, n):
         """The most symbols a push of n samples writes into one row."""
         b = C.c_size_t(0)
-        self.ctx._ck(lib.hzsdr_symsync_max_symbols(self._h, int(n), C.byref(b)))
+        self._call("max_symbols", int(n), C.byref(b))
         return b.value
 
     def push(self, samples, out=None, counts=None):
@@ -110,7 +103,7 @@ class SymbolSync:
             ok, cptr = counts.dtype == np.uint32 and counts.flags.c_contiguous and counts.shape == (self.rows,), counts.ctypes.data
         if not ok:
             raise ValueError("symbol sync: counts are (rows,) contiguous uint32 (numpy) or int32 (torch) values")
-        self.ctx._ck(lib.hzsdr_symsync_push(self._h, ptr, n, pitch, optr if cap else None, cap, opitch, cptr, None))
+        self._call("push", ptr, n, pitch, optr if cap else None, cap, opitch, cptr, None)
         return cut(out, self.rows, bound), counts
 
     def ragged(self, symbols, counts):
@@ -124,7 +117,7 @@ class SymbolSync:
     def set_params(self, params):
         """Exchange the parameters (same shape) between two pushes; the state and the position stay."""
         p = self._check(params, self.params)
-        self.ctx._ck(lib.hzsdr_symsync_set_params(self._h, p.ctypes.data_as(_PF)))
+        self._call("set_params", p.ctypes.data_as(_PF))
         self.params = p
 
     def _state_shape(self):
@@ -134,29 +127,7 @@ class SymbolSync:
         """(z, position): z is float32 (rows, 8) for real rows -- c, h, flag, y_prev, y_mid, x1, x2, x3 -- and
         (rows, 13) for complex rows, the five sample-valued entries as (re, im) pairs; behind every push so far.
         2 * z[:, 1] is the measured symbol period in samples."""
-        z = np.empty(self._state_shape(), np.float32)
-        self.ctx._ck(lib.hzsdr_symsync_get_state(self._h, z.ctypes.data_as(_PF), z.size))
-        return z, self.position()
-
-    def set_state(self, z, position=0):
-        z = np.ascontiguousarray(z, np.float32)
-        if z.shape != self._state_shape():
-            raise ErrInvalidArgument("symbol sync: the state is (rows, 8), or (rows, 13) for complex rows")
-        self.ctx._ck(lib.hzsdr_symsync_set_state(self._h, z.ctypes.data_as(_PF), z.size, int(position)))
-
-    def reset(self):
-        self.ctx._ck(lib.hzsdr_symsync_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib.hzsdr_symsync_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        return self._state()
 
 
 __all__ = ["SymbolSync", "loop_gains", "SYMSYNC_REAL_F32", "SYMSYNC_FORM_PER_ROW", "SYMSYNC_FORM_COMPLEX", "SYMSYNC_MAX_ROWS"]
