@@ -9,6 +9,7 @@
 #include "hz_device.h"
 #include "hz_fft.h"
 #include "hz_fftv.h"
+#include "hz_chain_fir_plan.h"
 #include "hz_nco.h"
 
 namespace hz {
@@ -909,12 +910,7 @@ __global__ __launch_bounds__(64 * W) void conv_blocks_shared_kernel(const typena
 struct LateFilters {
     const float2 *h[kNcoMaxSegs];
 };
-// the blocks of a run that do NOT take the late path, ascending (host: slow_blocks)
-constexpr int kMaxSlowBlocks = 96;
-struct SlowBlocks {
-    int n;
-    unsigned idx[kMaxSlowBlocks];
-};
+// (SlowBlocks, the blocks of a run that do NOT take the late path: hz_chain_fir_plan.h)
 
 // POLYPHASE form of the folded analysis (N = 4096, D in {2, 4, 8, 16}).  The fold sums the
 // D aliases of every output bin, sum_q H[k + M q] X[k + M q] (M = N/D).  Writing the

@@ -613,35 +613,11 @@ static void slow_blocks(const hzsdr_chain *c, const EwProgram &P, const LateFilt
                         size_t nblocks, SlowBlocks *out) {
     out->n = 0;
     if (diag_env().no_slow_first) return;  // measurement aid (tools/wrap_probe.py): stream order
-    const int64_t N = c->nfft, hop = c->hop, off = c->off;
-    std::vector<unsigned> v;
-    auto add_range = [&](int64_t lo, int64_t hi) {  // blocks lo .. hi inclusive, clipped
-        if (lo < 0) lo = 0;
-        if (hi >= (int64_t)nblocks) hi = (int64_t)nblocks - 1;
-        for (int64_t b = lo; b <= hi && v.size() <= (size_t)kMaxSlowBlocks; b++) v.push_back((unsigned)b);
-    };
-    // every block whose span contains a sample of [s_lo, s_hi]: b*hop - off <= s_hi and b*hop - off + N > s_lo
-    auto touching = [&](int64_t s_lo, int64_t s_hi) {
-        int64_t lo = s_lo + off - N;            // b*hop > lo
-        lo = lo < 0 ? 0 : lo / hop + 1;
-        add_range(lo, (s_hi + off) / hop);
-    };
-    // stream edges: spans that start before sample 0 (b*hop < off) or end after n - off (b*hop > n - N)
-    if (off > 0) add_range(0, (off - 1) / hop);
-    add_range((int64_t)n >= N ? ((int64_t)n - N) / hop + 1 : 0, (int64_t)nblocks - 1);
+    // (the list itself is host-only code: hz_chain_fir_plan.h, sanitizer-built in tests/host/)
     const int nr = P.segs.n > 0 ? P.segs.n : 1;
-    for (int r = 0; r < nr; r++) {
-        const int64_t first = P.segs.n > 0 ? (int64_t)P.segs.first[r] : 0;
-        const int64_t end = (P.segs.n > 0 && r + 1 < P.segs.n) ? (int64_t)P.segs.first[r + 1] : (int64_t)n;
-        if (late.h[r] == nullptr) touching(first, end - 1);      // a run without a filter: every block in it
-        else if (r > 0) touching(first - 1, first);              // a boundary: the blocks that straddle it
-        if (v.size() > (size_t)kMaxSlowBlocks) return;
-    }
-    std::sort(v.begin(), v.end());
-    v.erase(std::unique(v.begin(), v.end()), v.end());
-    if (v.size() > (size_t)kMaxSlowBlocks) return;
-    out->n = (int)v.size();
-    for (size_t i = 0; i < v.size(); i++) out->idx[i] = v[i];
+    bool has_filter[kNcoMaxSegs];
+    for (int r = 0; r < nr; r++) has_filter[r] = late.h[r] != nullptr;
+    slow_blocks_plan(c->nfft, c->hop, c->off, n, nblocks, P.segs.n, P.segs.first, has_filter, out);
     if (diag_env().debug_late) {
         int nh = 0;
         for (int r = 0; r < nr; r++) nh += late.h[r] != nullptr;
@@ -839,21 +815,10 @@ int hzsdr_chain_fir_decimate(hzsdr_chain *c, const float *taps, size_t n_taps, u
     HZ_TRY(chain_terminal_set(c));
     hzsdr_ctx *ctx = c->ctx;
     if (!taps || n_taps == 0 || factor == 0) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chain: fir taps / factor");
-    // N_fft = next power of two >= 4 * taps, in [N_min, 8192].  N_min is the smallest size at which the
-    // fast forms of the kernels apply: the late mixer needs one block per workgroup (N >= 1024) and
-    // the polyphase analysis N / D >= 256 for D = 2, 4, 8, 16.  Measured on 2^24 u8 samples (us per
-    // chain_run, N_min = 256 as in round 1 -> now): D = 8, 64 taps 152 -> 43, 256 taps 71 -> 45;
-    // D = 16, 256 taps 69 -> 41; D = 4, 128 taps 167 -> 54; D = 2, 64 taps 157 -> 78.
-    // (hzsdr_chain_fir_options' nfft_min overrides N_min: the measurement aid those numbers come from.)
-    unsigned nfft = 1024;
-    if (factor == 2 || factor == 4 || factor == 8 || factor == 16) nfft = std::max(1024u, 256u * factor);
-    if (c->fir_nfft_min) nfft = c->fir_nfft_min;
-    if (nfft < 256 || nfft > 8192 || (nfft & (nfft - 1))) nfft = 1024;
-    while (nfft < 4 * n_taps && nfft < 8192) nfft <<= 1;
-    unsigned off = (unsigned)(n_taps - 1);
-    off = (off + factor - 1) / factor * factor;  // first valid output on the decimation grid
-    if (off + factor > nfft) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chain: too many taps for the 8192-point overlap-save block");
-    unsigned hop = (nfft - off) / factor * factor;
+    // (the block's geometry: hz_chain_fir_plan.h)
+    const FirGeom geom = fir_geometry(n_taps, factor, c->fir_nfft_min);
+    if (!geom.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chain: too many taps for the 8192-point overlap-save block");
+    const unsigned nfft = geom.nfft, off = geom.off, hop = geom.hop;
     HZ_TRY(enter(ctx));
     const size_t hb = (size_t)(off ? off : 1) * 8;
     c->ntaps = n_taps;
