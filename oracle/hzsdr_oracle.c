@@ -538,6 +538,12 @@ int orc_sincos_narrow(double x, float *sn, float *cs) {
     return ds > 256u && dc > 256u;
 }
 
+/* orc_go_sincos over xs[0..n) (the tests' numpy restatements of the Shift factor) */
+void orc_go_sincos_n(const double *xs, double *sn, double *cs, long n) {
+    for (long i = 0; i < n; i++)
+        orc_go_sincos(xs[i], &sn[i], &cs[i]);
+}
+
 /* Over xs[0..n): how many arguments the check accepts, and how many of THOSE differ from complex64(math.Sincos)
  * in any bit (must be 0); the caller keeps |x| inside [2^-60, 2^29) or x = +-0, as the kernel does. */
 void orc_sincos_narrow_check(const double *xs, long n, long *accepted, long *wrong) {

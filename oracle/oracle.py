@@ -137,13 +137,7 @@ def go_sincos(x):
     x = np.ascontiguousarray(x, np.float64)
     s = np.empty_like(x)
     c = np.empty_like(x)
-    fn = lib().orc_go_sincos
-    sv, cv = C.c_double(), C.c_double()
-    flat = x.ravel()
-    so, co = s.ravel(), c.ravel()
-    for i in range(flat.size):
-        fn(C.c_double(flat[i]), C.byref(sv), C.byref(cv))
-        so[i], co[i] = sv.value, cv.value
+    lib().orc_go_sincos_n(_p(x), _p(s), _p(c), C.c_long(x.size))
     return s, c
 
 
