@@ -489,6 +489,14 @@ class Context:
         from .viterbi import ViterbiDecoder
         return ViterbiDecoder(self, kind, K, gens, data_bits, inv, pattern, termination, scale, crc, rows)
 
+    def reed_solomon(self, code, interleave=1, in_map=None, out_map=None, scramble=None, rows=1):
+        """The Reed-Solomon decoder bank (include/hzsdr_rs.h, rs.ReedSolomon): frames of `interleave` symbol-interleaved
+        codewords of `code` = (gfpoly, fcr, prim, nroots, n) -- CCSDS_RS_255_223, CCSDS_RS_255_239, DVB_RS_204_188 -- the
+        Viterbi bank's (or the frame sync bank's) frames as they are, descrambled by `scramble` and mapped by `in_map`,
+        to corrected data bytes through `out_map` and a verdict per frame, over `rows` rows of frames."""
+        from .rs import ReedSolomon
+        return ReedSolomon(self, code, interleave, in_map, out_map, scramble, rows)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -942,6 +950,9 @@ from .framesync import FrameSync, pack_bits, sync_hypotheses, unpack_bits  # noq
 from ._capi import (VITERBI_BITS, VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH, VITERBI_MAX_BITS, VITERBI_MAX_FRAMES, VITERBI_MAX_K,  # noqa: E402
                     VITERBI_MAX_PATTERN, VITERBI_MAX_RATE, VITERBI_MAX_ROWS, VITERBI_MIN_K, VITERBI_SOFT_F32, VITERBI_TAIL, VITERBI_TRUNCATED)
 from .viterbi import CCSDS_K7, ViterbiDecoder, conv_encode, crc_register, puncture_pattern  # noqa: E402
+from ._capi import (RS_MAX_FRAMES, RS_MAX_INTERLEAVE, RS_MAX_N, RS_MAX_ROOTS, RS_MAX_ROWS, RS_MAX_SCRAMBLE, RS_MIN_ROOTS)  # noqa: E402
+from .rs import (CCSDS_RS_255_223, CCSDS_RS_255_239, DVB_RS_204_188, ReedSolomon, ccsds_dual_basis, ccsds_randomizer, interleave_codewords,  # noqa: E402
+                 rs_encode, rs_generator)
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

@@ -382,10 +382,21 @@ VITERBI_BITS, VITERBI_SOFT_F32 = 1, 32
 VITERBI_TAIL, VITERBI_TRUNCATED = 0, 1
 VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_rs.h declares
+RS_SIGNATURES = {
+    "hzsdr_rs_create": (i32, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, sz, sz, pvp]),
+    "hzsdr_rs_decode": (i32, [vp, vp, sz, sz, vp, sz, vp, sz, sz, vp]),
+    "hzsdr_rs_sizes": (i32, [vp, psz, psz, psz, psz]),
+    "hzsdr_rs_plan": (i32, [vp, psz, psz, psz, psz]),
+    "hzsdr_rs_free": (i32, [vp]),
+}
+RS_MAX_ROWS, RS_MIN_ROOTS, RS_MAX_ROOTS, RS_MAX_N, RS_MAX_INTERLEAVE, RS_MAX_SCRAMBLE, RS_MAX_FRAMES = 8192, 2, 64, 255, 8, 2040, 1 << 22
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
-                             *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items()):
+                             *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items(),
+                             *RS_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -37,6 +37,7 @@
 #include "../../include/hzsdr_agc.h"
 #include "../../include/hzsdr_framesync.h"
 #include "../../include/hzsdr_viterbi.h"
+#include "../../include/hzsdr_rs.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1570,6 +1571,86 @@ private:
     size_t rows_;
     size_t n_ = 0, fb_ = 0, t_ = 0, db_ = 0;
     hzsdr_viterbi *v_ = nullptr;
+};
+
+// The Reed-Solomon decoder bank (include/hzsdr_rs.h): frames of `interleave` symbol-interleaved codewords over GF(2^8) --
+// the Viterbi bank's decoded frames as they are -- to corrected data bytes and a verdict per frame, over `rows` rows of
+// `cap` frame slots.  Decode runs min(in_counts[r], cap) frames of every row (row r starts r * in_stride bytes into `in`,
+// frame f of it f * in_pitch bytes further; dense rows and slots when they are 0; every row has cap frames when in_counts
+// is null).  The bank keeps no state.
+class ReedSolomon {
+public:
+    struct Frame {
+        std::vector<uint8_t> bytes;  // the I k data bytes, corrected where the codeword did not fail
+        uint32_t errors, failed;     // symbols corrected over the frame's decoded codewords; codewords that failed
+        bool ok;                     // failed == 0
+    };
+    struct Config {
+        unsigned gfpoly = 0x187, fcr = 112, prim = 11, nroots = 32, n = 255;  // CCSDS 255/223
+        unsigned interleave = 1;
+        std::vector<uint8_t> in_map, out_map;  // empty: identity; else 256 bytes
+        std::vector<uint8_t> scramble;         // empty: none
+    };
+    ReedSolomon(const Context &x, const Config &c, size_t rows = 1) : x_(x), rows_(rows) {
+        if ((!c.in_map.empty() && c.in_map.size() != 256) || (!c.out_map.empty() && c.out_map.size() != 256))
+            throw std::invalid_argument("ReedSolomon: a map is 256 bytes");
+        check(x_.raw(), hzsdr_rs_create(x_.raw(), c.gfpoly, c.fcr, c.prim, c.nroots, c.n, c.interleave, c.in_map.empty() ? nullptr : c.in_map.data(),
+                                        c.out_map.empty() ? nullptr : c.out_map.data(), c.scramble.empty() ? nullptr : c.scramble.data(), c.scramble.size(),
+                                        rows, &r_));
+        check(x_.raw(), hzsdr_rs_sizes(r_, &k_, &t_, &fb_, &db_));
+    }
+    ~ReedSolomon() { if (r_) hzsdr_rs_free(r_); }
+    ReedSolomon(const ReedSolomon &) = delete;
+    ReedSolomon &operator=(const ReedSolomon &) = delete;
+    std::vector<std::vector<Frame>> Decode(const uint8_t *in, size_t cap, size_t in_stride = 0, size_t in_pitch = 0, const uint32_t *in_counts = nullptr) {
+        std::vector<uint8_t> out(rows_ * cap * db_);
+        std::vector<uint32_t> info(rows_ * cap);
+        const size_t pitch = in_pitch ? in_pitch : fb_;
+        check(x_.raw(), hzsdr_rs_decode(r_, in, in_stride ? in_stride : cap * pitch, pitch, in_counts, cap, out.data(), cap * db_, db_, info.data()));
+        std::vector<std::vector<Frame>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            const size_t k = in_counts && in_counts[r] < cap ? in_counts[r] : cap;
+            for (size_t f = 0; f < k; f++) {
+                const uint8_t *p = out.data() + (r * cap + f) * db_;
+                const uint32_t w = info[r * cap + f];
+                rows[r].push_back({std::vector<uint8_t>(p, p + db_), w & 0xffffu, (w >> 16) & 0x7fffu, (w >> 31) != 0});
+            }
+        }
+        return rows;
+    }
+    // what Viterbi::Decode returned, frame for frame (a frame's bytes are the bank's frame bytes)
+    std::vector<std::vector<Frame>> Decode(const std::vector<std::vector<Viterbi::Frame>> &frames) {
+        if (frames.size() != rows_) throw std::invalid_argument("ReedSolomon: a list of frames per row");
+        size_t cap = 1;
+        for (const auto &row : frames) cap = row.size() > cap ? row.size() : cap;
+        std::vector<uint8_t> in(rows_ * cap * fb_, 0);
+        std::vector<uint32_t> counts(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            counts[r] = (uint32_t)frames[r].size();
+            for (size_t f = 0; f < frames[r].size(); f++) {
+                if (frames[r][f].bytes.size() != fb_) throw std::invalid_argument("ReedSolomon: a frame of another size");
+                std::copy(frames[r][f].bytes.begin(), frames[r][f].bytes.end(), in.begin() + (r * cap + f) * fb_);
+            }
+        }
+        return Decode(in.data(), cap, 0, 0, counts.data());
+    }
+    // -> (waves per workgroup, LDS bytes per workgroup, workgroups a compute unit holds, workgroups of a call at most)
+    std::tuple<size_t, size_t, size_t, size_t> Plan() const {
+        size_t w = 0, l = 0, c = 0, g = 0;
+        check(x_.raw(), hzsdr_rs_plan(r_, &w, &l, &c, &g));
+        return {w, l, c, g};
+    }
+    size_t Rows() const { return rows_; }
+    size_t DataSymbols() const { return k_; }
+    size_t Correctable() const { return t_; }
+    size_t FrameBytes() const { return fb_; }
+    size_t DataBytes() const { return db_; }
+
+private:
+    const Context &x_;
+    size_t rows_;
+    size_t k_ = 0, t_ = 0, fb_ = 0, db_ = 0;
+    hzsdr_rs *r_ = nullptr;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

@@ -1053,7 +1053,7 @@ def frame_rows(src, bank, cap=4, block=READER_BLOCK):
 
 # ---- frame_rows with the Viterbi decoder bank behind the frame sync bank (include/hzsdr_viterbi.h) ----
 
-def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK):
+def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None):
     """Push `src` through `bank` (a framesync.FrameSync) as frame_rows does and decode every push's frames with
     `decoder` (a viterbi.ViterbiDecoder of VITERBI_BITS input over the same rows, whose received positions N are the
     bank's payload bits).  The frame block and its counts go from the one bank to the other as they are, in the
@@ -1066,10 +1066,12 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK):
     def push(symbols, counts=None):
         frames, positions, info, got = bank.push(symbols, counts, cap)
         data, verdict = decoder.decode(frames, got, cap)
+        more = None if _behind is None else _behind(data, got, cap)  # (corrected_frames: launched before anything is read)
         if int(got.max()) > cap:
             raise ErrShortBuffer("sdr: a row accepted more frames in one push than decoded_frames keeps")
         found = bank.ragged(frames, positions, info, got)
-        return [(d, p, i, m, ok) for (_, p, i), (d, m, ok) in zip(found, decoder.ragged(data, verdict, got))]
+        rows = [(d, p, i, m, ok) for (_, p, i), (d, m, ok) in zip(found, decoder.ragged(data, verdict, got))]
+        return rows if more is None else more(rows)
     if isinstance(src, Reader):
         if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
             raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
@@ -1086,6 +1088,25 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK):
         symbols, counts = b if isinstance(b, tuple) else (b, None)
         if symbols.shape[-1]:
             yield push(symbols, counts)
+
+
+# ---- decoded_frames with the Reed-Solomon decoder bank behind the Viterbi bank (include/hzsdr_rs.h) ----
+
+def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK):
+    """decoded_frames with `rs` (an rs.ReedSolomon over the same rows whose frame bytes are the decoder's data bytes)
+    behind the Viterbi decoder: the decoded block and the counts go on to it as they are, in the context's memory space,
+    with nothing read in between.  Yields, per push, a list of `rows` tuples (data (k, I k) uint8 -- the corrected data
+    bytes --, positions (k,), sync info (k,), metric (k,), crc_ok (k,), E (k,), nfail (k,), ok (k,))."""
+    if rs.rows != decoder.rows or rs.frame_bytes != decoder.data_bytes or decoder.D != 8 * rs.frame_bytes:
+        raise ValueError("sdr: the Reed-Solomon bank's rows and frame bytes are the decoder's rows and data bytes")
+
+    def behind(data, got, cap):
+        clean, verdict = rs.decode(data, got, cap)
+
+        def read(rows):
+            return [(c, p, i, m, ok, e, nf, good) for (_, p, i, m, ok), (c, e, nf, good) in zip(rows, rs.ragged(clean, verdict, got))]
+        return read
+    return decoded_frames(src, bank, decoder, cap, block, _behind=behind)
 
 
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
