@@ -497,6 +497,16 @@ class Context:
         from .rs import ReedSolomon
         return ReedSolomon(self, code, interleave, in_map, out_map, scramble, rows)
 
+    def soft_frames(self, framesync):
+        """The soft frame bank (include/hzsdr_softframe.h, softframe.SoftFrames) beside `framesync` (a
+        framesync.FrameSync): the same kind, bits per symbol, payload bits, maps and rows.  Its push takes the frame sync
+        push's symbols, counts, positions, info and frame counts as they are and writes every frame's payload floats in
+        the layout the Viterbi bank's VITERBI_SOFT_F32 input reads.  A bank with diff != 0 has no soft counterpart."""
+        from .softframe import SoftFrames
+        if framesync.diff != 0:
+            raise ValueError("soft frames: a frame sync bank with a differential decoding has no soft counterpart")
+        return SoftFrames(self, framesync.kind, framesync.P, framesync.maps, framesync.B, framesync.rows)
+
     def channel_bank(self, src_fmt, channels, taps, hop=None, order=None, layout="frames"):
         """The channel bank (include/hzsdr_chanbank.h, chanbank.ChannelBank): the polyphase channelizer for the small
         channel counts, any `channels` from 2 to 255, out of a stream of src_fmt samples with the prototype `taps`
@@ -953,6 +963,9 @@ from .viterbi import CCSDS_K7, ViterbiDecoder, conv_encode, crc_register, punctu
 from ._capi import (RS_MAX_FRAMES, RS_MAX_INTERLEAVE, RS_MAX_N, RS_MAX_ROOTS, RS_MAX_ROWS, RS_MAX_SCRAMBLE, RS_MIN_ROOTS)  # noqa: E402
 from .rs import (CCSDS_RS_255_223, CCSDS_RS_255_239, DVB_RS_204_188, ReedSolomon, ccsds_dual_basis, ccsds_randomizer, interleave_codewords,  # noqa: E402
                  rs_encode, rs_generator)
+from ._capi import (SOFTFRAME_FORM_COMPLEX, SOFTFRAME_FORM_DIBIT, SOFTFRAME_MAX_HYPOTHESES, SOFTFRAME_MAX_PAYLOAD, SOFTFRAME_MAX_ROWS,  # noqa: E402
+                    SOFTFRAME_MAX_SLOTS, SOFTFRAME_NO_HYPOTHESIS, SOFTFRAME_OUTSIDE, SOFTFRAME_SERVED)
+from .softframe import SoftFrames  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

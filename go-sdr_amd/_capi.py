@@ -392,11 +392,26 @@ RS_SIGNATURES = {
 }
 RS_MAX_ROWS, RS_MIN_ROOTS, RS_MAX_ROOTS, RS_MAX_N, RS_MAX_INTERLEAVE, RS_MAX_SCRAMBLE, RS_MAX_FRAMES = 8192, 2, 64, 255, 8, 2040, 1 << 22
 
+# name -> (restype, argtypes); every symbol include/hzsdr_softframe.h declares
+SOFTFRAME_SIGNATURES = {
+    "hzsdr_softframe_create": (i32, [vp, i32, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint), sz, pvp]),
+    "hzsdr_softframe_push": (i32, [vp, vp, sz, sz, vp, vp, vp, vp, sz, vp, sz, vp]),
+    "hzsdr_softframe_get_state": (i32, [vp, C.POINTER(u64), C.POINTER(f32), sz]),
+    "hzsdr_softframe_set_state": (i32, [vp, C.POINTER(u64), C.POINTER(f32), sz]),
+    "hzsdr_softframe_positions": (i32, [vp, C.POINTER(u64), sz]),
+    "hzsdr_softframe_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_softframe_reset": (i32, [vp]),
+    "hzsdr_softframe_free": (i32, [vp]),
+}
+SOFTFRAME_MAX_ROWS, SOFTFRAME_MAX_PAYLOAD, SOFTFRAME_MAX_HYPOTHESES, SOFTFRAME_MAX_SLOTS = 8192, 8192, 4, 1 << 22
+SOFTFRAME_SERVED, SOFTFRAME_OUTSIDE, SOFTFRAME_NO_HYPOTHESIS = 0, 1, 2
+SOFTFRAME_FORM_COMPLEX, SOFTFRAME_FORM_DIBIT = 1, 2
+
 for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), *CHANNELIZER_SIGNATURES.items(),
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
                              *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items(),
-                             *RS_SIGNATURES.items()):
+                             *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

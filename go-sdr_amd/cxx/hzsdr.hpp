@@ -38,6 +38,7 @@
 #include "../../include/hzsdr_framesync.h"
 #include "../../include/hzsdr_viterbi.h"
 #include "../../include/hzsdr_rs.h"
+#include "../../include/hzsdr_softframe.h"
 #include "../../include/hzsdr_spectrum.h"
 #include "../../include/hzsdr_synthesizer.h"
 
@@ -1714,6 +1715,91 @@ private:
     const Context &x_;
     size_t tuners_, qp_;
     hzsdr_tuner *t_ = nullptr;
+};
+
+// The soft frame bank (include/hzsdr_softframe.h) beside a FrameSync of the same kind, configuration and rows: Push takes
+// the symbols that FrameSync::Push got and the frames it returned and gives, frame for frame, the payload's floats through
+// the frame's hypothesis map -- what a Viterbi of HZSDR_VITERBI_SOFT_F32 input reads -- and a status
+// (HZSDR_SOFTFRAME_SERVED for every frame the FrameSync emitted in the same push).  A FrameSync configuration with a
+// differential decoding has no soft counterpart and is refused.
+class SoftFrames {
+public:
+    struct Frame {
+        std::vector<float> values;  // float k decides payload bit k: sign bit clear means 1
+        uint32_t status;
+    };
+    SoftFrames(const Context &x, int kind, const FrameSync::Config &c, size_t rows = 1) : x_(x), rows_(rows), p_(c.payload_bits) {
+        if (c.diff != 0) throw std::invalid_argument("SoftFrames: a differential decoding has no soft counterpart");
+        if (c.maps.empty()) throw std::invalid_argument("SoftFrames: at least one map");
+        check(x_.raw(), hzsdr_softframe_create(x_.raw(), kind, c.bits_per_symbol, c.payload_bits, (unsigned)c.maps.size(), c.maps.data(), rows, &f_));
+    }
+    ~SoftFrames() { if (f_) hzsdr_softframe_free(f_); }
+    SoftFrames(const SoftFrames &) = delete;
+    SoftFrames &operator=(const SoftFrames &) = delete;
+    // the arrays of hzsdr_framesync_push as they are
+    void Push(const void *in, size_t n, size_t in_stride, const uint32_t *in_counts, const uint64_t *positions, const uint32_t *info,
+              const uint32_t *counts, size_t cap, float *out, size_t out_stride, uint32_t *status) {
+        check(x_.raw(), hzsdr_softframe_push(f_, n ? in : nullptr, n, in_stride ? in_stride : n, in_counts, positions, info, counts, cap, out, out_stride, status));
+    }
+    // what FrameSync::Push(in, n, in_stride, in_counts, ...) returned, frame for frame
+    std::vector<std::vector<Frame>> Push(const void *in, size_t n, const std::vector<std::vector<FrameSync::Frame>> &frames, size_t in_stride = 0,
+                                         const uint32_t *in_counts = nullptr) {
+        if (frames.size() != rows_) throw std::invalid_argument("SoftFrames: a list of frames per row");
+        size_t cap = 0;
+        for (const auto &row : frames) cap = row.size() > cap ? row.size() : cap;
+        std::vector<uint64_t> pos(rows_ * cap);
+        std::vector<uint32_t> info(rows_ * cap), counts(rows_), status(rows_ * cap);
+        std::vector<float> out(rows_ * cap * p_);
+        for (size_t r = 0; r < rows_; r++) {
+            counts[r] = (uint32_t)frames[r].size();
+            for (size_t f = 0; f < frames[r].size(); f++) {
+                pos[r * cap + f] = frames[r][f].position;
+                info[r * cap + f] = frames[r][f].distance | frames[r][f].hypothesis << 8;
+            }
+        }
+        Push(in, n, in_stride, in_counts, pos.data(), info.data(), counts.data(), cap, out.data(), cap * p_, status.data());
+        std::vector<std::vector<Frame>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++)
+            for (size_t f = 0; f < frames[r].size(); f++) {
+                const float *p = out.data() + (r * cap + f) * p_;
+                rows[r].push_back({std::vector<float>(p, p + p_), status[r * cap + f]});
+            }
+        return rows;
+    }
+    struct StateArrays {
+        std::vector<uint64_t> positions;
+        std::vector<float> history;  // rows * HistoryFloats(), oldest first
+    };
+    StateArrays State() const {
+        StateArrays z{std::vector<uint64_t>(rows_), std::vector<float>(rows_ * HistoryFloats())};
+        check(x_.raw(), hzsdr_softframe_get_state(f_, z.positions.data(), z.history.empty() ? nullptr : z.history.data(), rows_));
+        return z;
+    }
+    void SetState(const StateArrays &z) {
+        if (z.positions.size() != rows_ || z.history.size() != rows_ * HistoryFloats()) throw std::invalid_argument("SoftFrames: the state has an entry per row");
+        check(x_.raw(), hzsdr_softframe_set_state(f_, z.positions.data(), z.history.empty() ? nullptr : z.history.data(), rows_));
+    }
+    std::vector<uint64_t> Positions() const {
+        std::vector<uint64_t> p(rows_);
+        check(x_.raw(), hzsdr_softframe_positions(f_, p.data(), p.size()));
+        return p;
+    }
+    // -> (floats a workgroup moves per step, history floats per row, HZSDR_SOFTFRAME_FORM_*)
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t s = 0, h = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_softframe_plan(f_, &s, &h, &f));
+        return {s, h, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_softframe_reset(f_)); }
+    size_t Rows() const { return rows_; }
+    size_t PayloadBits() const { return p_; }
+    size_t HistoryFloats() const { return std::get<1>(Plan()); }
+
+private:
+    const Context &x_;
+    size_t rows_, p_;
+    hzsdr_softframe *f_ = nullptr;
 };
 }  // namespace stream
 

@@ -24,6 +24,7 @@ import numpy as np
 from . import (FMT_C64, FMT_I8, FMT_I16, FMT_U8, FFT_BACKWARD, FFT_FORWARD, Context, Ring,
                ErrDstTooSmall, ErrSampleFormatMismatch, ErrSampleFormatUnknown, HzsdrError,
                beamform_angles, beamform_angles_2d, fmt_of, format_size, length, make_samples)
+from ._capi import VITERBI_SOFT_F32
 
 READER_BLOCK = 32 * 1024  # stream/convert.go:43-44, decimate.go:41-42, downsample.go:54-55
 
@@ -1053,19 +1054,33 @@ def frame_rows(src, bank, cap=4, block=READER_BLOCK):
 
 # ---- frame_rows with the Viterbi decoder bank behind the frame sync bank (include/hzsdr_viterbi.h) ----
 
-def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None):
+def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, soft=None):
     """Push `src` through `bank` (a framesync.FrameSync) as frame_rows does and decode every push's frames with
     `decoder` (a viterbi.ViterbiDecoder of VITERBI_BITS input over the same rows, whose received positions N are the
     bank's payload bits).  The frame block and its counts go from the one bank to the other as they are, in the
     context's memory space, with nothing read in between.  Yields, per push, a list of `rows` tuples (data (k, DB) uint8,
     positions (k,), sync info (k,), metric (k,), crc_ok (k,)).  As in frame_rows, a row that accepted more than `cap`
-    frames in one push raises ErrShortBuffer."""
+    frames in one push raises ErrShortBuffer.
+    `soft`, when given, is a softframe.SoftFrames beside `bank` (Context.soft_frames(bank)) and `decoder` takes
+    VITERBI_SOFT_F32 input: every push runs frame sync -> soft frame bank -> decoder, and the decoder reads the frames'
+    payload floats (include/hzsdr_softframe.h) where it read their decided bits; the tuples are the same."""
     if decoder.rows != bank.rows or decoder.N != bank.P:
         raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
+    if soft is not None:
+        if soft.rows != bank.rows or soft.P != bank.P or soft.kind != bank.kind or soft.B != bank.B or list(soft.maps) != list(bank.maps):
+            raise ValueError("sdr: the soft frame bank's rows, kind, bits per symbol, payload bits and maps are the frame sync bank's")
+        if bank.diff != 0:
+            raise ValueError("sdr: a frame sync bank with a differential decoding has no soft counterpart")
+        if decoder.kind != VITERBI_SOFT_F32:
+            raise ValueError("sdr: behind a soft frame bank the decoder takes VITERBI_SOFT_F32 input")
 
     def push(symbols, counts=None):
         frames, positions, info, got = bank.push(symbols, counts, cap)
-        data, verdict = decoder.decode(frames, got, cap)
+        if soft is None:
+            data, verdict = decoder.decode(frames, got, cap)
+        else:
+            values, _ = soft.push(symbols, counts, positions, info, got, cap)
+            data, verdict = decoder.decode(values, got, cap)
         more = None if _behind is None else _behind(data, got, cap)  # (corrected_frames: launched before anything is read)
         if int(got.max()) > cap:
             raise ErrShortBuffer("sdr: a row accepted more frames in one push than decoded_frames keeps")
@@ -1092,11 +1107,12 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None):
 
 # ---- decoded_frames with the Reed-Solomon decoder bank behind the Viterbi bank (include/hzsdr_rs.h) ----
 
-def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK):
+def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK, soft=None):
     """decoded_frames with `rs` (an rs.ReedSolomon over the same rows whose frame bytes are the decoder's data bytes)
     behind the Viterbi decoder: the decoded block and the counts go on to it as they are, in the context's memory space,
     with nothing read in between.  Yields, per push, a list of `rows` tuples (data (k, I k) uint8 -- the corrected data
-    bytes --, positions (k,), sync info (k,), metric (k,), crc_ok (k,), E (k,), nfail (k,), ok (k,))."""
+    bytes --, positions (k,), sync info (k,), metric (k,), crc_ok (k,), E (k,), nfail (k,), ok (k,)).  `soft`: as in
+    decoded_frames."""
     if rs.rows != decoder.rows or rs.frame_bytes != decoder.data_bytes or decoder.D != 8 * rs.frame_bytes:
         raise ValueError("sdr: the Reed-Solomon bank's rows and frame bytes are the decoder's rows and data bytes")
 
@@ -1106,7 +1122,7 @@ def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK):
         def read(rows):
             return [(c, p, i, m, ok, e, nf, good) for (_, p, i, m, ok), (c, e, nf, good) in zip(rows, rs.ragged(clean, verdict, got))]
         return read
-    return decoded_frames(src, bank, decoder, cap, block, _behind=behind)
+    return decoded_frames(src, bank, decoder, cap, block, _behind=behind, soft=soft)
 
 
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------

@@ -12,8 +12,10 @@ not.  Soft values are quantised to -127 ... 127 by q = rint(clamp(x * scale)), a
 so that the metric of a hard frame is the number of channel bit errors corrected.  Row r decodes min(counts[r], cap)
 frames; the other slots of the destinations stay as they are.  Frames are independent and the bank keeps no state.
 
-Not here: tail-biting, one continuous stream across frames, soft outputs, bit unstuffing; descrambling and the outer
-Reed-Solomon code are the next bank's (include/hzsdr_rs.h, Context.reed_solomon: it takes data and counts as they are).
+Not here: tail-biting, one continuous stream across frames, soft outputs of the decoder, bit unstuffing; descrambling and
+the outer Reed-Solomon code are the next bank's (include/hzsdr_rs.h, Context.reed_solomon: it takes data and counts as
+they are).  The VITERBI_SOFT_F32 frames are what the soft frame bank writes (include/hzsdr_softframe.h,
+Context.soft_frames).
 """
 import ctypes as C
 

@@ -5,7 +5,8 @@
  * symbol-timing bank's (symbols, counts) as they are, on the device, and this is where the data rate falls from symbols
  * to packets -- where a receive chain hands over to the CPU.  What it leaves to others: decoding a convolutionally
  * coded payload and its CRC (hzsdr_viterbi.h takes `out` and `counts` as they are); descrambling, bit unstuffing and
- * every other word of a protocol; soft outputs; a sync word longer than 64 bits.
+ * every other word of a protocol; soft outputs (hzsdr_softframe.h runs beside this bank, takes `positions`, `info` and
+ * `counts` as they are and writes the frames' payload floats); a sync word longer than 64 bits.
  *
  * The entries live beside hzsdr.h and the other headers (same conventions, same status codes, same context).  The
  * reference has no frame sync: the definition below is the contract, restated under tests/ (tests/host/framesync_ref.cpp

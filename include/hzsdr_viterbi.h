@@ -4,8 +4,9 @@
  * hzsdr_tuner.h, hzsdr_iir.h, hzsdr_agc.h, hzsdr_carrier.h, hzsdr_symsync.h and hzsdr_framesync.h and stands behind the
  * last of them: it takes the frame sync bank's `out` block and its device-side `counts` as they are, with no host read in
  * between.  What it leaves to others: tail-biting codes; decoding ONE continuous coded stream across frame boundaries;
- * soft outputs; bit unstuffing; descrambling and the outer Reed-Solomon code of a concatenated link, which are the
- * Reed-Solomon decoder bank's (hzsdr_rs.h takes `out` and the counts as they are).
+ * soft outputs of the decoder; bit unstuffing; descrambling and the outer Reed-Solomon code of a concatenated link, which
+ * are the Reed-Solomon decoder bank's (hzsdr_rs.h takes `out` and the counts as they are).  The soft INPUT block
+ * (HZSDR_VITERBI_SOFT_F32) is what the soft frame bank writes beside the frame sync bank (hzsdr_softframe.h).
  *
  * The entries live beside hzsdr.h and the other headers (same conventions, same status codes, same context).  The
  * reference has no decoder: the definition below is the contract, restated under tests/ (tests/host/viterbi_ref.cpp over
