@@ -473,6 +473,15 @@ class Context:
         from .agc import Agc
         return Agc(self, kind, params, rows, per_row)
 
+    def equalizer(self, kind, mode, taps, centre, params, rows=1, per_row=False):
+        """The adaptive equalizer bank (include/hzsdr_equalizer.h, equalizer.Equalizer): a `taps`-tap linear equalizer at
+        the symbol rate over `rows` rows of `kind` (EQUALIZER_REAL_F32: float32 rows; FMT_C64: complex64 rows), adapted
+        blind (EQUALIZER_CMA) or on its own decisions (EQUALIZER_DD_BPSK, EQUALIZER_DD_QPSK), between the symbol-timing
+        bank and the frame sync bank.  At first tap `centre` is 1 and the others 0.  `params` is float32 (mu, level)
+        shared by all rows, or (rows, 2) with per_row."""
+        from .equalizer import Equalizer
+        return Equalizer(self, kind, mode, taps, centre, params, rows, per_row)
+
     def frame_sync(self, kind, word_bits, words, maps, payload_bits, bits_per_symbol=1, mask=None, thr=0, diff=0, holdoff=None, rows=1):
         """The frame sync bank (include/hzsdr_framesync.h, framesync.FrameSync): hard decisions, a search for a sync word
         of `word_bits` bits under the hypotheses (`words`, `maps`; framesync.sync_hypotheses builds them) and the
@@ -954,6 +963,9 @@ from ._capi import CARRIER_BPSK, CARRIER_FORM_MODE, CARRIER_FORM_PER_ROW, CARRIE
 from .carrier import CarrierLoop, carrier_gains  # noqa: E402
 from ._capi import AGC_FORM_COMPLEX, AGC_FORM_PER_ROW, AGC_MAX_ROWS, AGC_REAL_F32  # noqa: E402
 from .agc import Agc, agc_rates  # noqa: E402
+from ._capi import (EQUALIZER_CMA, EQUALIZER_DD_BPSK, EQUALIZER_DD_QPSK, EQUALIZER_FORM_COMPLEX, EQUALIZER_FORM_PER_ROW,  # noqa: E402
+                    EQUALIZER_MAX_ROWS, EQUALIZER_MAX_TAPS, EQUALIZER_REAL_F32)
+from .equalizer import Equalizer  # noqa: E402
 from ._capi import (FRAMESYNC_FORM_COMPLEX, FRAMESYNC_FORM_DIBIT, FRAMESYNC_FORM_DIFF, FRAMESYNC_MAX_HYPOTHESES,  # noqa: E402
                     FRAMESYNC_MAX_PAYLOAD, FRAMESYNC_MAX_ROWS, FRAMESYNC_MAX_WORD)
 from .framesync import FrameSync, pack_bits, sync_hypotheses, unpack_bits  # noqa: E402

@@ -354,6 +354,22 @@ AGC_REAL_F32 = 32  # (IIR_REAL_F32: one value names the real float32 rows all al
 AGC_MAX_ROWS = 8192
 AGC_FORM_PER_ROW, AGC_FORM_COMPLEX = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_equalizer.h declares
+EQUALIZER_SIGNATURES = {
+    "hzsdr_equalizer_create": (i32, [vp, i32, i32, sz, sz, C.POINTER(f32), i32, sz, pvp]),
+    "hzsdr_equalizer_push": (i32, [vp, vp, sz, sz, vp, vp, sz, vp, sz]),
+    "hzsdr_equalizer_set_params": (i32, [vp, C.POINTER(f32)]),
+    "hzsdr_equalizer_get_state": (i32, [vp, C.POINTER(f32), sz]),
+    "hzsdr_equalizer_set_state": (i32, [vp, C.POINTER(f32), sz]),
+    "hzsdr_equalizer_plan": (i32, [vp, psz, psz, C.POINTER(i32)]),
+    "hzsdr_equalizer_reset": (i32, [vp]),
+    "hzsdr_equalizer_free": (i32, [vp]),
+}
+EQUALIZER_REAL_F32 = 32  # (IIR_REAL_F32: one value names the real float32 rows all along the chain)
+EQUALIZER_MAX_ROWS, EQUALIZER_MAX_TAPS = 8192, 64
+EQUALIZER_CMA, EQUALIZER_DD_BPSK, EQUALIZER_DD_QPSK = 0, 1, 2
+EQUALIZER_FORM_PER_ROW, EQUALIZER_FORM_COMPLEX = 1, 2
+
 # name -> (restype, argtypes); every symbol include/hzsdr_framesync.h declares
 FRAMESYNC_SIGNATURES = {
     "hzsdr_framesync_create": (i32, [vp, i32, C.c_uint, C.c_uint, u64, C.c_uint, C.c_uint, C.POINTER(u64), C.POINTER(C.c_uint), C.c_uint, i32, u64, sz, pvp]),
@@ -411,7 +427,7 @@ for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), 
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
                              *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items(),
-                             *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items()):
+                             *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items(), *EQUALIZER_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -5,7 +5,8 @@ writes (R, count) rows likewise; one stream takes (n,) and writes (count,).  num
 the context's device in a DEVICE context.  The errors carry the calling class's noun.
 
 RowWaveBank is what the classes of the four row-wave banks (iir.IirBank, symsync.SymbolSync, carrier.CarrierLoop, agc.Agc)
-are built on: the object's life and the calls around its pushes (csrc/hz_loopbank.h is the same layer in C).
+are built on: the object's life and the calls around its pushes (csrc/hz_loopbank.h is the same layer in C).  The
+equalizer bank's class (equalizer.Equalizer) takes the object's life, plan and reset from it and has no position.
 """
 import ctypes as C
 

@@ -15,6 +15,8 @@
 //   check_kind(ctx, kind)        the status and message of a kind the bank does not have
 //   shape(f, kind)               kind, geometry and state words of the new object (ctx, R, per_row are set)
 //   initial(f, r, set, z)        row r's entries of the initial state z (+0 elsewhere) from parameter set `set`
+// The equalizer bank (hz_equalizer.hip), whose create takes a mode, a tap count and a centre beside the kind, has a create
+// of its own over stage_params, commit_params and initial_state, and a push of its own; the rest it takes from here.
 // Nothing here knows which bank it serves.
 #pragma once
 #include "hz_common.h"

@@ -35,6 +35,7 @@
 #include "../../include/hzsdr_symsync.h"
 #include "../../include/hzsdr_carrier.h"
 #include "../../include/hzsdr_agc.h"
+#include "../../include/hzsdr_equalizer.h"
 #include "../../include/hzsdr_framesync.h"
 #include "../../include/hzsdr_viterbi.h"
 #include "../../include/hzsdr_rs.h"
@@ -1397,6 +1398,65 @@ private:
         if (size != (kind_ == HZSDR_FMT_C64 ? 8u : 4u)) throw std::invalid_argument("Agc: samples are not of the bank's kind");
     }
     int kind_;
+};
+
+// The adaptive equalizer bank (include/hzsdr_equalizer.h): a `taps`-tap linear equalizer at the symbol rate over `rows`
+// rows of `kind` (HZSDR_EQUALIZER_REAL_F32: float rows; HZSDR_FMT_C64: std::complex<float> rows), adapted under `mode`
+// (HZSDR_EQUALIZER_CMA, _DD_BPSK, _DD_QPSK) with the parameters mu, level shared by all rows, or rows of them when
+// per_row.  Push runs min(in_counts[r], n) symbols of every row (row r starts r * in_stride symbols into `in`; dense rows
+// when in_stride is 0; every row has n when in_counts is null) and returns dense rows of n values of the input's type (S
+// is float or std::complex<float>, as the kind says), zero behind a row's count; where `track` is given it takes dense
+// rows of n squared clipped errors.  No flush, no position.  The state: per row the taps, then the taps - 1 latest inputs.
+class Equalizer {
+public:
+    Equalizer(const Context &x, int kind, int mode, size_t taps, size_t centre, const std::vector<float> &params, size_t rows = 1, bool per_row = false)
+        : x_(x), rows_(rows), kind_(kind), state_words_(rows * (2 * taps - 1) * (kind == HZSDR_FMT_C64 ? 2 : 1)) {
+        if (params.size() != 2 * (per_row ? rows : 1)) throw std::invalid_argument("Equalizer: params are 2, or rows * 2 values");
+        check(x_.raw(), hzsdr_equalizer_create(x_.raw(), kind, mode, taps, centre, params.data(), per_row ? 1 : 0, rows, &h_));
+    }
+    ~Equalizer() { if (h_) hzsdr_equalizer_free(h_); }
+    Equalizer(const Equalizer &) = delete;
+    Equalizer &operator=(const Equalizer &) = delete;
+    template <typename S>
+    std::vector<S> Push(const S *in, size_t n, size_t in_stride = 0, const uint32_t *in_counts = nullptr, std::vector<float> *track = nullptr) {
+        of_kind(sizeof(S));
+        std::vector<S> out(rows_ * n);
+        if (track) track->assign(rows_ * n, 0.0f);
+        check(x_.raw(), hzsdr_equalizer_push(h_, n ? in : nullptr, n, in_stride ? in_stride : n, in_counts, n ? out.data() : nullptr, n,
+                                             track && n ? track->data() : nullptr, n));
+        return out;
+    }
+    // the rows equalized where they lie (pitch: symbols from one row's start to the next; n when 0)
+    template <typename S> void PushInPlace(S *rows, size_t n, size_t pitch = 0, const uint32_t *in_counts = nullptr) {
+        of_kind(sizeof(S));
+        check(x_.raw(), hzsdr_equalizer_push(h_, n ? rows : nullptr, n, pitch ? pitch : n, in_counts, n ? rows : nullptr, pitch ? pitch : n, nullptr, 0));
+    }
+    // the same form; the state stays
+    void SetParams(const std::vector<float> &params) { check(x_.raw(), hzsdr_equalizer_set_params(h_, params.data())); }
+    std::vector<float> State() const {
+        std::vector<float> z(state_words_);
+        check(x_.raw(), hzsdr_equalizer_get_state(h_, z.data(), z.size()));
+        return z;
+    }
+    void SetState(const std::vector<float> &z) { check(x_.raw(), hzsdr_equalizer_set_state(h_, z.data(), z.size())); }
+    std::tuple<size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_equalizer_plan(h_, &g, &t, &f));
+        return {g, t, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_equalizer_reset(h_)); }
+    size_t Rows() const { return rows_; }
+
+private:
+    void of_kind(size_t size) const {
+        if (size != (kind_ == HZSDR_FMT_C64 ? 8u : 4u)) throw std::invalid_argument("Equalizer: symbols are not of the bank's kind");
+    }
+    const Context &x_;
+    size_t rows_;
+    int kind_;
+    size_t state_words_;
+    hzsdr_equalizer *h_ = nullptr;
 };
 
 // The frame sync bank (include/hzsdr_framesync.h): hard decisions, a search for a sync word of `word_bits` bits under the

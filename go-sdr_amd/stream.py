@@ -1020,6 +1020,26 @@ def agc_rows(src, bank, block=READER_BLOCK):
     yield from _pushed_rows(src, bank, block, lambda fmt: fmt != FMT_C64 or bank.kind != FMT_C64)
 
 
+# ---- a Reader, or a symbol-timing bank's pushes, through the equalizer bank (include/hzsdr_equalizer.h) ----
+
+def equalized_rows(src, bank, block=READER_BLOCK):
+    """Push `src` through `bank` (an equalizer.Equalizer on a HOST context) and yield each push's (symbols, counts), the
+    form symbol_rows(...) yields and frame_rows(...) takes.  `src` is a Reader of complex64 samples at ONE sample per
+    symbol, read to its end in blocks of `block` symbols (a one-row complex bank; counts is None), or any iterable of
+    (symbols, counts) pairs -- what symbol_rows(...) yields: the counts go through as they are -- or of blocks of
+    symbols alone (counts is None).  The taps and the history carry from block to block and there is nothing to flush."""
+    if isinstance(src, Reader):
+        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        for y in _pushed_rows(src, bank, block, lambda fmt: False):
+            yield y, None
+        return
+    for b in src:
+        symbols, counts = b if isinstance(b, tuple) else (b, None)
+        if symbols.shape[-1]:
+            yield bank.push(symbols, counts), counts
+
+
 # ---- a Reader, or a symbol-timing bank's pushes, through the frame sync bank (include/hzsdr_framesync.h) ----
 
 def frame_rows(src, bank, cap=4, block=READER_BLOCK):
