@@ -490,6 +490,14 @@ class Context:
         from .framesync import FrameSync
         return FrameSync(self, kind, word_bits, words, maps, payload_bits, bits_per_symbol, mask, thr, diff, holdoff, rows)
 
+    def hdlc(self, kind, diff=0, fcs=16, min_bytes=None, max_bytes=256, msb_first=False, keep_bad=False, rows=1):
+        """The HDLC deframer bank (include/hzsdr_hdlc.h, hdlc.Hdlc): hard decisions, flags, bit unstuffing and the FCS
+        check (`fcs` 0, 16 or 32) over `rows` rows of soft symbols of `kind` (SYMSYNC_REAL_F32, or FMT_C64 read Re only),
+        frames of `min_bytes` (default: one byte more than the FCS) to `max_bytes` bytes: the symbol-timing bank's
+        (symbols, counts) as they are.  `diff` 2 is NRZI, what AIS and AX.25 send."""
+        from .hdlc import Hdlc
+        return Hdlc(self, kind, diff, fcs, min_bytes, max_bytes, msb_first, keep_bad, rows)
+
     def viterbi(self, kind, K, gens, data_bits, inv=0, pattern=None, termination=0, scale=1.0, crc=None, rows=1):
         """The Viterbi decoder bank (include/hzsdr_viterbi.h, viterbi.ViterbiDecoder): frames of a rate 1 / len(gens)
         convolutional code of constraint length `K`, packed hard bits (VITERBI_BITS: the frame sync bank's frames as
@@ -978,6 +986,9 @@ from .rs import (CCSDS_RS_255_223, CCSDS_RS_255_239, DVB_RS_204_188, ReedSolomon
 from ._capi import (SOFTFRAME_FORM_COMPLEX, SOFTFRAME_FORM_DIBIT, SOFTFRAME_MAX_HYPOTHESES, SOFTFRAME_MAX_PAYLOAD, SOFTFRAME_MAX_ROWS,  # noqa: E402
                     SOFTFRAME_MAX_SLOTS, SOFTFRAME_NO_HYPOTHESIS, SOFTFRAME_OUTSIDE, SOFTFRAME_SERVED)
 from .softframe import SoftFrames  # noqa: E402
+from ._capi import (HDLC_EVENT_ABORT, HDLC_EVENT_FLAG, HDLC_FORM_COMPLEX, HDLC_FORM_DIFF, HDLC_FORM_FCS16, HDLC_FORM_FCS32,  # noqa: E402
+                    HDLC_FORM_KEEP_BAD, HDLC_FORM_MSB_FIRST, HDLC_MAX_BYTES, HDLC_MAX_ROWS)
+from .hdlc import Hdlc, hdlc_encode, hdlc_fcs16, hdlc_fcs32, hdlc_line  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

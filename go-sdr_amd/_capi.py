@@ -384,6 +384,21 @@ FRAMESYNC_SIGNATURES = {
 FRAMESYNC_MAX_ROWS, FRAMESYNC_MAX_WORD, FRAMESYNC_MAX_PAYLOAD, FRAMESYNC_MAX_HYPOTHESES = 8192, 64, 8192, 4
 FRAMESYNC_FORM_COMPLEX, FRAMESYNC_FORM_DIBIT, FRAMESYNC_FORM_DIFF = 1, 2, 4
 
+# name -> (restype, argtypes); every symbol include/hzsdr_hdlc.h declares
+HDLC_SIGNATURES = {
+    "hzsdr_hdlc_create": (i32, [vp, i32, i32, C.c_uint, C.c_uint, C.c_uint, i32, i32, sz, pvp]),
+    "hzsdr_hdlc_push": (i32, [vp, vp, sz, sz, vp, vp, sz, sz, vp, vp, vp, psz]),
+    "hzsdr_hdlc_get_state": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), sz]),
+    "hzsdr_hdlc_set_state": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), sz]),
+    "hzsdr_hdlc_positions": (i32, [vp, C.POINTER(u64), sz]),
+    "hzsdr_hdlc_plan": (i32, [vp, psz, psz, psz, C.POINTER(i32)]),
+    "hzsdr_hdlc_reset": (i32, [vp]),
+    "hzsdr_hdlc_free": (i32, [vp]),
+}
+HDLC_MAX_ROWS, HDLC_MAX_BYTES = 8192, 1024
+HDLC_EVENT_ABORT, HDLC_EVENT_FLAG = 0, 1
+HDLC_FORM_COMPLEX, HDLC_FORM_DIFF, HDLC_FORM_FCS16, HDLC_FORM_FCS32, HDLC_FORM_MSB_FIRST, HDLC_FORM_KEEP_BAD = 1, 4, 8, 16, 32, 64
+
 # name -> (restype, argtypes); every symbol include/hzsdr_viterbi.h declares
 VITERBI_SIGNATURES = {
     "hzsdr_viterbi_create": (i32, [vp, i32, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.c_uint, u64, C.c_uint, i32, sz, f32, C.c_uint, C.c_uint32, C.c_uint32,
@@ -427,7 +442,7 @@ for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), 
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
                              *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items(),
-                             *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items(), *EQUALIZER_SIGNATURES.items()):
+                             *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items(), *EQUALIZER_SIGNATURES.items(), *HDLC_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

@@ -37,6 +37,7 @@
 #include "../../include/hzsdr_agc.h"
 #include "../../include/hzsdr_equalizer.h"
 #include "../../include/hzsdr_framesync.h"
+#include "../../include/hzsdr_hdlc.h"
 #include "../../include/hzsdr_viterbi.h"
 #include "../../include/hzsdr_rs.h"
 #include "../../include/hzsdr_softframe.h"
@@ -1545,6 +1546,87 @@ private:
     size_t rows_;
     Config c_;
     hzsdr_framesync *f_ = nullptr;
+};
+
+// The HDLC deframer bank (include/hzsdr_hdlc.h): hard decisions, flags, bit unstuffing and the FCS check over `rows` rows
+// of soft symbols of `kind` (HZSDR_SYMSYNC_REAL_F32: float rows; HZSDR_FMT_C64: std::complex<float> rows, Re only).  Push
+// takes what FrameSync::Push takes and returns, per row, the frames the push completed, up to `cap` of them, FCS bytes
+// included; a row that emitted more than `cap` throws.  Nothing to flush.
+class Hdlc {
+public:
+    struct Frame {
+        std::vector<uint8_t> bytes;  // frame bit k in byte k / 8, bit k % 8 (msb_first: bit 7 - k % 8)
+        uint64_t position;           // the frame's first bit: the one behind its opening flag
+        bool good;                   // the FCS verdict
+    };
+    struct Config {
+        int diff = 0;  // 2: NRZI
+        unsigned fcs = 16, min_bytes = 0 /* 0: one more than the FCS */, max_bytes = 256;
+        bool msb_first = false, keep_bad = false;
+    };
+    Hdlc(const Context &x, int kind, const Config &c, size_t rows = 1) : x_(x), rows_(rows), c_(c) {
+        if (!c_.min_bytes) c_.min_bytes = c_.fcs / 8 + 1;
+        check(x_.raw(), hzsdr_hdlc_create(x_.raw(), kind, c_.diff, c_.fcs, c_.min_bytes, c_.max_bytes, c_.msb_first, c_.keep_bad, rows, &f_));
+    }
+    ~Hdlc() { if (f_) hzsdr_hdlc_free(f_); }
+    Hdlc(const Hdlc &) = delete;
+    Hdlc &operator=(const Hdlc &) = delete;
+    std::vector<std::vector<Frame>> Push(const void *in, size_t n, size_t in_stride = 0, const uint32_t *in_counts = nullptr, size_t cap = 4) {
+        const size_t fb = c_.max_bytes;
+        std::vector<uint8_t> out(rows_ * cap * fb);
+        std::vector<uint64_t> pos(rows_ * cap);
+        std::vector<uint32_t> info(rows_ * cap), counts(rows_, 0);
+        size_t most = 0;
+        check(x_.raw(), hzsdr_hdlc_push(f_, n ? in : nullptr, n, in_stride ? in_stride : n, in_counts, out.data(), cap, cap * fb, pos.data(), info.data(),
+                                        counts.data(), &most));
+        if (most > cap) throw std::length_error("Hdlc: a row emitted more frames than cap");
+        std::vector<std::vector<Frame>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++)
+            for (size_t f = 0; f < counts[r]; f++) {
+                const uint8_t *p = out.data() + (r * cap + f) * fb;
+                const uint32_t i = info[r * cap + f];
+                rows[r].push_back({std::vector<uint8_t>(p, p + (i & 0x7fffffffu)), pos[r * cap + f], (i >> 31) != 0});
+            }
+        return rows;
+    }
+    struct StateArrays {
+        std::vector<uint64_t> positions, events;  // events: the previous event's position plus one
+        std::vector<uint8_t> kinds, history, last;  // history: rows * ceil(K / 8) bytes, oldest bit first, most significant bit first
+    };
+    StateArrays State() const {
+        StateArrays z{std::vector<uint64_t>(rows_), std::vector<uint64_t>(rows_), std::vector<uint8_t>(rows_), std::vector<uint8_t>(rows_ * HistoryBytes()),
+                      std::vector<uint8_t>(rows_)};
+        check(x_.raw(), hzsdr_hdlc_get_state(f_, z.positions.data(), z.events.data(), z.kinds.data(), z.history.data(), z.last.data(), rows_));
+        return z;
+    }
+    void SetState(const StateArrays &z) {
+        if (z.positions.size() != rows_ || z.events.size() != rows_ || z.kinds.size() != rows_ || z.history.size() != rows_ * HistoryBytes() ||
+            z.last.size() != rows_)
+            throw std::invalid_argument("Hdlc: the state has an entry per row");
+        check(x_.raw(), hzsdr_hdlc_set_state(f_, z.positions.data(), z.events.data(), z.kinds.data(), z.history.data(), z.last.data(), rows_));
+    }
+    std::vector<uint64_t> Positions() const {
+        std::vector<uint64_t> p(rows_);
+        check(x_.raw(), hzsdr_hdlc_positions(f_, p.data(), p.size()));
+        return p;
+    }
+    // -> (rows per wave, bits per tile, words of the history ring, HZSDR_HDLC_FORM_*)
+    std::tuple<size_t, size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0, r = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_hdlc_plan(f_, &g, &t, &r, &f));
+        return {g, t, r, f};
+    }
+    void Reset() { check(x_.raw(), hzsdr_hdlc_reset(f_)); }
+    size_t Rows() const { return rows_; }
+    size_t MaxBytes() const { return c_.max_bytes; }
+    size_t HistoryBytes() const { return (8 * c_.max_bytes + 8 * c_.max_bytes / 5 + 8 + 7) / 8; }
+
+private:
+    const Context &x_;
+    size_t rows_;
+    Config c_;
+    hzsdr_hdlc *f_ = nullptr;
 };
 
 // The Viterbi decoder bank (include/hzsdr_viterbi.h): frames of a rate 1 / gens.size() convolutional code -- packed hard

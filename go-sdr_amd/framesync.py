@@ -15,7 +15,8 @@ positions, info, counts and state do not depend on how the stream is cut, on the
 either pitch or on the other rows.  counts[r] above `cap` says that row r lost frames in this push.
 
 Not here: decoding a convolutionally coded payload and its CRC (include/hzsdr_viterbi.h, Context.viterbi: it takes
-frames and counts as push returns them); descrambling, bit unstuffing; soft outputs (include/hzsdr_softframe.h,
+frames and counts as push returns them); bit unstuffing (include/hzsdr_hdlc.h, Context.hdlc: the bank that stands here
+on HDLC-framed links); descrambling; soft outputs (include/hzsdr_softframe.h,
 Context.soft_frames: the bank beside this one, it takes positions, info and counts as push returns them); sync words
 above 64 bits.
 """

@@ -1072,6 +1072,38 @@ def frame_rows(src, bank, cap=4, block=READER_BLOCK):
             yield push(symbols, counts)
 
 
+# ---- the HDLC deframer bank where the frame sync bank stands (include/hzsdr_hdlc.h) ----
+
+def hdlc_frames(src, bank, cap=4, block=READER_BLOCK):
+    """Push `src` through `bank` (an hdlc.Hdlc) and yield, per push, bank.ragged(...) of its results: a list of `rows`
+    triples (packets: a list of bytes objects, FCS included; positions (k,); good (k,) bool).  `src` is what frame_rows
+    takes: a Reader of complex64 samples at ONE sample per symbol (a one-row complex bank on a HOST context), or any
+    iterable of (symbols, counts) pairs -- what symbol_rows(...) yields -- or of blocks of symbols alone.  `cap` frames
+    per row and push are kept; a row that emitted more raises ErrShortBuffer.  The state carries from block to block; a
+    frame still open at the end is not emitted."""
+    def push(symbols, counts=None):
+        frames, positions, info, got = bank.push(symbols, counts, cap)
+        if int(got.max()) > cap:
+            raise ErrShortBuffer("sdr: a row emitted more frames in one push than hdlc_frames keeps")
+        return bank.ragged(frames, positions, info, got)
+    if isinstance(src, Reader):
+        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield push(buf[:k])
+        return
+    for b in src:
+        symbols, counts = b if isinstance(b, tuple) else (b, None)
+        if symbols.shape[-1]:
+            yield push(symbols, counts)
+
+
 # ---- frame_rows with the Viterbi decoder bank behind the frame sync bank (include/hzsdr_viterbi.h) ----
 
 def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, soft=None):

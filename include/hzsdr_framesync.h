@@ -4,8 +4,8 @@
  * hzsdr_iir.h, hzsdr_agc.h, hzsdr_carrier.h and hzsdr_symsync.h and stands behind the last of them: it takes the
  * symbol-timing bank's (symbols, counts) as they are, on the device, and this is where the data rate falls from symbols
  * to packets -- where a receive chain hands over to the CPU.  What it leaves to others: decoding a convolutionally
- * coded payload and its CRC (hzsdr_viterbi.h takes `out` and `counts` as they are); descrambling, bit unstuffing and
- * every other word of a protocol; soft outputs (hzsdr_softframe.h runs beside this bank, takes `positions`, `info` and
+ * coded payload and its CRC (hzsdr_viterbi.h takes `out` and `counts` as they are); bit unstuffing (hzsdr_hdlc.h stands
+ * where this bank stands on HDLC-framed links); descrambling and every other word of a protocol; soft outputs (hzsdr_softframe.h runs beside this bank, takes `positions`, `info` and
  * `counts` as they are and writes the frames' payload floats); a sync word longer than 64 bits.
  *
  * The entries live beside hzsdr.h and the other headers (same conventions, same status codes, same context).  The
