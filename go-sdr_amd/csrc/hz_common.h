@@ -181,6 +181,18 @@ struct Stage {
     int finish();
 };
 
+// An output of `R` rows of `width` elements of `size` bytes, `stride` elements apart, that the kernel writes only in
+// part and whose rest stays as it is: a HOST context's rows go up before they come back, the gaps between them untouched.
+inline int stage_out_rows_preserved(Stage &st, int slot, void *p, size_t R, size_t width, size_t stride, size_t size, void **dev, size_t *dev_stride) {
+    if (R == 1 || stride == width) {
+        *dev_stride = width;
+        return st.out_preserve(slot, p, R * width * size, dev);
+    }
+    const void *up;
+    HZ_TRY(st.in_rows(slot, p, R, width, stride, size, &up, dev_stride));
+    return st.out_rows(slot, p, R, width, stride, size, dev, dev_stride);
+}
+
 // ---- what the bank objects (spectrum, channelizer, synthesizer, resampler, demodulator, tuner, channel bank,
 // covariance, IIR, symbol timing, carrier recovery, AGC, frame sync, Viterbi) share on the host ----
 

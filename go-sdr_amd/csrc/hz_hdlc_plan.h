@@ -1,37 +1,30 @@
 // hz_hdlc_plan.h -- the host arithmetic of the HDLC deframer bank (include/hzsdr_hdlc.h), HIP-free so that
-// tests/host/hdlc_plan.cpp can run it under the sanitizers: the validation of a bank's configuration, the history ring
-// and where an event's window and a span lie in it, the table of the FCS combine, the state's layout on the device and
-// as the ABI moves it.  A wave owns one row, as in the frame sync bank (hz_framesync_plan.h has why), and the ring is
-// that bank's: the same tiles, the same chunk, the same slots.
+// tests/host/hdlc_plan.cpp can run it under the sanitizers: the validation of a bank's configuration, where an event's
+// window and a span lie in the history ring, the table of the FCS combine, the state's layout on the device.  The bits,
+// the ring, the dealing of rows to waves and the history as the ABI moves it are the bit-ring banks': hz_bitring_plan.h.
 //
-// Bits.  A row's bit stream is numbered from 0 at create or reset; a push numbers the bits it consumes 0 ... m - 1
-// (LOCAL bits); tile t is the local bits 64 t ... 64 t + 63, one word (earliest bit lowest).  An event is kept as its
-// END, the position of its last bit plus one: the abort at -1 that a row starts with has end 0, and for a flag the end
-// is the first bit of the span behind it -- what `positions` reports.  For two flags of ends E1 < E2 the raw span is
-// the L = E2 - E1 - 8 bits from E1 on (none when E2 - E1 <= 8).  Lmax = 8 max_bytes + floor(8 max_bytes / 5) is the
-// longest span that can be well-formed, K = Lmax + 8 the history's bits: a span and its closing flag.
-//
-// The ring.  HW = ceil(K / 64) words of history lie in front of a push's first tile, the LAST bit consumed so far in
-// bit 63 of the last of them, zeros where the stream had not begun.  Numbering the words from the oldest history word
-// (ring word 0), tile t is ring word HW + t and local bit i is ring bit 64 HW + i.  The window b[i-7 ... i] of local
-// bit i starts at ring bit 64 HW + i - 7; the span that the flag of end E2 at local bit i closes starts at ring bit
-// 64 HW + i + 1 - (E2 - E1), which is not negative while L <= Lmax.  Ring word w lives in slot w & (RW - 1) of the
-// wave's LDS, RW the power of two that holds HW words of history, the kChunk words of the tiles whose loads travel
-// together, and one more: at most 256 words.  Behind the ring lie OW = ceil(max_bytes / 8) + 1 words in which a frame's
-// unstuffed bits are put together, and behind them the FCS's byte table, 256 words of 32 bits.  When a push ends behind
-// m local bits the history is re-aligned: new history word j is the 64 ring bits from 64 j + m on.
+// An event is kept as its END, the position of its last bit plus one: the abort at -1 that a row starts with has end 0,
+// and for a flag the end is the first bit of the span behind it -- what `positions` reports.  For two flags of ends
+// E1 < E2 the raw span is the L = E2 - E1 - 8 bits from E1 on (none when E2 - E1 <= 8).  Lmax = 8 max_bytes +
+// floor(8 max_bytes / 5) is the longest span that can be well-formed, K = Lmax + 8 the history's bits: a span and its
+// closing flag.  The window b[i-7 ... i] of local bit i starts at ring bit 64 HW + i - 7; the span that the flag of end
+// E2 at local bit i closes starts at ring bit 64 HW + i + 1 - (E2 - E1), which is not negative while L <= Lmax.  Behind
+// the ring lie OW = ceil(max_bytes / 8) + 1 words in which a frame's unstuffed bits are put together, and behind them the
+// FCS's byte table, 256 words of 32 bits.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
-#include "hz_framesync_plan.h"
+#include "hz_bitring_plan.h"
+#include "hz_framesync_math.h"
 #include "hz_hdlc_math.h"
 
 namespace hz {
 namespace hp {
 
-using fp::kMaxRows, fp::kLanes, fp::kTileBits, fp::kChunk, fp::kMaxPush, fp::kRealF32, fp::kC64;
-using fp::wave_first_row, fp::wave_row_count, fp::ring_slot, fp::tile_word;
+using br::kMaxRows, br::kLanes, br::kTileBits, br::kChunk, br::kMaxPush, br::kRealF32, br::kC64;
+using br::wave_first_row, br::wave_row_count, br::ring_slot, br::tile_word;
+using br::history_bytes, br::history_to_bytes, br::history_from_bytes;
 
 constexpr uint32_t kMaxBytes = 1024;
 constexpr uint32_t kMaxPass = 3;  // a span's words over the 64 lanes: ceil(154 / 64) passes at most
@@ -64,15 +57,11 @@ inline const char *check_config(const Config &q) {
 
 inline uint32_t span_max(uint32_t max_bytes) { return 8 * max_bytes + 8 * max_bytes / 5; }
 
-struct Geom {
-    uint32_t G, waves;  // rows per wave, waves
-    uint32_t Lmax;      // the longest raw span that can be well-formed
-    uint32_t K;         // Lmax + 8: the history's bits
-    uint32_t HW;        // the history's words: ceil(K / 64)
-    uint32_t RW;        // the ring's words, a power of two
-    uint32_t c;         // 64 HW - K: where the history's oldest bit lies in its first word
-    uint32_t OW;        // the words in which a frame is put together
-    uint32_t per;       // a row's state on the device, in uint64 words: bits, event end, event kind, last, HW of history
+// the ring's K is Lmax + 8
+struct Geom : br::Ring, br::Deal {
+    uint32_t Lmax;  // the longest raw span that can be well-formed
+    uint32_t OW;    // the words in which a frame is put together
+    uint32_t per;   // a row's state on the device, in uint64 words: bits, event end, event kind, last, HW of history
     size_t lds_bytes;
 };
 
@@ -80,14 +69,8 @@ constexpr uint32_t kStBits = 0, kStEvEnd = 1, kStEvKind = 2, kStLast = 3, kStHis
 
 // rows: 1 ... kMaxRows; a checked max_bytes
 inline Geom geom(uint32_t rows, uint32_t max_bytes) {
-    Geom g{};
-    g.G = 1, g.waves = rows;
+    Geom g{br::ring(span_max(max_bytes) + 8), br::deal(rows)};
     g.Lmax = span_max(max_bytes);
-    g.K = g.Lmax + 8;
-    g.HW = (g.K + 63) / 64;
-    g.RW = 1;
-    while (g.RW < g.HW + kChunk + 1) g.RW *= 2;
-    g.c = 64 * g.HW - g.K;
     g.OW = (max_bytes + 7) / 8 + 1;
     g.per = kStHist + g.HW;
     g.lds_bytes = (size_t)(g.RW + g.OW) * 8 + kTableBytes;
@@ -114,23 +97,6 @@ inline void fcs_powers(uint32_t fcs, uint32_t *tab) {
     for (uint32_t k = 0; k < kPowers; k++) {
         tab[k] = a;
         for (int s = 0; s < 64; s++) a = hm::fcs_next_power(a, hm::fcs_poly(fcs));
-    }
-}
-
-// ---- the history as the ABI moves it: K bits, oldest first, bit k in byte k / 8, bit 7 - k % 8 ----
-inline size_t history_bytes(uint32_t K) { return (K + 7) / 8; }
-inline void history_to_bytes(const uint64_t *words, const Geom &g, uint8_t *bytes) {
-    for (size_t b = 0; b < history_bytes(g.K); b++) bytes[b] = 0;
-    for (uint32_t k = 0; k < g.K; k++) {
-        const uint32_t at = g.c + k;
-        if ((words[at >> 6] >> (at & 63)) & 1ull) bytes[k >> 3] |= (uint8_t)(0x80u >> (k & 7));
-    }
-}
-inline void history_from_bytes(const uint8_t *bytes, const Geom &g, uint64_t *words) {
-    for (uint32_t w = 0; w < g.HW; w++) words[w] = 0;
-    for (uint32_t k = 0; k < g.K; k++) {
-        const uint32_t at = g.c + k;
-        if (bytes[k >> 3] & (0x80u >> (k & 7))) words[at >> 6] |= 1ull << (at & 63);
     }
 }
 

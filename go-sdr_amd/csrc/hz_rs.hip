@@ -252,15 +252,8 @@ int hzsdr_rs_decode(hzsdr_rs *v, const uint8_t *in, size_t in_stride, size_t in_
     size_t istride = R > 1 ? in_stride : iw, ostride = R > 1 ? out_stride : ow;
     HZ_TRY(st.in_rows(0, in, R, iw, istride, 1, &din, &istride));
     if (in_counts) HZ_TRY(st.in(1, in_counts, R * sizeof(uint32_t), &dic));
-    // the slots behind a row's count, and the bytes behind a slot's data, stay as they are: a HOST context's rows go up before they come back
-    if (R == 1 || out_stride == ow) {
-        HZ_TRY(st.out_preserve(2, out, R * ow, &dout));
-        ostride = ow;
-    } else {
-        const void *up;
-        HZ_TRY(st.in_rows(2, out, R, ow, out_stride, 1, &up, &ostride));
-        HZ_TRY(st.out_rows(2, out, R, ow, out_stride, 1, &dout, &ostride));
-    }
+    // the slots behind a row's count, and the bytes behind a slot's data, stay as they are
+    HZ_TRY(stage_out_rows_preserved(st, 2, out, R, ow, out_stride, 1, &dout, &ostride));
     HZ_TRY(st.out_preserve(3, info, R * cap * sizeof(uint32_t), &dinfo));
     RsArgs a{};
     a.in = (const uint8_t *)din, a.in_stride = istride, a.in_pitch = in_pitch, a.in_counts = (const uint32_t *)dic;

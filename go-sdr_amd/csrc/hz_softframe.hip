@@ -172,16 +172,8 @@ int hzsdr_softframe_push(hzsdr_softframe *f, const void *in, size_t n, size_t in
         HZ_TRY(st.in(2, positions, R * cap * sizeof(uint64_t), &dpos));
         HZ_TRY(st.in(3, info, R * cap * sizeof(uint32_t), &dinfo));
         HZ_TRY(st.in(4, counts, R * sizeof(uint32_t), &dcounts));
-        // the slots behind a row's count stay as they are: a HOST context's rows go up before they come back
-        const size_t width = cap * P;
-        if (R == 1 || out_stride == width) {
-            HZ_TRY(st.out_preserve(5, out, R * width * sizeof(float), &dout));
-            ostride = width;
-        } else {
-            const void *up;
-            HZ_TRY(st.in_rows(5, out, R, width, out_stride, sizeof(float), &up, &ostride));
-            HZ_TRY(st.out_rows(5, out, R, width, out_stride, sizeof(float), &dout, &ostride));
-        }
+        // the slots behind a row's count stay as they are
+        HZ_TRY(stage_out_rows_preserved(st, 5, out, R, cap * P, out_stride, sizeof(float), &dout, &ostride));
         HZ_TRY(st.out_preserve(6, status, R * cap * sizeof(uint32_t), &dstatus));
     }
     SfArgs a{};

@@ -315,15 +315,8 @@ int hzsdr_viterbi_decode(hzsdr_viterbi *v, const void *in, size_t in_stride, con
     size_t istride = R > 1 ? in_stride : iw, ostride = R > 1 ? out_stride : ow;
     HZ_TRY(st.in_rows(0, in, R, iw, istride, isz, &din, &istride));
     if (in_counts) HZ_TRY(st.in(1, in_counts, R * sizeof(uint32_t), &dic));
-    // the slots behind a row's count, and a frame's neighbours, stay as they are: a HOST context's rows go up before they come back
-    if (R == 1 || out_stride == ow) {
-        HZ_TRY(st.out_preserve(2, out, R * ow, &dout));
-        ostride = ow;
-    } else {
-        const void *up;
-        HZ_TRY(st.in_rows(2, out, R, ow, out_stride, 1, &up, &ostride));
-        HZ_TRY(st.out_rows(2, out, R, ow, out_stride, 1, &dout, &ostride));
-    }
+    // the slots behind a row's count, and a frame's neighbours, stay as they are
+    HZ_TRY(stage_out_rows_preserved(st, 2, out, R, ow, out_stride, 1, &dout, &ostride));
     HZ_TRY(st.out_preserve(3, info, R * cap * sizeof(uint32_t), &dinfo));
     const vp::Config &q = v->q;
     const vp::Geom &g = v->g;

@@ -25,7 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import ErrInvalidArgument, FMT_C64, _is_torch, lib
-from ._rows import rows_input
+from ._frames import BitRingBank
 from ._capi import (FRAMESYNC_FORM_COMPLEX, FRAMESYNC_FORM_DIBIT, FRAMESYNC_FORM_DIFF, FRAMESYNC_MAX_HYPOTHESES, FRAMESYNC_MAX_PAYLOAD,
                     FRAMESYNC_MAX_ROWS, FRAMESYNC_MAX_WORD)
 
@@ -70,18 +70,17 @@ def sync_hypotheses(word, word_bits, bits_per_symbol=1, ambiguity="none"):
     raise ValueError('sync_hypotheses: ambiguity is "none", "invert" (1 bit per symbol) or "rotate" (2 bits per symbol)')
 
 
-class FrameSync:
+class FrameSync(BitRingBank):
     """hzsdr_framesync: push(symbols, counts) -> (frames, positions, info, counts).  `kind` is SYMSYNC_REAL_F32 (float32
     rows) or FMT_C64 (complex64 rows, bits_per_symbol 1 -- Re only -- or 2).  One row takes (n,) symbols; `rows` = R > 1
     takes (R, n) with unit stride along a row and any row pitch.  `words` and `maps` are the hypotheses (sync_hypotheses
     builds them); `mask` defaults to all word_bits bits, `holdoff` to one frame's symbols.  numpy in a HOST context; torch
     tensors on the context's device, written on the context's stream, in a DEVICE context (positions are int64, info and
     counts int32 there: the same bits as the ABI's unsigned types)."""
+    _c, _noun, _extent = "framesync", "frame sync", "FB"
 
     def __init__(self, ctx, kind, word_bits, words, maps, payload_bits, bits_per_symbol=1, mask=None, thr=0, diff=0, holdoff=None, rows=1):
-        self.ctx, self.kind, self.rows = ctx, int(kind), int(rows)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("frame sync: rows is at least 1")
+        self._open(ctx, kind, rows)
         self.W, self.P, self.B = int(word_bits), int(payload_bits), int(bits_per_symbol)
         words, maps = [int(w) for w in np.atleast_1d(words)], [int(m) for m in np.atleast_1d(maps)]
         if len(words) != len(maps) or not 1 <= len(words) <= FRAMESYNC_MAX_HYPOTHESES:
@@ -95,41 +94,13 @@ class FrameSync:
             raise ErrInvalidArgument("frame sync: mask and holdoff are uint64 values")
         self.frame_bytes, self.history_bytes = (self.P + 7) // 8, (self.W + self.P - 1 + 7) // 8
         w, m = (C.c_uint64 * len(words))(*words), (C.c_uint * len(maps))(*maps)
-        self._h = C.c_void_p()
         ctx._ck(lib.hzsdr_framesync_create(ctx._h, self.kind, self.B, self.W, self.mask, self.thr, len(words), w, m, self.P, self.diff, self.holdoff,
                                            self.rows, C.byref(self._h)))
 
     def plan(self):
         """(rows per wave, bits per tile, words of the history ring, form): the form is a sum of FRAMESYNC_FORM_COMPLEX,
         FRAMESYNC_FORM_DIBIT and FRAMESYNC_FORM_DIFF."""
-        g, t, r, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_framesync_plan(self._h, C.byref(g), C.byref(t), C.byref(r), C.byref(f)))
-        return g.value, t.value, r.value, f.value
-
-    def positions(self):
-        """Symbols consumed per row: uint64 (rows,), behind every push so far."""
-        p = np.empty(self.rows, np.uint64)
-        self.ctx._ck(lib.hzsdr_framesync_positions(self._h, p.ctypes.data_as(_PU64), p.size))
-        return p
-
-    def _new(self, shape, dtype, like):
-        if _is_torch(like):
-            import torch
-            return torch.zeros(shape, dtype={np.uint8: torch.uint8, np.uint64: torch.int64, np.uint32: torch.int32}[dtype], device=like.device)
-        return np.zeros(shape, dtype)
-
-    @staticmethod
-    def _dense(a, shape, dtype, what):
-        """pointer of a contiguous destination of `shape`: numpy of `dtype`, or torch of the same width"""
-        if _is_torch(a):
-            import torch
-            ok = a.dtype == {np.uint8: torch.uint8, np.uint64: torch.int64, np.uint32: torch.int32}[dtype] and a.is_contiguous()
-            ptr = a.data_ptr()
-        else:
-            ok, ptr = a.dtype == dtype and a.flags.c_contiguous, a.ctypes.data
-        if not ok or tuple(a.shape) != tuple(shape):
-            raise ValueError(f"frame sync: {what} is a contiguous {np.dtype(dtype).name} {tuple(shape)} (torch: the signed type of that width)")
-        return ptr
+        return self._plan()
 
     def push(self, symbols, counts=None, cap=4, out=None):
         """Run the symbols of every row through the bank -> (frames, positions, info, counts).  `counts`, when given, is
@@ -138,29 +109,7 @@ class FrameSync:
         (rows, cap) dist | h << 8, counts (rows,) the frames accepted in this push: above cap where a row lost some.
         Slots from a row's count up hold what the destination held (a new one is zero).  `out`, when given, is such a
         tuple (frames, positions, info, counts) to write into; frames may be a view with a row pitch above cap * FB."""
-        ptr, n, pitch = rows_input(symbols, self.kind, self.rows, "frame sync")
-        cap, R, FB = int(cap), self.rows, self.frame_bytes
-        if cap < 0:
-            raise ValueError("frame sync: cap is not negative")
-        if out is None:
-            out = (self._new((R, cap, FB), np.uint8, symbols), self._new((R, cap), np.uint64, symbols), self._new((R, cap), np.uint32, symbols),
-                   self._new((R,), np.uint32, symbols))
-        frames, positions, info, got = out
-        if _is_torch(frames):
-            import torch
-            ok, strides, fptr = frames.dtype == torch.uint8, tuple(frames.stride()), frames.data_ptr()
-        else:
-            ok, strides, fptr = frames.dtype == np.uint8, tuple(frames.strides), frames.ctypes.data
-        if not ok or tuple(frames.shape) != (R, cap, FB) or (cap and (strides[2] != 1 or (cap > 1 and strides[1] != FB) or (R > 1 and strides[0] < cap * FB))):
-            raise ValueError("frame sync: frames are uint8 (rows, cap, FB) with contiguous rows")
-        pptr, iptr = self._dense(positions, (R, cap), np.uint64, "positions"), self._dense(info, (R, cap), np.uint32, "info")
-        gptr = self._dense(got, (R,), np.uint32, "counts")
-        cptr = None
-        if counts is not None:
-            cptr = self._dense(counts, (R,), np.uint32, "the symbols' counts")
-        self.ctx._ck(lib.hzsdr_framesync_push(self._h, ptr, n, pitch, cptr, fptr if cap else None, cap, int(strides[0]) if cap else 0,
-                                              pptr if cap else None, iptr if cap else None, gptr, None))
-        return frames, positions, info, got
+        return self._push(symbols, counts, cap, out)
 
     def ragged(self, frames, positions, info, counts):
         """A push's results -> a list of `rows` host triples (frames (k, FB), positions (k,) uint64, info (k,) uint32),
@@ -192,20 +141,6 @@ class FrameSync:
             raise ErrInvalidArgument("frame sync: the state is positions (rows,), holds (rows,), history (rows, ceil(K / 8)), last (rows,)")
         self.ctx._ck(lib.hzsdr_framesync_set_state(self._h, p.ctypes.data_as(_PU64), h.ctypes.data_as(_PU64), y.ctypes.data_as(_PU8),
                                                    d.ctypes.data_as(_PU8), R))
-
-    def reset(self):
-        self.ctx._ck(lib.hzsdr_framesync_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib.hzsdr_framesync_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 __all__ = ["FrameSync", "sync_hypotheses", "pack_bits", "unpack_bits", "FRAMESYNC_FORM_COMPLEX", "FRAMESYNC_FORM_DIBIT", "FRAMESYNC_FORM_DIFF",

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import ErrInvalidArgument, _is_torch, lib
-from ._rows import rows_input
+from ._frames import BitRingBank
 from ._capi import (HDLC_EVENT_ABORT, HDLC_EVENT_FLAG, HDLC_FORM_COMPLEX, HDLC_FORM_DIFF, HDLC_FORM_FCS16, HDLC_FORM_FCS32, HDLC_FORM_KEEP_BAD,
                     HDLC_FORM_MSB_FIRST, HDLC_MAX_BYTES, HDLC_MAX_ROWS)
 
@@ -97,58 +97,29 @@ def hdlc_line(bits, diff=0):
     return (np.cumsum(b ^ 1 if diff == 2 else b) & 1).astype(np.uint8)
 
 
-class Hdlc:
+class Hdlc(BitRingBank):
     """hzsdr_hdlc: push(symbols, counts) -> (frames, positions, info, counts).  `kind` is SYMSYNC_REAL_F32 (float32 rows)
     or FMT_C64 (complex64 rows, Re only).  One row takes (n,) symbols; `rows` = R > 1 takes (R, n) with unit stride along
     a row and any row pitch.  numpy in a HOST context; torch tensors on the context's device, written on the context's
     stream, in a DEVICE context (positions are int64, info and counts int32 there: the same bits as the ABI's unsigned
     types)."""
+    _c, _noun, _extent = "hdlc", "hdlc", "max_bytes"
 
     def __init__(self, ctx, kind, diff=0, fcs=16, min_bytes=None, max_bytes=256, msb_first=False, keep_bad=False, rows=1):
-        self.ctx, self.kind, self.rows = ctx, int(kind), int(rows)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("hdlc: rows is at least 1")
+        self._open(ctx, kind, rows)
         self.diff, self.fcs, self.max_bytes = int(diff), int(fcs), int(max_bytes)
         self.min_bytes = self.fcs // 8 + 1 if min_bytes is None else int(min_bytes)
         self.msb_first, self.keep_bad = int(bool(msb_first)), int(bool(keep_bad))
         if min(self.diff, self.fcs, self.min_bytes, self.max_bytes) < 0 or max(self.fcs, self.min_bytes, self.max_bytes) >= 1 << 32:
             raise ErrInvalidArgument("hdlc: diff, fcs and the bounds are not negative")
         self.span_max = 8 * self.max_bytes + 8 * self.max_bytes // 5
-        self.history_bytes = (self.span_max + 8 + 7) // 8
-        self._h = C.c_void_p()
+        self.frame_bytes, self.history_bytes = self.max_bytes, (self.span_max + 8 + 7) // 8
         ctx._ck(lib.hzsdr_hdlc_create(ctx._h, self.kind, self.diff, self.fcs, self.min_bytes, self.max_bytes, self.msb_first, self.keep_bad, self.rows,
                                       C.byref(self._h)))
 
     def plan(self):
         """(rows per wave, bits per tile, words of the history ring, form): the form is a sum of HDLC_FORM_*."""
-        g, t, r, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_hdlc_plan(self._h, C.byref(g), C.byref(t), C.byref(r), C.byref(f)))
-        return g.value, t.value, r.value, f.value
-
-    def positions(self):
-        """Symbols consumed per row: uint64 (rows,), behind every push so far."""
-        p = np.empty(self.rows, np.uint64)
-        self.ctx._ck(lib.hzsdr_hdlc_positions(self._h, p.ctypes.data_as(_PU64), p.size))
-        return p
-
-    def _new(self, shape, dtype, like):
-        if _is_torch(like):
-            import torch
-            return torch.zeros(shape, dtype={np.uint8: torch.uint8, np.uint64: torch.int64, np.uint32: torch.int32}[dtype], device=like.device)
-        return np.zeros(shape, dtype)
-
-    @staticmethod
-    def _dense(a, shape, dtype, what):
-        """pointer of a contiguous destination of `shape`: numpy of `dtype`, or torch of the same width"""
-        if _is_torch(a):
-            import torch
-            ok = a.dtype == {np.uint8: torch.uint8, np.uint64: torch.int64, np.uint32: torch.int32}[dtype] and a.is_contiguous()
-            ptr = a.data_ptr()
-        else:
-            ok, ptr = a.dtype == dtype and a.flags.c_contiguous, a.ctypes.data
-        if not ok or tuple(a.shape) != tuple(shape):
-            raise ValueError(f"hdlc: {what} is a contiguous {np.dtype(dtype).name} {tuple(shape)} (torch: the signed type of that width)")
-        return ptr
+        return self._plan()
 
     def push(self, symbols, counts=None, cap=4, out=None):
         """Run the symbols of every row through the bank -> (frames, positions, info, counts).  `counts`, when given, is
@@ -158,29 +129,7 @@ class Hdlc:
         Slots from a row's count up, and a slot's bytes behind its frame, hold what the destination held (a new one is
         zero).  `out`, when given, is such a tuple (frames, positions, info, counts) to write into; frames may be a view
         with a row pitch above cap * max_bytes."""
-        ptr, n, pitch = rows_input(symbols, self.kind, self.rows, "hdlc")
-        cap, R, FB = int(cap), self.rows, self.max_bytes
-        if cap < 0:
-            raise ValueError("hdlc: cap is not negative")
-        if out is None:
-            out = (self._new((R, cap, FB), np.uint8, symbols), self._new((R, cap), np.uint64, symbols), self._new((R, cap), np.uint32, symbols),
-                   self._new((R,), np.uint32, symbols))
-        frames, positions, info, got = out
-        if _is_torch(frames):
-            import torch
-            ok, strides, fptr = frames.dtype == torch.uint8, tuple(frames.stride()), frames.data_ptr()
-        else:
-            ok, strides, fptr = frames.dtype == np.uint8, tuple(frames.strides), frames.ctypes.data
-        if not ok or tuple(frames.shape) != (R, cap, FB) or (cap and (strides[2] != 1 or (cap > 1 and strides[1] != FB) or (R > 1 and strides[0] < cap * FB))):
-            raise ValueError("hdlc: frames are uint8 (rows, cap, max_bytes) with contiguous rows")
-        pptr, iptr = self._dense(positions, (R, cap), np.uint64, "positions"), self._dense(info, (R, cap), np.uint32, "info")
-        gptr = self._dense(got, (R,), np.uint32, "counts")
-        cptr = None
-        if counts is not None:
-            cptr = self._dense(counts, (R,), np.uint32, "the symbols' counts")
-        self.ctx._ck(lib.hzsdr_hdlc_push(self._h, ptr, n, pitch, cptr, fptr if cap else None, cap, int(strides[0]) if cap else 0,
-                                         pptr if cap else None, iptr if cap else None, gptr, None))
-        return frames, positions, info, got
+        return self._push(symbols, counts, cap, out)
 
     def ragged(self, frames, positions, info, counts):
         """A push's results -> a list of `rows` host triples (packets: a list of k bytes objects, FCS included;
@@ -216,20 +165,6 @@ class Hdlc:
             raise ErrInvalidArgument("hdlc: the state is positions (rows,), events (rows,), kinds (rows,), history (rows, ceil(K / 8)), last (rows,)")
         self.ctx._ck(lib.hzsdr_hdlc_set_state(self._h, p.ctypes.data_as(_PU64), e.ctypes.data_as(_PU64), k.ctypes.data_as(_PU8), y.ctypes.data_as(_PU8),
                                               d.ctypes.data_as(_PU8), R))
-
-    def reset(self):
-        self.ctx._ck(lib.hzsdr_hdlc_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib.hzsdr_hdlc_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 __all__ = ["Hdlc", "hdlc_encode", "hdlc_line", "hdlc_fcs16", "hdlc_fcs32", "HDLC_EVENT_ABORT", "HDLC_EVENT_FLAG", "HDLC_FORM_COMPLEX", "HDLC_FORM_DIFF",

@@ -22,6 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import ErrInvalidArgument, _is_torch, lib
+from ._frames import dense_ptr, new_like, pitched_block_ptr
 from ._capi import RS_MAX_FRAMES, RS_MAX_INTERLEAVE, RS_MAX_N, RS_MAX_ROOTS, RS_MAX_ROWS, RS_MAX_SCRAMBLE, RS_MIN_ROOTS
 
 CCSDS_RS_255_223 = (0x187, 112, 11, 32, 255)  # (gfpoly, fcr, prim, nroots, n)
@@ -150,36 +151,6 @@ class ReedSolomon:
         self.ctx._ck(lib.hzsdr_rs_plan(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
-    def _block(self, a, cap, least, what):
-        """(pointer, row pitch, slot pitch) in bytes of a (rows, cap, width >= least) uint8 block"""
-        if _is_torch(a):
-            import torch
-            ok, strides, ptr = a.dtype == torch.uint8, tuple(a.stride()), a.data_ptr()
-        else:
-            ok, strides, ptr = a.dtype == np.uint8, tuple(a.strides), a.ctypes.data
-        shape = tuple(a.shape)
-        if not ok or len(shape) != 3 or shape[:2] != (self.rows, cap) or shape[2] < least or (shape[2] > 1 and strides[2] != 1):
-            raise ValueError(f"rs: {what} is uint8 ({self.rows}, {cap}, at least {least}) with unit stride along a frame")
-        pitch = int(strides[1]) if cap > 1 else shape[2]
-        return ptr, int(strides[0]) if self.rows > 1 else cap * pitch, pitch
-
-    def _dense(self, a, shape, what):
-        if _is_torch(a):
-            import torch
-            ok, ptr = a.dtype == torch.int32 and a.is_contiguous(), a.data_ptr()
-        else:
-            ok, ptr = a.dtype == np.uint32 and a.flags.c_contiguous, a.ctypes.data
-        if not ok or tuple(a.shape) != tuple(shape):
-            raise ValueError(f"rs: {what} is a contiguous uint32 {tuple(shape)} (torch: int32)")
-        return ptr
-
-    @staticmethod
-    def _new(shape, dtype, like):
-        if _is_torch(like):
-            import torch
-            return torch.zeros(shape, dtype={np.uint8: torch.uint8, np.uint32: torch.int32}[dtype], device=like.device)
-        return np.zeros(shape, dtype)
-
     def decode(self, frames, counts=None, cap=None, out=None):
         """Decode min(counts[r], cap) frames of every row -> (data uint8 (rows, cap, I k), info (rows, cap) =
         E | nfail << 16 | ok << 31).  `counts`, when given, is what the bank in front returned beside the frames (values
@@ -191,15 +162,15 @@ class ReedSolomon:
         if frames.ndim != 3:
             raise ValueError("rs: frames are (rows, cap, width)")
         cap = int(frames.shape[1]) if cap is None else int(cap)
-        fptr, fstride, fpitch = self._block(frames, cap, self.frame_bytes, "frames")
+        fptr, fstride, fpitch = pitched_block_ptr(frames, self.rows, cap, self.frame_bytes, "frames", "rs")
         if out is None:
-            out = (self._new((self.rows, cap, self.data_bytes), np.uint8, frames), self._new((self.rows, cap), np.uint32, frames))
+            out = (new_like((self.rows, cap, self.data_bytes), np.uint8, frames), new_like((self.rows, cap), np.uint32, frames))
         data, info = out
         if data.ndim == 2 and self.rows == 1:
             data = data[None]
-        dptr, dstride, dpitch = self._block(data, cap, self.data_bytes, "data")
-        iptr = self._dense(info, (self.rows, cap), "info")
-        cptr = None if counts is None else self._dense(counts, (self.rows,), "the frames' counts")
+        dptr, dstride, dpitch = pitched_block_ptr(data, self.rows, cap, self.data_bytes, "data", "rs")
+        iptr = dense_ptr(info, (self.rows, cap), np.uint32, "info", "rs", "int32")
+        cptr = None if counts is None else dense_ptr(counts, (self.rows,), np.uint32, "the frames' counts", "rs", "int32")
         self.ctx._ck(lib.hzsdr_rs_decode(self._h, fptr, fstride, fpitch, cptr, cap, dptr, dstride, dpitch, iptr))
         return out[0], info
 

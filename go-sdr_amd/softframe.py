@@ -25,6 +25,7 @@ import ctypes as C
 import numpy as np
 
 from . import ErrInvalidArgument, _is_torch, lib
+from ._frames import dense_ptr, new_like
 from ._rows import rows_input
 from ._capi import (SOFTFRAME_FORM_COMPLEX, SOFTFRAME_FORM_DIBIT, SOFTFRAME_MAX_HYPOTHESES, SOFTFRAME_MAX_PAYLOAD, SOFTFRAME_MAX_ROWS,
                     SOFTFRAME_MAX_SLOTS, SOFTFRAME_NO_HYPOTHESIS, SOFTFRAME_OUTSIDE, SOFTFRAME_SERVED)
@@ -65,18 +66,6 @@ class SoftFrames:
         self.ctx._ck(lib.hzsdr_softframe_positions(self._h, p.ctypes.data_as(_PU64), p.size))
         return p
 
-    @staticmethod
-    def _dense(a, shape, dtype, what):
-        """pointer of a contiguous array of `shape`: numpy of `dtype`, or torch of the signed type of that width"""
-        if _is_torch(a):
-            import torch
-            ok, ptr = a.dtype == {np.uint64: torch.int64, np.uint32: torch.int32}[dtype] and a.is_contiguous(), a.data_ptr()
-        else:
-            ok, ptr = a.dtype == dtype and a.flags.c_contiguous, a.ctypes.data
-        if not ok or tuple(a.shape) != tuple(shape):
-            raise ValueError(f"soft frames: {what} is a contiguous {np.dtype(dtype).name} {tuple(shape)} (torch: the signed type of that width)")
-        return ptr
-
     def push(self, symbols, counts, positions, info, got, cap, out=None):
         """Serve the frames of FrameSync.push(symbols, counts, cap) -> (frames, positions, info, got) and run the symbols
         into the history -> (soft float32 (rows, cap, P), status (rows, cap)).  `symbols` and `counts` (or None) are
@@ -87,11 +76,7 @@ class SoftFrames:
         if cap < 0:
             raise ValueError("soft frames: cap is not negative")
         if out is None:
-            if _is_torch(symbols):
-                import torch
-                out = (torch.zeros((R, cap, P), dtype=torch.float32, device=symbols.device), torch.zeros((R, cap), dtype=torch.int32, device=symbols.device))
-            else:
-                out = (np.zeros((R, cap, P), np.float32), np.zeros((R, cap), np.uint32))
+            out = (new_like((R, cap, P), np.float32, symbols), new_like((R, cap), np.uint32, symbols))
         soft, status = out
         if _is_torch(soft):
             import torch
@@ -100,10 +85,11 @@ class SoftFrames:
             ok, strides, optr = soft.dtype == np.float32, tuple(s // 4 for s in soft.strides), soft.ctypes.data
         if not ok or tuple(soft.shape) != (R, cap, P) or (cap and ((P > 1 and strides[2] != 1) or (cap > 1 and strides[1] != P) or (R > 1 and strides[0] < cap * P))):
             raise ValueError("soft frames: soft is float32 (rows, cap, P) with contiguous rows")
-        sptr = self._dense(status, (R, cap), np.uint32, "status")
-        pptr, iptr = self._dense(positions, (R, cap), np.uint64, "positions"), self._dense(info, (R, cap), np.uint32, "info")
-        gptr = self._dense(got, (R,), np.uint32, "the frames' counts")
-        cptr = None if counts is None else self._dense(counts, (R,), np.uint32, "the symbols' counts")
+        noun = "soft frames"
+        sptr = dense_ptr(status, (R, cap), np.uint32, "status", noun)
+        pptr, iptr = dense_ptr(positions, (R, cap), np.uint64, "positions", noun), dense_ptr(info, (R, cap), np.uint32, "info", noun)
+        gptr = dense_ptr(got, (R,), np.uint32, "the frames' counts", noun)
+        cptr = None if counts is None else dense_ptr(counts, (R,), np.uint32, "the symbols' counts", noun)
         self.ctx._ck(lib.hzsdr_softframe_push(self._h, ptr, n, pitch, cptr, pptr if cap else None, iptr if cap else None, gptr if cap else None, cap,
                                               optr if cap else None, int(strides[0]) if cap and R > 1 else cap * P, sptr if cap else None))
         return soft, status

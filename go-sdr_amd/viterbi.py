@@ -22,6 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import ErrInvalidArgument, _is_torch, lib
+from ._frames import block_ptr, dense_ptr, new_like
 from ._capi import (VITERBI_BITS, VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH, VITERBI_MAX_BITS, VITERBI_MAX_FRAMES, VITERBI_MAX_K, VITERBI_MAX_PATTERN,
                     VITERBI_MAX_RATE, VITERBI_MAX_ROWS, VITERBI_MIN_K, VITERBI_SOFT_F32, VITERBI_TAIL, VITERBI_TRUNCATED)
 
@@ -116,37 +117,6 @@ class ViterbiDecoder:
         self.ctx._ck(lib.hzsdr_viterbi_plan(self._h, C.byref(g), C.byref(s), C.byref(d), C.byref(f)))
         return g.value, s.value, d.value, f.value
 
-    @staticmethod
-    def _block(a, shape, dtype, what):
-        """(pointer, row pitch in elements) of a (rows, cap, width) block with contiguous rows"""
-        if _is_torch(a):
-            import torch
-            ok = a.dtype == {np.uint8: torch.uint8, np.float32: torch.float32}[dtype]
-            strides, ptr = tuple(a.stride()), a.data_ptr()
-        else:
-            ok, strides, ptr = a.dtype == dtype, tuple(s // a.itemsize for s in a.strides), a.ctypes.data
-        R, cap, w = shape
-        if not ok or tuple(a.shape) != shape or (w > 1 and strides[2] != 1) or (cap > 1 and strides[1] != w) or (R > 1 and strides[0] < cap * w):
-            raise ValueError(f"viterbi: {what} is {np.dtype(dtype).name} {shape} with contiguous rows")
-        return ptr, int(strides[0]) if R > 1 else cap * w
-
-    @staticmethod
-    def _dense(a, shape, what):
-        if _is_torch(a):
-            import torch
-            ok, ptr = a.dtype == torch.int32 and a.is_contiguous(), a.data_ptr()
-        else:
-            ok, ptr = a.dtype == np.uint32 and a.flags.c_contiguous, a.ctypes.data
-        if not ok or tuple(a.shape) != tuple(shape):
-            raise ValueError(f"viterbi: {what} is a contiguous uint32 {tuple(shape)} (torch: int32)")
-        return ptr
-
-    def _new(self, shape, dtype, like):
-        if _is_torch(like):
-            import torch
-            return torch.zeros(shape, dtype={np.uint8: torch.uint8, np.uint32: torch.int32}[dtype], device=like.device)
-        return np.zeros(shape, dtype)
-
     def decode(self, frames, counts=None, cap=None, out=None):
         """Decode min(counts[r], cap) frames of every row -> (data uint8 (rows, cap, DB), info (rows, cap) =
         metric | crc_ok << 31).  `counts`, when given, is what FrameSync.push returned beside the frames (values above
@@ -161,13 +131,13 @@ class ViterbiDecoder:
         if frames.ndim != 3:
             raise ValueError("viterbi: frames are (rows, cap, FB or N)")
         cap = int(frames.shape[1]) if cap is None else int(cap)
-        fptr, fpitch = self._block(frames, (R, cap, width), dtype, "frames")
+        fptr, fpitch = block_ptr(frames, (R, cap, width), dtype, "frames", "viterbi")
         if out is None:
-            out = (self._new((R, cap, self.data_bytes), np.uint8, frames), self._new((R, cap), np.uint32, frames))
+            out = (new_like((R, cap, self.data_bytes), np.uint8, frames), new_like((R, cap), np.uint32, frames))
         data, info = out
-        dptr, dpitch = self._block(data, (R, cap, self.data_bytes), np.uint8, "data")
-        iptr = self._dense(info, (R, cap), "info")
-        cptr = None if counts is None else self._dense(counts, (R,), "the frames' counts")
+        dptr, dpitch = block_ptr(data, (R, cap, self.data_bytes), np.uint8, "data", "viterbi")
+        iptr = dense_ptr(info, (R, cap), np.uint32, "info", "viterbi", "int32")
+        cptr = None if counts is None else dense_ptr(counts, (R,), np.uint32, "the frames' counts", "viterbi", "int32")
         self.ctx._ck(lib.hzsdr_viterbi_decode(self._h, fptr, fpitch, cptr, cap, dptr, dpitch, iptr))
         return data, info
 
