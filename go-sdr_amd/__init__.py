@@ -506,6 +506,15 @@ class Context:
         from .viterbi import ViterbiDecoder
         return ViterbiDecoder(self, kind, K, gens, data_bits, inv, pattern, termination, scale, crc, rows)
 
+    def ldpc(self, kind, code, received=None, head=0, data_bits=None, scale=1.0, level=1, max_iters=50, norm=12, offset=0, rows=1):
+        """The LDPC decoder bank (include/hzsdr_ldpc.h, ldpc.LdpcDecoder): frames of the binary LDPC code `code` (an
+        ldpc.LdpcCode: qc_code, regular_code, ldpc_systematic), soft float32 values (LDPC_SOFT_F32: the soft frame
+        bank's values as they are) or packed hard bits (LDPC_BITS: the frame sync bank's frames), decoded by at most
+        `max_iters` iterations of flooding min-sum in integers with the normalisation `norm` / 16 and the offset `offset`,
+        to `data_bits` data bits, the unsatisfied checks, the iterations run and a verdict per frame, over `rows` rows."""
+        from .ldpc import LdpcDecoder
+        return LdpcDecoder(self, kind, code, received, head, data_bits, scale, level, max_iters, norm, offset, rows)
+
     def reed_solomon(self, code, interleave=1, in_map=None, out_map=None, scramble=None, rows=1):
         """The Reed-Solomon decoder bank (include/hzsdr_rs.h, rs.ReedSolomon): frames of `interleave` symbol-interleaved
         codewords of `code` = (gfpoly, fcr, prim, nroots, n) -- CCSDS_RS_255_223, CCSDS_RS_255_239, DVB_RS_204_188 -- the
@@ -989,6 +998,9 @@ from .softframe import SoftFrames  # noqa: E402
 from ._capi import (HDLC_EVENT_ABORT, HDLC_EVENT_FLAG, HDLC_FORM_COMPLEX, HDLC_FORM_DIFF, HDLC_FORM_FCS16, HDLC_FORM_FCS32,  # noqa: E402
                     HDLC_FORM_KEEP_BAD, HDLC_FORM_MSB_FIRST, HDLC_MAX_BYTES, HDLC_MAX_ROWS)
 from .hdlc import Hdlc, hdlc_encode, hdlc_fcs16, hdlc_fcs32, hdlc_line  # noqa: E402
+from ._capi import (LDPC_BITS, LDPC_FORM_TABLES_CACHE, LDPC_FORM_TABLES_LDS, LDPC_MAX_BITS, LDPC_MAX_CHECKS, LDPC_MAX_DEGREE,  # noqa: E402
+                    LDPC_MAX_EDGES, LDPC_MAX_FRAMES, LDPC_MAX_ITERS, LDPC_MAX_ROWS, LDPC_MAX_VARIABLES, LDPC_SOFT_F32)
+from .ldpc import LdpcCode, LdpcDecoder, ldpc_encode, ldpc_systematic, qc_code, regular_code  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

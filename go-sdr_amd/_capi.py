@@ -413,6 +413,20 @@ VITERBI_BITS, VITERBI_SOFT_F32 = 1, 32
 VITERBI_TAIL, VITERBI_TRUNCATED = 0, 1
 VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_ldpc.h declares
+LDPC_SIGNATURES = {
+    "hzsdr_ldpc_create": (i32, [vp, i32, sz, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, sz, sz, f32, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                sz, pvp]),
+    "hzsdr_ldpc_decode": (i32, [vp, vp, sz, vp, sz, vp, sz, vp]),
+    "hzsdr_ldpc_sizes": (i32, [vp, psz, psz, psz, psz, psz, psz]),
+    "hzsdr_ldpc_plan": (i32, [vp, psz, psz, psz, C.POINTER(i32)]),
+    "hzsdr_ldpc_free": (i32, [vp]),
+}
+LDPC_MAX_ROWS, LDPC_MAX_CHECKS, LDPC_MAX_VARIABLES, LDPC_MAX_EDGES, LDPC_MAX_DEGREE, LDPC_MAX_BITS, LDPC_MAX_ITERS, LDPC_MAX_FRAMES = \
+    8192, 16384, 16384, 65536, 64, 8192, 255, 1 << 22
+LDPC_BITS, LDPC_SOFT_F32 = 1, 32
+LDPC_FORM_TABLES_LDS, LDPC_FORM_TABLES_CACHE = 1, 2
+
 # name -> (restype, argtypes); every symbol include/hzsdr_rs.h declares
 RS_SIGNATURES = {
     "hzsdr_rs_create": (i32, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, sz, sz, pvp]),
@@ -442,7 +456,8 @@ for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), 
                              *SYNTHESIZER_SIGNATURES.items(), *RESAMPLER_SIGNATURES.items(), *DEMOD_SIGNATURES.items(), *TUNER_SIGNATURES.items(),
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
                              *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items(),
-                             *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items(), *EQUALIZER_SIGNATURES.items(), *HDLC_SIGNATURES.items()):
+                             *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items(), *EQUALIZER_SIGNATURES.items(), *HDLC_SIGNATURES.items(),
+                             *LDPC_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

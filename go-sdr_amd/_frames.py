@@ -1,5 +1,5 @@
 """What the classes of the frame banks (framesync.FrameSync, hdlc.Hdlc, softframe.SoftFrames, viterbi.ViterbiDecoder,
-rs.ReedSolomon) share around a call: new blocks of slots where the input lives, the pointers of blocks and of dense
+ldpc.LdpcDecoder, rs.ReedSolomon) share around a call: new blocks of slots where the input lives, the pointers of blocks and of dense
 arrays behind their checks.  numpy in a HOST context; torch tensors on the context's device in a DEVICE context, where
 the ABI's unsigned 32- and 64-bit types are the signed types of the same width.  The errors carry the calling class's noun.
 

@@ -39,6 +39,7 @@
 #include "../../include/hzsdr_framesync.h"
 #include "../../include/hzsdr_hdlc.h"
 #include "../../include/hzsdr_viterbi.h"
+#include "../../include/hzsdr_ldpc.h"
 #include "../../include/hzsdr_rs.h"
 #include "../../include/hzsdr_softframe.h"
 #include "../../include/hzsdr_spectrum.h"
@@ -1714,6 +1715,94 @@ private:
     size_t rows_;
     size_t n_ = 0, fb_ = 0, t_ = 0, db_ = 0;
     hzsdr_viterbi *v_ = nullptr;
+};
+
+// The LDPC decoder bank (include/hzsdr_ldpc.h): frames of a binary LDPC code given by its parity-check matrix in
+// check-major compressed form -- soft floats (HZSDR_LDPC_SOFT_F32: the soft frame bank's values as they are) or packed
+// hard bits (HZSDR_LDPC_BITS: the frame sync bank's frames) -- decoded by flooding min-sum in integers to data_bits data
+// bits, the unsatisfied checks, the iterations run and a verdict per frame, over `rows` rows of `cap` frame slots.
+// Decode runs min(in_counts[r], cap) frames of every row (row r starts r * in_stride bytes or floats into `in`; dense
+// rows when in_stride is 0; every row has cap frames when in_counts is null).  The bank keeps no state.
+class Ldpc {
+public:
+    struct Frame {
+        std::vector<uint8_t> bytes;  // data bit k in byte k / 8, bit 7 - k % 8
+        uint32_t unsatisfied;        // checks of odd parity behind the last iteration run
+        uint32_t iters;              // iterations run
+        bool ok;                     // unsatisfied == 0
+    };
+    struct Config {
+        size_t variables = 0;
+        std::vector<uint32_t> row_ptr, col;  // checks + 1 entries; the variables of every check, ascending
+        size_t head = 0;
+        size_t received = 0;   // 0: every variable behind head
+        size_t data_bits = 0;  // 0: every variable
+        float scale = 1.0f;
+        unsigned level = 1, max_iters = 50, norm = 12, offset = 0;
+    };
+    Ldpc(const Context &x, int kind, const Config &c, size_t rows = 1) : x_(x), kind_(kind), rows_(rows) {
+        if (c.row_ptr.empty() || c.head > c.variables) throw std::invalid_argument("Ldpc: row_ptr has checks + 1 entries, head is at most variables");
+        check(x_.raw(), hzsdr_ldpc_create(x_.raw(), kind, c.row_ptr.size() - 1, c.variables, c.row_ptr.data(), c.col.data(), c.col.size(), c.head,
+                                          c.received ? c.received : c.variables - c.head, c.data_bits ? c.data_bits : c.variables, c.scale, c.level,
+                                          c.max_iters, c.norm, c.offset, rows, &l_));
+        check(x_.raw(), hzsdr_ldpc_sizes(l_, &n_, &fb_, &vars_, &checks_, &edges_, &db_));
+    }
+    ~Ldpc() { if (l_) hzsdr_ldpc_free(l_); }
+    Ldpc(const Ldpc &) = delete;
+    Ldpc &operator=(const Ldpc &) = delete;
+    std::vector<std::vector<Frame>> Decode(const void *in, size_t cap, size_t in_stride = 0, const uint32_t *in_counts = nullptr) {
+        std::vector<uint8_t> out(rows_ * cap * db_);
+        std::vector<uint32_t> info(rows_ * cap);
+        const size_t width = cap * (kind_ == HZSDR_LDPC_BITS ? fb_ : n_);
+        check(x_.raw(), hzsdr_ldpc_decode(l_, in, in_stride ? in_stride : width, in_counts, cap, out.data(), cap * db_, info.data()));
+        std::vector<std::vector<Frame>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            const size_t k = in_counts && in_counts[r] < cap ? in_counts[r] : cap;
+            for (size_t f = 0; f < k; f++) {
+                const uint8_t *p = out.data() + (r * cap + f) * db_;
+                const uint32_t w = info[r * cap + f];
+                rows[r].push_back({std::vector<uint8_t>(p, p + db_), w & 0xffffu, (w >> 16) & 0xffu, (w >> 31) != 0});
+            }
+        }
+        return rows;
+    }
+    // what FrameSync::Push returned, frame for frame (HZSDR_LDPC_BITS; a frame's bytes are the bank's FB)
+    std::vector<std::vector<Frame>> Decode(const std::vector<std::vector<FrameSync::Frame>> &frames) {
+        if (kind_ != HZSDR_LDPC_BITS || frames.size() != rows_) throw std::invalid_argument("Ldpc: hard-bit frames, a list per row");
+        size_t cap = 1;
+        for (const auto &row : frames) cap = row.size() > cap ? row.size() : cap;
+        std::vector<uint8_t> in(rows_ * cap * fb_, 0);
+        std::vector<uint32_t> counts(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            counts[r] = (uint32_t)frames[r].size();
+            for (size_t f = 0; f < frames[r].size(); f++) {
+                if (frames[r][f].bytes.size() != fb_) throw std::invalid_argument("Ldpc: a frame of another size");
+                std::copy(frames[r][f].bytes.begin(), frames[r][f].bytes.end(), in.begin() + (r * cap + f) * fb_);
+            }
+        }
+        return Decode(in.data(), cap, 0, counts.data());
+    }
+    // -> (frames per workgroup, threads per frame, LDS bytes of a frame's state, HZSDR_LDPC_FORM_*)
+    std::tuple<size_t, size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0, b = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_ldpc_plan(l_, &g, &t, &b, &f));
+        return {g, t, b, f};
+    }
+    size_t Rows() const { return rows_; }
+    size_t ReceivedBits() const { return n_; }
+    size_t FrameBytes() const { return fb_; }
+    size_t Variables() const { return vars_; }
+    size_t Checks() const { return checks_; }
+    size_t Edges() const { return edges_; }
+    size_t DataBytes() const { return db_; }
+
+private:
+    const Context &x_;
+    int kind_;
+    size_t rows_;
+    size_t n_ = 0, fb_ = 0, vars_ = 0, checks_ = 0, edges_ = 0, db_ = 0;
+    hzsdr_ldpc *l_ = nullptr;
 };
 
 // The Reed-Solomon decoder bank (include/hzsdr_rs.h): frames of `interleave` symbol-interleaved codewords over GF(2^8) --

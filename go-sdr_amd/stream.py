@@ -24,7 +24,7 @@ import numpy as np
 from . import (FMT_C64, FMT_I8, FMT_I16, FMT_U8, FFT_BACKWARD, FFT_FORWARD, Context, Ring,
                ErrDstTooSmall, ErrSampleFormatMismatch, ErrSampleFormatUnknown, HzsdrError,
                beamform_angles, beamform_angles_2d, fmt_of, format_size, length, make_samples)
-from ._capi import VITERBI_SOFT_F32
+from ._capi import LDPC_SOFT_F32, VITERBI_SOFT_F32
 
 READER_BLOCK = 32 * 1024  # stream/convert.go:43-44, decimate.go:41-42, downsample.go:54-55
 
@@ -1175,6 +1175,51 @@ def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK, soft=Non
             return [(c, p, i, m, ok, e, nf, good) for (_, p, i, m, ok), (c, e, nf, good) in zip(rows, rs.ragged(clean, verdict, got))]
         return read
     return decoded_frames(src, bank, decoder, cap, block, _behind=behind, soft=soft)
+
+
+# ---- frame sync -> soft frame bank -> the LDPC decoder bank (include/hzsdr_ldpc.h) ----
+
+def ldpc_frames(src, bank, soft, decoder, cap=4, block=READER_BLOCK):
+    """Push `src` through `bank` (a framesync.FrameSync) as frame_rows does, gather every push's payload floats with
+    `soft` (a softframe.SoftFrames beside `bank`: Context.soft_frames(bank)) and decode them with `decoder` (an
+    ldpc.LdpcDecoder of LDPC_SOFT_F32 input over the same rows, whose received positions N are the bank's payload
+    bits).  The blocks and their counts go from bank to bank as they are, in the context's memory space, with nothing
+    read in between.  Yields, per push, a list of `rows` tuples (data (k, DB) uint8, positions (k,), sync info (k,),
+    unsatisfied (k,), iters (k,), ok (k,)).  The checks are decoded_frames': a row that accepted more than `cap` frames
+    in one push raises ErrShortBuffer."""
+    if decoder.rows != bank.rows or decoder.N != bank.P:
+        raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
+    if soft.rows != bank.rows or soft.P != bank.P or soft.kind != bank.kind or soft.B != bank.B or list(soft.maps) != list(bank.maps):
+        raise ValueError("sdr: the soft frame bank's rows, kind, bits per symbol, payload bits and maps are the frame sync bank's")
+    if bank.diff != 0:
+        raise ValueError("sdr: a frame sync bank with a differential decoding has no soft counterpart")
+    if decoder.kind != LDPC_SOFT_F32:
+        raise ValueError("sdr: behind a soft frame bank the decoder takes LDPC_SOFT_F32 input")
+
+    def push(symbols, counts=None):
+        frames, positions, info, got = bank.push(symbols, counts, cap)
+        values, _ = soft.push(symbols, counts, positions, info, got, cap)
+        data, verdict = decoder.decode(values, got, cap)
+        if int(got.max()) > cap:
+            raise ErrShortBuffer("sdr: a row accepted more frames in one push than ldpc_frames keeps")
+        found = bank.ragged(frames, positions, info, got)
+        return [(d, p, i, u, it, ok) for (_, p, i), (d, u, it, ok) in zip(found, decoder.ragged(data, verdict, got))]
+    if isinstance(src, Reader):
+        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
+            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
+        buf = make_samples(src.sample_format(), block)
+        while True:
+            try:
+                k = src.read(buf)
+            except EOF:
+                break
+            if k:
+                yield push(buf[:k])
+        return
+    for b in src:
+        symbols, counts = b if isinstance(b, tuple) else (b, None)
+        if symbols.shape[-1]:
+            yield push(symbols, counts)
 
 
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------
