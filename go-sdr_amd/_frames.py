@@ -4,7 +4,9 @@ arrays behind their checks.  numpy in a HOST context; torch tensors on the conte
 the ABI's unsigned 32- and 64-bit types are the signed types of the same width.  The errors carry the calling class's noun.
 
 BitRingBank is what the classes of the two bit-ring banks (FrameSync, Hdlc) are built on: the object's life and its
-push (csrc/hz_framebank.h is the same layer in C).
+push (csrc/hz_framebank.h is the same layer in C).  DecoderBank is what the classes of the three decoder banks
+(ViterbiDecoder, LdpcDecoder, ReedSolomon) are built on: the create, sizes, plan, the dense decode and ragged
+(csrc/hz_decodebank.h).  Both stand on _Bank: the handle, its calls and its end.
 """
 import ctypes as C
 
@@ -64,25 +66,106 @@ def pitched_block_ptr(a, rows, cap, least, what, noun):
     return ptr, int(strides[0]) if rows > 1 else cap * pitch, pitch
 
 
-class BitRingBank:
-    """The context, the rows, the handle, and the calls hzsdr_<_c>_push, _plan, _positions, _reset and _free over them.
-    A subclass names its C prefix `_c`, the noun of its errors `_noun` and what its errors call a slot's extent,
-    `_extent`; it sets `kind` and `frame_bytes`, a slot's bytes, creates `_h` behind _open(), and keeps push() and plan()
-    for their doc strings."""
-    _c = _noun = _extent = None
+class _Bank:
+    """The context, the rows and the handle `_h` of a bank whose C functions are hzsdr_<_c>_*, the calls over them and
+    the object's end.  A subclass names `_c` and the noun of its errors, `_noun`."""
+    _c = _noun = None
 
-    def _open(self, ctx, kind, rows):
-        self.ctx, self.kind, self.rows, self._h = ctx, int(kind), int(rows), C.c_void_p()
+    def _open(self, ctx, rows):
+        self.ctx, self.rows, self._h = ctx, int(rows), C.c_void_p()
         if self.rows <= 0:
             raise ErrInvalidArgument(f"{self._noun}: rows is at least 1")
 
     def _call(self, name, *args):
         self.ctx._ck(getattr(lib, f"hzsdr_{self._c}_{name}")(self._h, *args))
 
+    def _sizes(self, name, n):
+        """the `n` size_t results of hzsdr_<_c>_<name>"""
+        v = [C.c_size_t(0) for _ in range(n)]
+        self._call(name, *[C.byref(x) for x in v])
+        return tuple(x.value for x in v)
+
     def _plan(self):
         g, t, r, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
         self._call("plan", C.byref(g), C.byref(t), C.byref(r), C.byref(f))
         return g.value, t.value, r.value, f.value
+
+    def close(self):
+        if self._h:
+            getattr(lib, f"hzsdr_{self._c}_free")(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class DecoderBank(_Bank):
+    """What the classes of the three decoder banks (ViterbiDecoder, LdpcDecoder, ReedSolomon) are built on
+    (csrc/hz_decodebank.h is the same layer in C): hzsdr_<_c>_create behind _open(), the dense decode of the banks that
+    take hard bits (`kind` is `_bits`: uint8 frames of `frame_bytes`) or soft float32 values (frames of `N`), and ragged()
+    over _fields(info words) -> what a frame's tuple holds behind its data.  A subclass keeps decode(), ragged(), plan()
+    and sizes() for their doc strings."""
+    _bits = None
+
+    def _create(self, *args):
+        self.ctx._ck(getattr(lib, f"hzsdr_{self._c}_create")(self.ctx._h, *args, self.rows, C.byref(self._h)))
+
+    def _out(self, frames, cap, out):
+        """a call's (data, info): new ones where `frames` lives when `out` is None"""
+        if out is None:
+            out = (new_like((self.rows, cap, self.data_bytes), np.uint8, frames), new_like((self.rows, cap), np.uint32, frames))
+        return out
+
+    def _tail_ptrs(self, info, counts, cap):
+        """the pointers of a call's info and counts"""
+        noun, R = self._noun, self.rows
+        iptr = dense_ptr(info, (R, cap), np.uint32, "info", noun, "int32")
+        return iptr, None if counts is None else dense_ptr(counts, (R,), np.uint32, "the frames' counts", noun, "int32")
+
+    def _decode(self, frames, counts, cap, out):
+        noun, R = self._noun, self.rows
+        width, dtype = (self.frame_bytes, np.uint8) if self.kind == self._bits else (self.N, np.float32)
+        if frames.ndim == 2 and R == 1:
+            frames = frames[None]
+        if frames.ndim != 3:
+            raise ValueError(f"{noun}: frames are (rows, cap, FB or N)")
+        cap = int(frames.shape[1]) if cap is None else int(cap)
+        fptr, fpitch = block_ptr(frames, (R, cap, width), dtype, "frames", noun)
+        data, info = self._out(frames, cap, out)
+        dptr, dpitch = block_ptr(data, (R, cap, self.data_bytes), np.uint8, "data", noun)
+        iptr, cptr = self._tail_ptrs(info, counts, cap)
+        self._call("decode", fptr, fpitch, cptr, cap, dptr, dpitch, iptr)
+        return data, info
+
+    def _ragged(self, data, info, counts):
+        if _is_torch(data):
+            data, info = data.cpu().numpy(), info.cpu().numpy()
+            counts = None if counts is None else counts.cpu().numpy()
+        if data.ndim == 2:
+            data, info = data[None], np.asarray(info).reshape(1, -1)
+        cap = data.shape[1]
+        info = np.asarray(info).view(np.uint32)
+        got = np.full(self.rows, cap, np.uint32) if counts is None else np.asarray(counts).reshape(-1).view(np.uint32)
+        out = []
+        for r, c in enumerate(got):
+            k = min(int(c), cap)
+            out.append((data[r, :k, :self.data_bytes].copy(), *self._fields(info[r, :k])))
+        return out
+
+
+class BitRingBank(_Bank):
+    """The context, the rows, the handle, and the calls hzsdr_<_c>_push, _plan, _positions, _reset and _free over them.
+    A subclass names its C prefix `_c`, the noun of its errors `_noun` and what its errors call a slot's extent,
+    `_extent`; it sets `kind` and `frame_bytes`, a slot's bytes, creates `_h` behind _open(), and keeps push() and plan()
+    for their doc strings."""
+    _extent = None
+
+    def _open(self, ctx, kind, rows):
+        self.kind = int(kind)
+        super()._open(ctx, rows)
 
     def positions(self):
         """Symbols consumed per row: uint64 (rows,), behind every push so far."""
@@ -114,14 +197,3 @@ class BitRingBank:
 
     def reset(self):
         self._call("reset")
-
-    def close(self):
-        if self._h:
-            getattr(lib, f"hzsdr_{self._c}_free")(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()

@@ -194,7 +194,8 @@ inline int stage_out_rows_preserved(Stage &st, int slot, void *p, size_t R, size
 }
 
 // ---- what the bank objects (spectrum, channelizer, synthesizer, resampler, demodulator, tuner, channel bank,
-// covariance, IIR, symbol timing, carrier recovery, AGC, frame sync, Viterbi) share on the host ----
+// covariance, IIR, symbol timing, carrier recovery, AGC, equalizer, frame sync, soft frame, HDLC, Viterbi, Reed-Solomon,
+// LDPC) share on the host ----
 
 // The checks of a call that writes `count` outputs into each of `rows` rows, before anything is launched; tile: outputs
 // per workgroup of the kernel whose grid the count sets (0: no such limit).
@@ -230,5 +231,7 @@ inline int bank_upload(hzsdr_ctx *ctx, void *dst_dev, const void *src, size_t by
 
 // (what the four row-wave banks -- IIR, symbol timing, carrier recovery, AGC -- share on top, a state array that the
 // caller may read and replace and parameter sets with a row per row, is hz_loopbank.h)
+// (what the two bit-ring banks -- frame sync, HDLC -- share on top is hz_framebank.h; what the three decoder banks --
+// Viterbi, Reed-Solomon, LDPC -- share, the call over rows of frame slots with a count per row, is hz_decodebank.h)
 
 }  // namespace hz

@@ -1,0 +1,76 @@
+// hz_decodebank.h -- the host side of the decoder banks (hz_viterbi.hip, hz_ldpc.hip, hz_rs.hip): what their objects
+// hold alike and the calls over it, around the kernels.  A bank's object derives from Bank and adds its configuration,
+// its geometry, its device tables and, as a static, the noun that starts its messages.  A bank decodes
+// min(counts[r], cap) frames of every row into a block of data bytes and an info word per slot, leaves every other slot
+// as it was and keeps no state; the arithmetic of a call is hz_decodebank_plan.h.  Nothing here knows which bank it serves.
+#pragma once
+#include <initializer_list>
+#include <string>
+
+#include "hz_common.h"
+#include "hz_decodebank_plan.h"
+
+namespace hz {
+// (hidden: the instantiations below add nothing to the library's dynamic symbols)
+namespace db __attribute__((visibility("hidden"))) {
+
+struct Bank {
+    hzsdr_ctx *ctx = nullptr;
+    uint32_t R = 0;
+};
+
+template <class F> std::string who(const char *msg) { return std::string(F::noun) + ": " + msg; }
+
+// the checks in front of a create (a bank of one input kind passes kBits)
+template <class F> int check_create(hzsdr_ctx *ctx, int kind, size_t rows, F **out) {
+    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (kind != dbp::kBits && kind != dbp::kSoftF32) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, who<F>("packed bits or soft float32 input"));
+    if (rows == 0 || rows > dbp::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, who<F>("1 ... 8192 rows"));
+    return HZSDR_OK;
+}
+
+// a device table of `bytes` bytes (none: skipped) behind *dev, filled from `host` (null: left as it comes)
+struct Table {
+    void **dev;
+    const void *host;
+    size_t bytes;
+};
+// every table's memory first, then the contents; `what` names the create in a HIP error
+inline int upload(hzsdr_ctx *ctx, const char *what, std::initializer_list<Table> tables) {
+    for (const Table &t : tables) {
+        const hipError_t e = t.bytes ? hipMalloc(t.dev, t.bytes) : hipSuccess;
+        if (e != hipSuccess) return hip_fail(ctx, e, what, __FILE__, __LINE__);
+    }
+    for (const Table &t : tables)
+        if (t.bytes && t.host) HZ_TRY(bank_upload(ctx, *t.dev, t.host, t.bytes));
+    return HZSDR_OK;
+}
+
+// A call: the checks in their order, the rows staged (`isz`: the bytes of an input element), launch(FrameArgs, cap,
+// slots) -> status with the leading part of the kernel's arguments filled in, the rows brought back.
+template <class F, class Launch>
+int decode(F *f, const dbp::Slots &s, size_t isz, const dbp::Call &c, const uint32_t *in_counts, uint32_t *info, Launch launch) {
+    hzsdr_ctx *ctx = f->ctx;
+    const char *why = nullptr;
+    const int bad = dbp::check_call(s, c, &why);
+    if (bad) return fail(ctx, bad == dbp::kDstTooSmall ? HZSDR_ERR_DST_TOO_SMALL : HZSDR_ERR_INVALID_ARGUMENT, who<F>(why));
+    HZ_TRY(enter(ctx));
+    Stage st(ctx);
+    const size_t R = c.rows, cap = c.cap;
+    const size_t iw = (cap - 1) * c.in_pitch + s.in_width, ow = (cap - 1) * c.out_pitch + s.out_width;
+    const void *din, *dic = nullptr;
+    void *dout = (void *)c.out, *dinfo = info;
+    size_t istride = R > 1 ? c.in_stride : iw, ostride = R > 1 ? c.out_stride : ow;
+    HZ_TRY(st.in_rows(0, (const void *)c.in, R, iw, istride, isz, &din, &istride));
+    if (in_counts) HZ_TRY(st.in(1, in_counts, R * sizeof(uint32_t), &dic));
+    // the slots behind a row's count, and what lies between a slot's data and the next slot, stay as they are
+    HZ_TRY(stage_out_rows_preserved(st, 2, (void *)c.out, R, ow, c.out_stride, 1, &dout, &ostride));
+    HZ_TRY(st.out_preserve(3, info, R * cap * sizeof(uint32_t), &dinfo));
+    HZ_TRY(launch(dbp::FrameArgs{din, istride, (const uint32_t *)dic, (uint8_t *)dout, ostride, (uint32_t *)dinfo}, (uint32_t)cap, (uint32_t)(R * cap)));
+    HZ_HIP(ctx, hipGetLastError());
+    return st.finish();
+}
+
+}  // namespace db
+}  // namespace hz

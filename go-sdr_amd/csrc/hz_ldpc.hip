@@ -24,13 +24,13 @@
 
 #include "hz_chain_host.h"
 #include "../../include/hzsdr_ldpc.h"
+#include "hz_decodebank.h"
 #include "hz_ldpc_math.h"
 #include "hz_ldpc_plan.h"
 
-struct hzsdr_ldpc {
-    hzsdr_ctx *ctx;
+struct hzsdr_ldpc : hz::db::Bank {
+    static constexpr const char *noun = "ldpc";
     hz::lp::Config q;
-    uint32_t R;
     hz::lp::Geom g{};
     uint32_t *row_ptr = nullptr, *vptr = nullptr;
     uint16_t *col = nullptr, *vedge = nullptr;
@@ -38,13 +38,7 @@ struct hzsdr_ldpc {
 
 namespace hz {
 
-struct LdArgs {
-    const void *in;
-    size_t in_stride;  // bytes (hard bits) or floats
-    const uint32_t *in_counts;
-    uint8_t *out;
-    size_t out_stride;  // bytes
-    uint32_t *info;
+struct LdArgs : dbp::FrameArgs {
     const uint32_t *row_ptr, *vptr;
     const uint16_t *col, *vedge;
     uint32_t cap, slots;  // slots: R * cap
@@ -83,9 +77,8 @@ __global__ __launch_bounds__(lp::kMaxThreads) void ldpc_frames_kernel(LdArgs a) 
         for (uint32_t k = 0; k < a.G; k++) {
             const uint32_t slot = base + k;
             if (slot >= a.slots) break;
-            const uint32_t rr = slot / a.cap, ff = slot - rr * a.cap;
-            const uint32_t cnt = a.in_counts ? a.in_counts[rr] : a.cap;
-            const bool live = ff < (cnt < a.cap ? cnt : a.cap);
+            uint32_t rr, ff;
+            const bool live = dbp::slot_frame(slot, a.cap, a.in_counts, &rr, &ff);
             any |= live;
             if (k == g) act = live, row = rr, f = ff;
         }
@@ -181,8 +174,6 @@ __global__ __launch_bounds__(lp::kMaxThreads) void ldpc_frames_kernel(LdArgs a) 
     }
 }
 
-static size_t ld_in_width(const hzsdr_ldpc *l, size_t cap) { return cap * (l->q.kind == lp::kBits ? l->g.FB : l->g.N); }
-
 }  // namespace hz
 
 extern "C" {
@@ -191,16 +182,13 @@ int hzsdr_ldpc_create(hzsdr_ctx *ctx, int kind, size_t checks, size_t variables,
                       size_t head, size_t received, size_t data_bits, float scale, unsigned level, unsigned max_iters, unsigned norm,
                       unsigned offset, size_t rows, hzsdr_ldpc **out) {
     using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (kind != HZSDR_LDPC_BITS && kind != HZSDR_LDPC_SOFT_F32) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "ldpc: packed bits or soft float32 input");
-    if (rows == 0 || rows > lp::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "ldpc: 1 ... 8192 rows");
+    HZ_TRY(db::check_create(ctx, kind, rows, out));
     if (!row_ptr || !col) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "ldpc: null row_ptr or col");
     lp::Config q{kind, checks, variables, edges, head, received, data_bits, scale, level, max_iters, norm, offset};
     if (const char *why = lp::check_config(q)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string("ldpc: ") + why);
     if (const char *why = lp::check_code(q, row_ptr, col)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string("ldpc: ") + why);
     HZ_TRY(enter(ctx));
-    hzsdr_ldpc *l = new hzsdr_ldpc{ctx, q, (uint32_t)rows};
+    hzsdr_ldpc *l = new hzsdr_ldpc{{ctx, (uint32_t)rows}, q};
     l->g = lp::geom(q);
     auto undo = [&](int rc) {
         hzsdr_ldpc_free(l);
@@ -208,15 +196,11 @@ int hzsdr_ldpc_create(hzsdr_ctx *ctx, int kind, size_t checks, size_t variables,
     };
     lp::Tables t;
     lp::build_tables(q, row_ptr, col, t);
-    hipError_t e = hipMalloc((void **)&l->row_ptr, t.row_ptr.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&l->vptr, t.vptr.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&l->col, t.col.size() * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&l->vedge, t.vedge.size() * sizeof(uint16_t));
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "ldpc_create", __FILE__, __LINE__));
-    int rc = bank_upload(ctx, l->row_ptr, t.row_ptr.data(), t.row_ptr.size() * sizeof(uint32_t));
-    if (rc == HZSDR_OK) rc = bank_upload(ctx, l->vptr, t.vptr.data(), t.vptr.size() * sizeof(uint32_t));
-    if (rc == HZSDR_OK) rc = bank_upload(ctx, l->col, t.col.data(), t.col.size() * sizeof(uint16_t));
-    if (rc == HZSDR_OK) rc = bank_upload(ctx, l->vedge, t.vedge.data(), t.vedge.size() * sizeof(uint16_t));
+    const int rc = db::upload(ctx, "ldpc_create",
+                              {{(void **)&l->row_ptr, t.row_ptr.data(), t.row_ptr.size() * sizeof(uint32_t)},
+                               {(void **)&l->vptr, t.vptr.data(), t.vptr.size() * sizeof(uint32_t)},
+                               {(void **)&l->col, t.col.data(), t.col.size() * sizeof(uint16_t)},
+                               {(void **)&l->vedge, t.vedge.data(), t.vedge.size() * sizeof(uint16_t)}});
     if (rc != HZSDR_OK) return undo(rc);
     *out = l;
     return HZSDR_OK;
@@ -226,46 +210,28 @@ int hzsdr_ldpc_decode(hzsdr_ldpc *l, const void *in, size_t in_stride, const uin
                       uint32_t *info) {
     using namespace hz;
     if (!l) return HZSDR_ERR_INVALID_ARGUMENT;
-    hzsdr_ctx *ctx = l->ctx;
-    const size_t R = l->R, DB = l->g.DB;
-    if (cap == 0 || cap > lp::kMaxFrames / R) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "ldpc: cap is at least 1 and rows * cap at most 2^22");
-    if (!in || !out || !info) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "ldpc: null in, out or info");
-    const size_t iw = ld_in_width(l, cap), ow = cap * DB, isz = l->q.kind == lp::kBits ? 1 : sizeof(float);
-    if (R > 1 && in_stride < iw) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "ldpc: in_stride is below cap frames");
-    if (R > 1 && out_stride < ow) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "ldpc: out_stride is below cap frames");
-    HZ_TRY(enter(ctx));
-    Stage st(ctx);
-    const void *din, *dic = nullptr;
-    void *dout = out, *dinfo = info;
-    size_t istride = R > 1 ? in_stride : iw, ostride = R > 1 ? out_stride : ow;
-    HZ_TRY(st.in_rows(0, in, R, iw, istride, isz, &din, &istride));
-    if (in_counts) HZ_TRY(st.in(1, in_counts, R * sizeof(uint32_t), &dic));
-    // the slots behind a row's count, and a frame's neighbours, stay as they are
-    HZ_TRY(stage_out_rows_preserved(st, 2, out, R, ow, out_stride, 1, &dout, &ostride));
-    HZ_TRY(st.out_preserve(3, info, R * cap * sizeof(uint32_t), &dinfo));
     const lp::Config &q = l->q;
     const lp::Geom &g = l->g;
-    LdArgs a{};
-    a.in = din, a.in_stride = istride, a.in_counts = (const uint32_t *)dic, a.out = (uint8_t *)dout, a.out_stride = ostride, a.info = (uint32_t *)dinfo;
-    a.row_ptr = l->row_ptr, a.vptr = l->vptr, a.col = l->col, a.vedge = l->vedge;
-    a.cap = (uint32_t)cap, a.slots = (uint32_t)(R * cap);
-    a.m = g.m, a.n = g.n, a.E = g.E, a.head = g.head, a.N = g.N, a.D = g.D, a.FB = g.FB, a.DB = g.DB, a.T = g.T, a.G = g.G;
-    a.off_rowptr = g.off_rowptr, a.off_vptr = g.off_vptr, a.off_col = g.off_col, a.off_vedge = g.off_vedge;
-    a.off_frames = g.off_frames, a.frame_bytes = g.frame_bytes, a.off_q = g.off_q, a.off_r = g.off_r;
-    a.scale = q.scale, a.level = (int)q.level, a.max_iters = q.max_iters, a.a = q.a, a.beta = q.beta;
-    const dim3 grid(lp::groups_for(g, R * cap)), block(g.G * g.T);
-    const bool soft = q.kind == lp::kSoftF32, tlds = g.form == lp::kFormTablesLds;
-    hipStream_t s = ctx->stream;
-    if (soft && tlds)
-        HZ_TRY(launch_fv(ldpc_frames_kernel<true, true>, grid, block, g.lds_bytes, s, a));
-    else if (soft)
-        HZ_TRY(launch_fv(ldpc_frames_kernel<true, false>, grid, block, g.lds_bytes, s, a));
-    else if (tlds)
-        HZ_TRY(launch_fv(ldpc_frames_kernel<false, true>, grid, block, g.lds_bytes, s, a));
-    else
-        HZ_TRY(launch_fv(ldpc_frames_kernel<false, false>, grid, block, g.lds_bytes, s, a));
-    HZ_HIP(ctx, hipGetLastError());
-    return st.finish();
+    const bool bits = q.kind == lp::kBits;
+    const size_t w = bits ? g.FB : g.N;
+    const dbp::Call c{(uintptr_t)in, (uintptr_t)out, in_stride, w, out_stride, g.DB, cap, l->R, info != nullptr};
+    return db::decode(l, dbp::dense(w, g.DB), bits ? 1 : sizeof(float), c, in_counts, info, [&](const dbp::FrameArgs &fa, uint32_t cap, uint32_t slots) {
+        LdArgs a{};
+        static_cast<dbp::FrameArgs &>(a) = fa;
+        a.row_ptr = l->row_ptr, a.vptr = l->vptr, a.col = l->col, a.vedge = l->vedge;
+        a.cap = cap, a.slots = slots;
+        a.m = g.m, a.n = g.n, a.E = g.E, a.head = g.head, a.N = g.N, a.D = g.D, a.FB = g.FB, a.DB = g.DB, a.T = g.T, a.G = g.G;
+        a.off_rowptr = g.off_rowptr, a.off_vptr = g.off_vptr, a.off_col = g.off_col, a.off_vedge = g.off_vedge;
+        a.off_frames = g.off_frames, a.frame_bytes = g.frame_bytes, a.off_q = g.off_q, a.off_r = g.off_r;
+        a.scale = q.scale, a.level = (int)q.level, a.max_iters = q.max_iters, a.a = q.a, a.beta = q.beta;
+        const dim3 grid(lp::groups_for(g, slots)), block(g.G * g.T);
+        const bool soft = !bits, tlds = g.form == lp::kFormTablesLds;
+        hipStream_t s = l->ctx->stream;
+        if (soft && tlds) return launch_fv(ldpc_frames_kernel<true, true>, grid, block, g.lds_bytes, s, a);
+        if (soft) return launch_fv(ldpc_frames_kernel<true, false>, grid, block, g.lds_bytes, s, a);
+        if (tlds) return launch_fv(ldpc_frames_kernel<false, true>, grid, block, g.lds_bytes, s, a);
+        return launch_fv(ldpc_frames_kernel<false, false>, grid, block, g.lds_bytes, s, a);
+    });
 }
 
 int hzsdr_ldpc_sizes(const hzsdr_ldpc *l, size_t *N, size_t *FB, size_t *n, size_t *m, size_t *E, size_t *DB) {

@@ -8,22 +8,15 @@
 #include <stdint.h>
 
 #include "hz_plan.h"
+#include "hz_received.h"
 
 namespace hz {
 namespace lm {
 
 constexpr int kClamp = 127;
 
-// ---- one received value -> q in -127 ... 127 (0: an erasure) ----
-// each step is ONE float32 operation; a NaN gives 0, +-infinity +-127, -0 gives 0 (the Viterbi bank's quantiser)
-HZ_HD int quantise(float x, float scale) {
-    const float y = x * scale;
-    if (y != y) return 0;
-    return (int)rintf(fminf(fmaxf(y, -127.0f), 127.0f));
-}
-HZ_HD int hard(uint32_t bit, int level) { return bit ? level : -level; }
-// bit k (0: the first) of a frame of packed bits, most significant bit first
-HZ_HD uint32_t packed_bit(const uint8_t *bytes, uint32_t k) { return (uint32_t)(bytes[k >> 3] >> (7u - (k & 7u))) & 1u; }
+// ---- one received value -> q in -127 ... 127 (0: an erasure): hz_received.h; a hard bit is +-level ----
+using rx::quantise, rx::hard, rx::packed_bit;
 
 // ---- step 1: what an edge sends to its check ----
 HZ_HD int to_check(int P, int r) {

@@ -22,16 +22,16 @@
 
 #include <vector>
 
+#include "hz_decodebank_plan.h"
 #include "hz_ldpc_math.h"
 
 namespace hz {
 namespace lp {
 
-constexpr int kBits = 1, kSoftF32 = 32;                  // HZSDR_LDPC_BITS, HZSDR_LDPC_SOFT_F32
+using dbp::kBits, dbp::kSoftF32, dbp::kMaxRows, dbp::kMaxFrames;  // HZSDR_LDPC_BITS, HZSDR_LDPC_SOFT_F32
 constexpr int kFormTablesLds = 1, kFormTablesCache = 2;  // HZSDR_LDPC_FORM_*
 constexpr uint32_t kMaxChecks = 16384, kMaxVars = 16384, kMaxEdges = 65536, kMaxDegree = 64, kMinCheckDegree = 2;
-constexpr uint32_t kMaxBits = 8192, kMaxRows = 8192, kMaxIters = 255, kMaxNorm = 16, kMaxOffset = 126, kMaxLevel = 127;
-constexpr size_t kMaxFrames = (size_t)1 << 22;
+constexpr uint32_t kMaxBits = 8192, kMaxIters = 255, kMaxNorm = 16, kMaxOffset = 126, kMaxLevel = 127;
 constexpr uint32_t kLanes = 64, kMaxThreads = 1024, kMaxGroup = 8, kMaxGrid = 2048;
 constexpr uint32_t kHeadBytes = 2 * kMaxGroup * 4;
 constexpr size_t kLdsBudget = 160 * 1024;
@@ -54,7 +54,7 @@ inline const char *check_config(const Config &q) {
     if (q.max_iters < 1 || q.max_iters > kMaxIters) return "1 <= max_iters <= 255";
     if (q.a < 1 || q.a > kMaxNorm) return "1 <= norm <= 16";
     if (q.beta > kMaxOffset) return "offset <= 126";
-    if (q.kind == kSoftF32 && !(q.scale > 0.0f && q.scale <= 3.402823466e38f)) return "scale is finite and positive";
+    if (const char *why = q.kind == kSoftF32 ? dbp::check_scale(q.scale) : nullptr) return why;
     if (q.kind == kBits && (q.level < 1 || q.level > kMaxLevel)) return "1 <= level <= 127";
     return nullptr;
 }
@@ -120,7 +120,7 @@ struct Geom {
 inline Geom geom(const Config &q) {
     Geom g{};
     g.m = (uint32_t)q.m, g.n = (uint32_t)q.n, g.E = (uint32_t)q.E, g.head = (uint32_t)q.head, g.N = (uint32_t)q.N, g.D = (uint32_t)q.D;
-    g.FB = (g.N + 7) / 8, g.DB = (g.D + 7) / 8;
+    g.FB = dbp::packed_bytes(g.N), g.DB = dbp::packed_bytes(g.D);
     uint32_t want = g.m > (g.n + 1) / 2 ? g.m : (g.n + 1) / 2;
     g.T = up(want, kLanes);
     if (g.T > kMaxThreads) g.T = kMaxThreads;

@@ -19,6 +19,7 @@
 
 #include <vector>
 
+#include "hz_decodebank_plan.h"
 #include "hz_rowwave_plan.h"
 #include "hz_rs_math.h"
 
@@ -26,9 +27,9 @@ namespace hz {
 namespace rsp {
 
 using rw::kLanes, rw::kLdsBudget;
+using dbp::kMaxRows, dbp::kMaxFrames;
 
-constexpr uint32_t kMinRoots = 2, kMaxRoots = rsm::kMaxRoots, kMaxN = 255, kMaxInterleave = 8, kMaxScramble = 2040, kMaxRows = 8192;
-constexpr size_t kMaxFrames = (size_t)1 << 22;
+constexpr uint32_t kMinRoots = 2, kMaxRoots = rsm::kMaxRoots, kMaxN = 255, kMaxInterleave = 8, kMaxScramble = 2040;
 constexpr uint32_t kTabExp = 0, kTabLog = kTabExp + rsm::kExpSize, kTabIn = kTabLog + rsm::kLogSize, kTabOut = kTabIn + 256, kTabBytes = kTabOut + 256;
 constexpr uint32_t kWaveSyn = 0, kWaveLam = 64, kWaveOmg = 128, kWaveBytes = 192;
 constexpr uint32_t kMaxGroups = 65536;   // the grid at most; a workgroup walks on from slot to slot
@@ -117,33 +118,10 @@ inline bool build_block(const Config &q, const Geom &g, const uint8_t *in_map, c
 }
 
 // ---- a call ----
-constexpr int kOk = 0, kInvalid = 1, kDstTooSmall = 2;
-struct Call {
-    uintptr_t in, out;
-    size_t in_stride, in_pitch, out_stride, out_pitch, cap, rows;
-    bool has_info;
-};
-// kOk, or what to refuse the call with and why (*why)
-inline int check_call(const Geom &g, const Call &c, const char **why) {
-    *why = nullptr;
-    if (c.cap == 0 || c.cap > kMaxFrames / c.rows) return *why = "cap is at least 1 and rows * cap at most 2^22", kInvalid;
-    if (!c.in || !c.out || !c.has_info) return *why = "null in, out or info", kInvalid;
-    if (c.in_pitch < g.F) return *why = "in_pitch is below the frame bytes", kInvalid;
-    if (c.out_pitch < g.IK) return *why = "out_pitch is below the data bytes", kInvalid;
-    if (c.rows > 1 && c.in_stride / c.cap < c.in_pitch) return *why = "in_stride is below cap frame slots", kInvalid;
-    if (c.rows > 1 && c.out_stride / c.cap < c.out_pitch) return *why = "out_stride is below cap frame slots", kDstTooSmall;
-    // (strides and pitches beyond any address space are refused here, before they are multiplied)
-    const size_t lim = (size_t)1 << 40;
-    if (c.in_pitch > lim || c.out_pitch > lim || (c.rows > 1 && (c.in_stride > lim || c.out_stride > lim))) return *why = "a pitch or stride beyond 2^40", kInvalid;
-    const size_t ispan = (c.rows - 1) * (c.rows > 1 ? c.in_stride : 0) + (c.cap - 1) * c.in_pitch + g.F;
-    const size_t ospan = (c.rows - 1) * (c.rows > 1 ? c.out_stride : 0) + (c.cap - 1) * c.out_pitch + g.IK;
-    if (c.in == c.out) {
-        if (c.in_pitch != c.out_pitch || (c.rows > 1 && c.in_stride != c.out_stride)) return *why = "in place takes equal strides and pitches", kInvalid;
-    } else if (c.in < c.out + ospan && c.out < c.in + ispan) {
-        return *why = "in and out overlap in part", kInvalid;
-    }
-    return kOk;
-}
+// (hz_decodebank_plan.h's, over slots with pitches in bytes; in place, or apart)
+using dbp::kOk, dbp::kInvalid, dbp::kDstTooSmall, dbp::Call;
+inline dbp::Slots slots(const Geom &g) { return {g.F, g.IK, true, "in_stride is below cap frame slots", "out_stride is below cap frame slots"}; }
+inline int check_call(const Geom &g, const Call &c, const char **why) { return dbp::check_call(slots(g), c, why); }
 
 // ---- the kernel's index maps ----
 // where symbol p of codeword i lies in the frame

@@ -23,14 +23,14 @@
 
 #include "hz_chain_host.h"
 #include "../../include/hzsdr_viterbi.h"
+#include "hz_decodebank.h"
 #include "hz_rowwave.h"
 #include "hz_viterbi_math.h"
 #include "hz_viterbi_plan.h"
 
-struct hzsdr_viterbi {
-    hzsdr_ctx *ctx;
+struct hzsdr_viterbi : hz::db::Bank {
+    static constexpr const char *noun = "viterbi";
     hz::vp::Config q;
-    uint32_t R;
     hz::vp::Geom g{};
     uint16_t *idx = nullptr;       // T n entries
     uint32_t *crc_table = nullptr;  // 256 entries (C != 0)
@@ -39,13 +39,7 @@ struct hzsdr_viterbi {
 
 namespace hz {
 
-struct VtArgs {
-    const void *in;
-    size_t in_stride;  // bytes (hard bits) or floats
-    const uint32_t *in_counts;
-    uint8_t *out;
-    size_t out_stride;  // bytes
-    uint32_t *info;
+struct VtArgs : dbp::FrameArgs {
     const uint16_t *idx;
     const uint32_t *crc_table;
     uint64_t *scratch;
@@ -93,9 +87,9 @@ __global__ __launch_bounds__(vp::kLanes) void viterbi_frames_kernel(VtArgs a) {
         uint32_t r = 0, f = 0;
         bool act = false;
         if (slot < a.slots) {
-            r = slot / a.cap, f = slot - r * a.cap;
-            const uint32_t cnt = a.in_counts ? a.in_counts[r] : a.cap;
-            act = f < (cnt < a.cap ? cnt : a.cap);
+            uint32_t rr, ff;  // (locals keep the instruction stream of the lines written out, move for move)
+            act = dbp::slot_frame(slot, a.cap, a.in_counts, &rr, &ff);
+            r = rr, f = ff;
         }
         if (__ballot(act) == 0) continue;  // wave-uniform
         const uint8_t *fbits = (const uint8_t *)a.in + (size_t)r * a.in_stride + (size_t)f * a.FB;
@@ -244,8 +238,6 @@ __global__ __launch_bounds__(vp::kLanes) void viterbi_frames_kernel(VtArgs a) {
     }
 }
 
-static size_t vt_in_width(const hzsdr_viterbi *v, size_t cap) { return cap * (v->q.kind == vp::kBits ? v->g.FB : v->g.N); }
-
 template <int SPL> static int vt_launch(hzsdr_viterbi *v, const VtArgs &a, dim3 grid) {
     const dim3 block(vp::kLanes);
     const size_t lds = v->g.lds_bytes;
@@ -265,16 +257,13 @@ int hzsdr_viterbi_create(hzsdr_ctx *ctx, int kind, unsigned K, unsigned n, const
                          unsigned pattern_bits, int termination, size_t data_bits, float scale, unsigned crc_bits, uint32_t crc_poly,
                          uint32_t crc_init, uint32_t crc_xorout, size_t rows, hzsdr_viterbi **out) {
     using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (kind != HZSDR_VITERBI_BITS && kind != HZSDR_VITERBI_SOFT_F32) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "viterbi: packed bits or soft float32 input");
-    if (rows == 0 || rows > vp::kMaxRows) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "viterbi: 1 ... 8192 rows");
+    HZ_TRY(db::check_create(ctx, kind, rows, out));
     if (!gens) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "viterbi: null generators");
     vp::Config q{kind, K, n, {0, 0, 0, 0}, inv, pattern, pattern_bits, termination, data_bits, scale, crc_bits, crc_poly, crc_init, crc_xorout};
     for (unsigned j = 0; j < n && j < vp::kMaxRate; j++) q.gens[j] = gens[j];
     if (const char *why = vp::check_config(q)) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, std::string("viterbi: ") + why);
     HZ_TRY(enter(ctx));
-    hzsdr_viterbi *v = new hzsdr_viterbi{ctx, q, (uint32_t)rows};
+    hzsdr_viterbi *v = new hzsdr_viterbi{{ctx, (uint32_t)rows}, q};
     v->g = vp::geom(q);
     auto undo = [&](int rc) {
         hzsdr_viterbi_free(v);
@@ -282,16 +271,12 @@ int hzsdr_viterbi_create(hzsdr_ctx *ctx, int kind, unsigned K, unsigned n, const
     };
     std::vector<uint16_t> idx;
     vp::build_index(q, v->g, idx);
-    hipError_t e = hipMalloc((void **)&v->idx, idx.size() * sizeof(uint16_t));
-    if (e == hipSuccess && q.C) e = hipMalloc((void **)&v->crc_table, 256 * sizeof(uint32_t));
-    if (e == hipSuccess && v->g.scratch_words) e = hipMalloc((void **)&v->scratch, v->g.scratch_words * sizeof(uint64_t));
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "viterbi_create", __FILE__, __LINE__));
-    int rc = bank_upload(ctx, v->idx, idx.data(), idx.size() * sizeof(uint16_t));
-    if (rc == HZSDR_OK && q.C) {
-        uint32_t table[256];
-        for (uint32_t b = 0; b < 256; b++) table[b] = vm::crc_table_entry(b, q.C, q.poly);
-        rc = bank_upload(ctx, v->crc_table, table, sizeof table);
-    }
+    uint32_t table[256];
+    for (uint32_t b = 0; q.C && b < 256; b++) table[b] = vm::crc_table_entry(b, q.C, q.poly);
+    const int rc = db::upload(ctx, "viterbi_create",
+                              {{(void **)&v->idx, idx.data(), idx.size() * sizeof(uint16_t)},
+                               {(void **)&v->crc_table, table, q.C ? sizeof table : 0},
+                               {(void **)&v->scratch, nullptr, v->g.scratch_words * sizeof(uint64_t)}});
     if (rc != HZSDR_OK) return undo(rc);
     *out = v;
     return HZSDR_OK;
@@ -301,43 +286,24 @@ int hzsdr_viterbi_decode(hzsdr_viterbi *v, const void *in, size_t in_stride, con
                          size_t out_stride, uint32_t *info) {
     using namespace hz;
     if (!v) return HZSDR_ERR_INVALID_ARGUMENT;
-    hzsdr_ctx *ctx = v->ctx;
-    const size_t R = v->R, DB = v->g.DB;
-    if (cap == 0 || cap > vp::kMaxFrames / R) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "viterbi: cap is at least 1 and rows * cap at most 2^22");
-    if (!in || !out || !info) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "viterbi: null in, out or info");
-    const size_t iw = vt_in_width(v, cap), ow = cap * DB, isz = v->q.kind == vp::kBits ? 1 : sizeof(float);
-    if (R > 1 && in_stride < iw) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "viterbi: in_stride is below cap frames");
-    if (R > 1 && out_stride < ow) return fail(ctx, HZSDR_ERR_DST_TOO_SMALL, "viterbi: out_stride is below cap frames");
-    HZ_TRY(enter(ctx));
-    Stage st(ctx);
-    const void *din, *dic = nullptr;
-    void *dout = out, *dinfo = info;
-    size_t istride = R > 1 ? in_stride : iw, ostride = R > 1 ? out_stride : ow;
-    HZ_TRY(st.in_rows(0, in, R, iw, istride, isz, &din, &istride));
-    if (in_counts) HZ_TRY(st.in(1, in_counts, R * sizeof(uint32_t), &dic));
-    // the slots behind a row's count, and a frame's neighbours, stay as they are
-    HZ_TRY(stage_out_rows_preserved(st, 2, out, R, ow, out_stride, 1, &dout, &ostride));
-    HZ_TRY(st.out_preserve(3, info, R * cap * sizeof(uint32_t), &dinfo));
     const vp::Config &q = v->q;
     const vp::Geom &g = v->g;
-    VtArgs a{};
-    a.in = din, a.in_stride = istride, a.in_counts = (const uint32_t *)dic, a.out = (uint8_t *)dout, a.out_stride = ostride, a.info = (uint32_t *)dinfo;
-    a.idx = v->idx, a.crc_table = v->crc_table, a.scratch = v->scratch;
-    a.cap = (uint32_t)cap, a.slots = (uint32_t)(R * cap);
-    a.K = q.K, a.n = q.n, a.S = g.S, a.G = g.G, a.gshift = (uint32_t)__builtin_ctz(g.gsz);
-    a.T = g.T, a.D = (uint32_t)q.D, a.N = g.N, a.FB = g.FB, a.DB = g.DB, a.DW = g.DW, a.tiles = g.tiles, a.chunk = g.chunk;
-    a.off_tb = g.off_tb, a.off_crc = g.off_crc, a.off_dec = g.off_dec;
-    for (uint32_t j = 0; j < vp::kMaxRate; j++) a.gens[j] = q.gens[j];
-    a.inv = q.inv, a.term = q.term, a.scale = q.scale, a.C = q.C, a.poly = q.poly, a.init = q.init, a.xorout = q.xorout;
-    const dim3 grid(vp::waves_for(g, R * cap));
-    if (g.SPL == 1)
-        HZ_TRY(vt_launch<1>(v, a, grid));
-    else if (g.SPL == 2)
-        HZ_TRY(vt_launch<2>(v, a, grid));
-    else
-        HZ_TRY(vt_launch<4>(v, a, grid));
-    HZ_HIP(ctx, hipGetLastError());
-    return st.finish();
+    const bool bits = q.kind == vp::kBits;
+    const size_t w = bits ? g.FB : g.N;
+    const dbp::Call c{(uintptr_t)in, (uintptr_t)out, in_stride, w, out_stride, g.DB, cap, v->R, info != nullptr};
+    return db::decode(v, dbp::dense(w, g.DB), bits ? 1 : sizeof(float), c, in_counts, info, [&](const dbp::FrameArgs &fa, uint32_t cap, uint32_t slots) {
+        VtArgs a{};
+        static_cast<dbp::FrameArgs &>(a) = fa;
+        a.idx = v->idx, a.crc_table = v->crc_table, a.scratch = v->scratch;
+        a.cap = cap, a.slots = slots;
+        a.K = q.K, a.n = q.n, a.S = g.S, a.G = g.G, a.gshift = (uint32_t)__builtin_ctz(g.gsz);
+        a.T = g.T, a.D = (uint32_t)q.D, a.N = g.N, a.FB = g.FB, a.DB = g.DB, a.DW = g.DW, a.tiles = g.tiles, a.chunk = g.chunk;
+        a.off_tb = g.off_tb, a.off_crc = g.off_crc, a.off_dec = g.off_dec;
+        for (uint32_t j = 0; j < vp::kMaxRate; j++) a.gens[j] = q.gens[j];
+        a.inv = q.inv, a.term = q.term, a.scale = q.scale, a.C = q.C, a.poly = q.poly, a.init = q.init, a.xorout = q.xorout;
+        const dim3 grid(vp::waves_for(g, slots));
+        return g.SPL == 1 ? vt_launch<1>(v, a, grid) : g.SPL == 2 ? vt_launch<2>(v, a, grid) : vt_launch<4>(v, a, grid);
+    });
 }
 
 int hzsdr_viterbi_sizes(const hzsdr_viterbi *v, size_t *N, size_t *FB, size_t *T, size_t *DB) {

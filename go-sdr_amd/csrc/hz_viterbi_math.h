@@ -8,6 +8,7 @@
 
 #include "hz_framesync_math.h"
 #include "hz_plan.h"
+#include "hz_received.h"
 
 namespace hz {
 namespace vm {
@@ -15,16 +16,9 @@ namespace vm {
 constexpr uint32_t kInf = 1u << 30;      // the start metric of every state but 0
 constexpr uint16_t kPunctured = 0xffffu;  // the index table's entry of a position that was not sent
 
-// ---- one received value -> q in -127 ... 127 (0: an erasure) ----
-// each step is ONE float32 operation; a NaN gives 0, +-infinity +-127, -0 gives 0
-HZ_HD int quantise(float x, float scale) {
-    const float y = x * scale;
-    if (y != y) return 0;
-    return (int)rintf(fminf(fmaxf(y, -127.0f), 127.0f));
-}
-HZ_HD int hard(uint32_t bit) { return bit ? 1 : -1; }
-// bit k (0: the first) of a frame of packed bits, most significant bit first
-HZ_HD uint32_t packed_bit(const uint8_t *bytes, uint32_t k) { return (uint32_t)(bytes[k >> 3] >> (7u - (k & 7u))) & 1u; }
+// ---- one received value -> q in -127 ... 127 (0: an erasure): hz_received.h; a hard bit is +-1 ----
+using rx::quantise, rx::packed_bit;
+HZ_HD int hard(uint32_t bit) { return rx::hard(bit, 1); }
 // a step's n values (j >= n: 0) as one word, q_j in byte j
 HZ_HD uint32_t pack_q(int q, uint32_t j) { return ((uint32_t)q & 0xffu) << (8u * j); }
 HZ_HD int unpack_q(uint32_t qw, uint32_t j) { return (int)(int8_t)(qw >> (8u * j)); }

@@ -20,6 +20,7 @@
 
 #include <vector>
 
+#include "hz_decodebank_plan.h"
 #include "hz_rowwave_plan.h"
 #include "hz_viterbi_math.h"
 
@@ -27,12 +28,11 @@ namespace hz {
 namespace vp {
 
 using rw::kLanes, rw::kLdsBudget;
+using dbp::kBits, dbp::kSoftF32, dbp::kMaxRows, dbp::kMaxFrames;  // HZSDR_VITERBI_BITS, HZSDR_VITERBI_SOFT_F32
 
-constexpr int kBits = 1, kSoftF32 = 32;     // HZSDR_VITERBI_BITS, HZSDR_VITERBI_SOFT_F32
 constexpr int kTail = 0, kTruncated = 1;    // HZSDR_VITERBI_TAIL, HZSDR_VITERBI_TRUNCATED
 constexpr int kFormLds = 1, kFormScratch = 2;
-constexpr uint32_t kMinK = 3, kMaxK = 9, kMinRate = 2, kMaxRate = 4, kMaxPattern = 64, kMaxBits = 8192, kMaxRows = 8192;
-constexpr size_t kMaxFrames = (size_t)1 << 22;
+constexpr uint32_t kMinK = 3, kMaxK = 9, kMinRate = 2, kMaxRate = 4, kMaxPattern = 64, kMaxBits = 8192;
 constexpr uint32_t kTileSteps = 64;    // the steps whose received values are quantised into LDS together
 constexpr uint32_t kChunkSteps = 512;  // FORM_SCRATCH: the steps of decisions the traceback holds in LDS at a time
 constexpr uint32_t kWavesLds = 4096, kWavesScratch = 1024;  // the grid at most; a wave walks on from slot to slot
@@ -68,7 +68,7 @@ inline const char *check_config(const Config &q) {
     }
     if (q.term != kTail && q.term != kTruncated) return "termination is TAIL or TRUNCATED";
     if (q.D < 1 || q.D > kMaxBits || steps(q) > kMaxBits) return "1 <= D, T <= 8192";
-    if (q.kind == kSoftF32 && !(q.scale > 0.0f && q.scale <= 3.402823466e38f)) return "scale is finite and positive";
+    if (const char *why = q.kind == kSoftF32 ? dbp::check_scale(q.scale) : nullptr) return why;
     if (q.C != 0 && q.C != 8 && q.C != 16 && q.C != 24 && q.C != 32) return "a CRC of 0, 8, 16, 24 or 32 bits";
     if (q.C && q.C >= q.D) return "the CRC is shorter than the data";
     if (q.C && q.C < 32 && ((q.poly | q.init | q.xorout) >> q.C)) return "CRC parameters below 2^C";
@@ -94,8 +94,9 @@ struct Geom {
     size_t scratch_words;   // FORM_SCRATCH: max_waves * T * SPL, else 0
 };
 
-// a checked configuration
-inline Geom geom(const Config &q) {
+// a checked configuration (out of line, as build_index is: both stay in the library's symbol table, where the compiler
+// had left them before the create shrank around them)
+__attribute__((noinline)) inline Geom geom(const Config &q) {
     Geom g{};
     g.S = 1u << (q.K - 1);
     g.G = g.S < kLanes ? kLanes / g.S : 1;
@@ -103,7 +104,7 @@ inline Geom geom(const Config &q) {
     g.gsz = g.S < kLanes ? g.S : kLanes;
     g.T = (uint32_t)steps(q);
     for (uint32_t m = 0; m < g.T * q.n; m++) g.N += vm::transmitted(q.pattern, q.Lp, m);
-    g.FB = (g.N + 7) / 8, g.DB = ((uint32_t)q.D + 7) / 8, g.DW = ((uint32_t)q.D + 63) / 64;
+    g.FB = dbp::packed_bytes(g.N), g.DB = dbp::packed_bytes((uint32_t)q.D), g.DW = ((uint32_t)q.D + 63) / 64;
     g.tiles = (g.T + kTileSteps - 1) / kTileSteps;
     g.off_tb = g.G * kTileSteps * 4;
     g.off_crc = g.off_tb + g.G * g.DW * 8;
@@ -125,7 +126,7 @@ inline uint32_t waves_for(const Geom &g, size_t slots) {
 }
 
 // idx: T n entries
-inline void build_index(const Config &q, const Geom &g, std::vector<uint16_t> &idx) {
+__attribute__((noinline)) inline void build_index(const Config &q, const Geom &g, std::vector<uint16_t> &idx) {
     idx.assign((size_t)g.T * q.n, vm::kPunctured);
     uint32_t at = 0, phase = 0;  // phase: m mod Lp, carried so that nothing is divided here either
     for (uint32_t t = 0; t < g.T; t++) {

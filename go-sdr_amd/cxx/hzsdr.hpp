@@ -1630,18 +1630,77 @@ private:
     hzsdr_hdlc *f_ = nullptr;
 };
 
+// What the three decoder bank classes below share: the handle and its life, the sizes every bank has, the cut of a call's
+// results into k = min(in_counts[r], cap) frames per row, and the packing of a list of frames per row into a block of
+// slots with counts.  D is the class itself -- its Frame, its frame(bytes, info word) maker and kName, which starts its
+// exceptions --, H the handle, Free hzsdr_<bank>_free.
+template <class D, class H, auto Free>
+class FrameDecoder {
+public:
+    FrameDecoder(const FrameDecoder &) = delete;
+    FrameDecoder &operator=(const FrameDecoder &) = delete;
+    size_t Rows() const { return rows_; }
+    size_t FrameBytes() const { return fb_; }
+    size_t DataBytes() const { return db_; }
+
+protected:
+    FrameDecoder(const Context &x, size_t rows) : x_(x), rows_(rows) {}
+    ~FrameDecoder() { if (h_) Free(h_); }
+    // call(out, info) -> status decodes into dense destinations of `cap` slots a row; the first k frames of every row
+    template <class Call> auto decoded(size_t cap, const uint32_t *in_counts, Call call) {
+        std::vector<uint8_t> out(rows_ * cap * db_);
+        std::vector<uint32_t> info(rows_ * cap);
+        check(x_.raw(), call(out.data(), info.data()));
+        std::vector<std::vector<typename D::Frame>> rows(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            const size_t k = in_counts && in_counts[r] < cap ? in_counts[r] : cap;
+            for (size_t f = 0; f < k; f++) {
+                const uint8_t *p = out.data() + (r * cap + f) * db_;
+                rows[r].push_back(D::frame(std::vector<uint8_t>(p, p + db_), info[r * cap + f]));
+            }
+        }
+        return rows;
+    }
+    // a list of frames per row (rows_ lists; a frame's bytes are the bank's fb_) as a dense block with counts
+    struct Packed {
+        size_t cap = 1;
+        std::vector<uint8_t> in;
+        std::vector<uint32_t> counts;
+    };
+    template <class In> Packed pack(const std::vector<std::vector<In>> &frames) const {
+        Packed p;
+        for (const auto &row : frames) p.cap = row.size() > p.cap ? row.size() : p.cap;
+        p.in.assign(rows_ * p.cap * fb_, 0);
+        p.counts.resize(rows_);
+        for (size_t r = 0; r < rows_; r++) {
+            p.counts[r] = (uint32_t)frames[r].size();
+            for (size_t f = 0; f < frames[r].size(); f++) {
+                if (frames[r][f].bytes.size() != fb_) throw std::invalid_argument(std::string(D::kName) + ": a frame of another size");
+                std::copy(frames[r][f].bytes.begin(), frames[r][f].bytes.end(), p.in.begin() + (r * p.cap + f) * fb_);
+            }
+        }
+        return p;
+    }
+    const Context &x_;
+    size_t rows_;
+    size_t fb_ = 0, db_ = 0;
+    H *h_ = nullptr;
+};
+
 // The Viterbi decoder bank (include/hzsdr_viterbi.h): frames of a rate 1 / gens.size() convolutional code -- packed hard
 // bits (HZSDR_VITERBI_BITS: the frame sync bank's frames as they are) or soft floats (HZSDR_VITERBI_SOFT_F32) -- to
 // data_bits data bits, a path metric and a CRC verdict per frame, over `rows` rows of `cap` frame slots.  Decode runs
 // min(in_counts[r], cap) frames of every row (row r starts r * in_stride bytes or floats into `in`; dense rows when
 // in_stride is 0; every row has cap frames when in_counts is null).  The bank keeps no state.
-class Viterbi {
+class Viterbi : public FrameDecoder<Viterbi, hzsdr_viterbi, hzsdr_viterbi_free> {
 public:
+    static constexpr const char *kName = "Viterbi";
     struct Frame {
         std::vector<uint8_t> bytes;  // data bit k in byte k / 8, bit 7 - k % 8
         uint32_t metric;             // hard input: the channel bit errors corrected
         bool crc_ok;
     };
+    static Frame frame(std::vector<uint8_t> bytes, uint32_t w) { return {std::move(bytes), w & 0x7fffffffu, (w >> 31) != 0}; }
     struct Config {
         unsigned K = 7;
         std::vector<unsigned> gens = {0171, 0133};
@@ -1654,67 +1713,39 @@ public:
         unsigned crc_bits = 0;
         uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;
     };
-    Viterbi(const Context &x, int kind, const Config &c, size_t rows = 1) : x_(x), kind_(kind), rows_(rows) {
+    Viterbi(const Context &x, int kind, const Config &c, size_t rows = 1) : FrameDecoder(x, rows), kind_(kind) {
         if (c.gens.empty()) throw std::invalid_argument("Viterbi: at least two generators");
         const unsigned n = (unsigned)c.gens.size();
         const uint64_t pattern = c.pattern_bits ? c.pattern : (1ull << n) - 1;
         check(x_.raw(), hzsdr_viterbi_create(x_.raw(), kind, c.K, n, c.gens.data(), c.inv, pattern, c.pattern_bits ? c.pattern_bits : n, c.termination,
-                                             c.data_bits, c.scale, c.crc_bits, c.crc_poly, c.crc_init, c.crc_xorout, rows, &v_));
-        check(x_.raw(), hzsdr_viterbi_sizes(v_, &n_, &fb_, &t_, &db_));
+                                             c.data_bits, c.scale, c.crc_bits, c.crc_poly, c.crc_init, c.crc_xorout, rows, &h_));
+        check(x_.raw(), hzsdr_viterbi_sizes(h_, &n_, &fb_, &t_, &db_));
     }
-    ~Viterbi() { if (v_) hzsdr_viterbi_free(v_); }
-    Viterbi(const Viterbi &) = delete;
-    Viterbi &operator=(const Viterbi &) = delete;
     std::vector<std::vector<Frame>> Decode(const void *in, size_t cap, size_t in_stride = 0, const uint32_t *in_counts = nullptr) {
-        std::vector<uint8_t> out(rows_ * cap * db_);
-        std::vector<uint32_t> info(rows_ * cap);
         const size_t width = cap * (kind_ == HZSDR_VITERBI_BITS ? fb_ : n_);
-        check(x_.raw(), hzsdr_viterbi_decode(v_, in, in_stride ? in_stride : width, in_counts, cap, out.data(), cap * db_, info.data()));
-        std::vector<std::vector<Frame>> rows(rows_);
-        for (size_t r = 0; r < rows_; r++) {
-            const size_t k = in_counts && in_counts[r] < cap ? in_counts[r] : cap;
-            for (size_t f = 0; f < k; f++) {
-                const uint8_t *p = out.data() + (r * cap + f) * db_;
-                rows[r].push_back({std::vector<uint8_t>(p, p + db_), info[r * cap + f] & 0x7fffffffu, (info[r * cap + f] >> 31) != 0});
-            }
-        }
-        return rows;
+        return decoded(cap, in_counts, [&](uint8_t *out, uint32_t *info) {
+            return hzsdr_viterbi_decode(h_, in, in_stride ? in_stride : width, in_counts, cap, out, cap * db_, info);
+        });
     }
     // what FrameSync::Push returned, frame for frame (HZSDR_VITERBI_BITS; a frame's bytes are the bank's FB)
     std::vector<std::vector<Frame>> Decode(const std::vector<std::vector<FrameSync::Frame>> &frames) {
         if (kind_ != HZSDR_VITERBI_BITS || frames.size() != rows_) throw std::invalid_argument("Viterbi: hard-bit frames, a list per row");
-        size_t cap = 1;
-        for (const auto &row : frames) cap = row.size() > cap ? row.size() : cap;
-        std::vector<uint8_t> in(rows_ * cap * fb_, 0);
-        std::vector<uint32_t> counts(rows_);
-        for (size_t r = 0; r < rows_; r++) {
-            counts[r] = (uint32_t)frames[r].size();
-            for (size_t f = 0; f < frames[r].size(); f++) {
-                if (frames[r][f].bytes.size() != fb_) throw std::invalid_argument("Viterbi: a frame of another size");
-                std::copy(frames[r][f].bytes.begin(), frames[r][f].bytes.end(), in.begin() + (r * cap + f) * fb_);
-            }
-        }
-        return Decode(in.data(), cap, 0, counts.data());
+        const Packed p = pack(frames);
+        return Decode(p.in.data(), p.cap, 0, p.counts.data());
     }
     // -> (frames per wave, states per lane, bytes of a frame's decisions, HZSDR_VITERBI_FORM_*)
     std::tuple<size_t, size_t, size_t, int> Plan() const {
         size_t g = 0, s = 0, d = 0;
         int f = 0;
-        check(x_.raw(), hzsdr_viterbi_plan(v_, &g, &s, &d, &f));
+        check(x_.raw(), hzsdr_viterbi_plan(h_, &g, &s, &d, &f));
         return {g, s, d, f};
     }
-    size_t Rows() const { return rows_; }
     size_t ReceivedBits() const { return n_; }
-    size_t FrameBytes() const { return fb_; }
     size_t Steps() const { return t_; }
-    size_t DataBytes() const { return db_; }
 
 private:
-    const Context &x_;
     int kind_;
-    size_t rows_;
-    size_t n_ = 0, fb_ = 0, t_ = 0, db_ = 0;
-    hzsdr_viterbi *v_ = nullptr;
+    size_t n_ = 0, t_ = 0;
 };
 
 // The LDPC decoder bank (include/hzsdr_ldpc.h): frames of a binary LDPC code given by its parity-check matrix in
@@ -1723,14 +1754,16 @@ private:
 // bits, the unsatisfied checks, the iterations run and a verdict per frame, over `rows` rows of `cap` frame slots.
 // Decode runs min(in_counts[r], cap) frames of every row (row r starts r * in_stride bytes or floats into `in`; dense
 // rows when in_stride is 0; every row has cap frames when in_counts is null).  The bank keeps no state.
-class Ldpc {
+class Ldpc : public FrameDecoder<Ldpc, hzsdr_ldpc, hzsdr_ldpc_free> {
 public:
+    static constexpr const char *kName = "Ldpc";
     struct Frame {
         std::vector<uint8_t> bytes;  // data bit k in byte k / 8, bit 7 - k % 8
         uint32_t unsatisfied;        // checks of odd parity behind the last iteration run
         uint32_t iters;              // iterations run
         bool ok;                     // unsatisfied == 0
     };
+    static Frame frame(std::vector<uint8_t> bytes, uint32_t w) { return {std::move(bytes), w & 0xffffu, (w >> 16) & 0xffu, (w >> 31) != 0}; }
     struct Config {
         size_t variables = 0;
         std::vector<uint32_t> row_ptr, col;  // checks + 1 entries; the variables of every check, ascending
@@ -1740,69 +1773,40 @@ public:
         float scale = 1.0f;
         unsigned level = 1, max_iters = 50, norm = 12, offset = 0;
     };
-    Ldpc(const Context &x, int kind, const Config &c, size_t rows = 1) : x_(x), kind_(kind), rows_(rows) {
+    Ldpc(const Context &x, int kind, const Config &c, size_t rows = 1) : FrameDecoder(x, rows), kind_(kind) {
         if (c.row_ptr.empty() || c.head > c.variables) throw std::invalid_argument("Ldpc: row_ptr has checks + 1 entries, head is at most variables");
         check(x_.raw(), hzsdr_ldpc_create(x_.raw(), kind, c.row_ptr.size() - 1, c.variables, c.row_ptr.data(), c.col.data(), c.col.size(), c.head,
                                           c.received ? c.received : c.variables - c.head, c.data_bits ? c.data_bits : c.variables, c.scale, c.level,
-                                          c.max_iters, c.norm, c.offset, rows, &l_));
-        check(x_.raw(), hzsdr_ldpc_sizes(l_, &n_, &fb_, &vars_, &checks_, &edges_, &db_));
+                                          c.max_iters, c.norm, c.offset, rows, &h_));
+        check(x_.raw(), hzsdr_ldpc_sizes(h_, &n_, &fb_, &vars_, &checks_, &edges_, &db_));
     }
-    ~Ldpc() { if (l_) hzsdr_ldpc_free(l_); }
-    Ldpc(const Ldpc &) = delete;
-    Ldpc &operator=(const Ldpc &) = delete;
     std::vector<std::vector<Frame>> Decode(const void *in, size_t cap, size_t in_stride = 0, const uint32_t *in_counts = nullptr) {
-        std::vector<uint8_t> out(rows_ * cap * db_);
-        std::vector<uint32_t> info(rows_ * cap);
         const size_t width = cap * (kind_ == HZSDR_LDPC_BITS ? fb_ : n_);
-        check(x_.raw(), hzsdr_ldpc_decode(l_, in, in_stride ? in_stride : width, in_counts, cap, out.data(), cap * db_, info.data()));
-        std::vector<std::vector<Frame>> rows(rows_);
-        for (size_t r = 0; r < rows_; r++) {
-            const size_t k = in_counts && in_counts[r] < cap ? in_counts[r] : cap;
-            for (size_t f = 0; f < k; f++) {
-                const uint8_t *p = out.data() + (r * cap + f) * db_;
-                const uint32_t w = info[r * cap + f];
-                rows[r].push_back({std::vector<uint8_t>(p, p + db_), w & 0xffffu, (w >> 16) & 0xffu, (w >> 31) != 0});
-            }
-        }
-        return rows;
+        return decoded(cap, in_counts, [&](uint8_t *out, uint32_t *info) {
+            return hzsdr_ldpc_decode(h_, in, in_stride ? in_stride : width, in_counts, cap, out, cap * db_, info);
+        });
     }
     // what FrameSync::Push returned, frame for frame (HZSDR_LDPC_BITS; a frame's bytes are the bank's FB)
     std::vector<std::vector<Frame>> Decode(const std::vector<std::vector<FrameSync::Frame>> &frames) {
         if (kind_ != HZSDR_LDPC_BITS || frames.size() != rows_) throw std::invalid_argument("Ldpc: hard-bit frames, a list per row");
-        size_t cap = 1;
-        for (const auto &row : frames) cap = row.size() > cap ? row.size() : cap;
-        std::vector<uint8_t> in(rows_ * cap * fb_, 0);
-        std::vector<uint32_t> counts(rows_);
-        for (size_t r = 0; r < rows_; r++) {
-            counts[r] = (uint32_t)frames[r].size();
-            for (size_t f = 0; f < frames[r].size(); f++) {
-                if (frames[r][f].bytes.size() != fb_) throw std::invalid_argument("Ldpc: a frame of another size");
-                std::copy(frames[r][f].bytes.begin(), frames[r][f].bytes.end(), in.begin() + (r * cap + f) * fb_);
-            }
-        }
-        return Decode(in.data(), cap, 0, counts.data());
+        const Packed p = pack(frames);
+        return Decode(p.in.data(), p.cap, 0, p.counts.data());
     }
     // -> (frames per workgroup, threads per frame, LDS bytes of a frame's state, HZSDR_LDPC_FORM_*)
     std::tuple<size_t, size_t, size_t, int> Plan() const {
         size_t g = 0, t = 0, b = 0;
         int f = 0;
-        check(x_.raw(), hzsdr_ldpc_plan(l_, &g, &t, &b, &f));
+        check(x_.raw(), hzsdr_ldpc_plan(h_, &g, &t, &b, &f));
         return {g, t, b, f};
     }
-    size_t Rows() const { return rows_; }
     size_t ReceivedBits() const { return n_; }
-    size_t FrameBytes() const { return fb_; }
     size_t Variables() const { return vars_; }
     size_t Checks() const { return checks_; }
     size_t Edges() const { return edges_; }
-    size_t DataBytes() const { return db_; }
 
 private:
-    const Context &x_;
     int kind_;
-    size_t rows_;
-    size_t n_ = 0, fb_ = 0, vars_ = 0, checks_ = 0, edges_ = 0, db_ = 0;
-    hzsdr_ldpc *l_ = nullptr;
+    size_t n_ = 0, vars_ = 0, checks_ = 0, edges_ = 0;
 };
 
 // The Reed-Solomon decoder bank (include/hzsdr_rs.h): frames of `interleave` symbol-interleaved codewords over GF(2^8) --
@@ -1810,79 +1814,52 @@ private:
 // `cap` frame slots.  Decode runs min(in_counts[r], cap) frames of every row (row r starts r * in_stride bytes into `in`,
 // frame f of it f * in_pitch bytes further; dense rows and slots when they are 0; every row has cap frames when in_counts
 // is null).  The bank keeps no state.
-class ReedSolomon {
+class ReedSolomon : public FrameDecoder<ReedSolomon, hzsdr_rs, hzsdr_rs_free> {
 public:
+    static constexpr const char *kName = "ReedSolomon";
     struct Frame {
         std::vector<uint8_t> bytes;  // the I k data bytes, corrected where the codeword did not fail
         uint32_t errors, failed;     // symbols corrected over the frame's decoded codewords; codewords that failed
         bool ok;                     // failed == 0
     };
+    static Frame frame(std::vector<uint8_t> bytes, uint32_t w) { return {std::move(bytes), w & 0xffffu, (w >> 16) & 0x7fffu, (w >> 31) != 0}; }
     struct Config {
         unsigned gfpoly = 0x187, fcr = 112, prim = 11, nroots = 32, n = 255;  // CCSDS 255/223
         unsigned interleave = 1;
         std::vector<uint8_t> in_map, out_map;  // empty: identity; else 256 bytes
         std::vector<uint8_t> scramble;         // empty: none
     };
-    ReedSolomon(const Context &x, const Config &c, size_t rows = 1) : x_(x), rows_(rows) {
+    ReedSolomon(const Context &x, const Config &c, size_t rows = 1) : FrameDecoder(x, rows) {
         if ((!c.in_map.empty() && c.in_map.size() != 256) || (!c.out_map.empty() && c.out_map.size() != 256))
             throw std::invalid_argument("ReedSolomon: a map is 256 bytes");
         check(x_.raw(), hzsdr_rs_create(x_.raw(), c.gfpoly, c.fcr, c.prim, c.nroots, c.n, c.interleave, c.in_map.empty() ? nullptr : c.in_map.data(),
                                         c.out_map.empty() ? nullptr : c.out_map.data(), c.scramble.empty() ? nullptr : c.scramble.data(), c.scramble.size(),
-                                        rows, &r_));
-        check(x_.raw(), hzsdr_rs_sizes(r_, &k_, &t_, &fb_, &db_));
+                                        rows, &h_));
+        check(x_.raw(), hzsdr_rs_sizes(h_, &k_, &t_, &fb_, &db_));
     }
-    ~ReedSolomon() { if (r_) hzsdr_rs_free(r_); }
-    ReedSolomon(const ReedSolomon &) = delete;
-    ReedSolomon &operator=(const ReedSolomon &) = delete;
     std::vector<std::vector<Frame>> Decode(const uint8_t *in, size_t cap, size_t in_stride = 0, size_t in_pitch = 0, const uint32_t *in_counts = nullptr) {
-        std::vector<uint8_t> out(rows_ * cap * db_);
-        std::vector<uint32_t> info(rows_ * cap);
         const size_t pitch = in_pitch ? in_pitch : fb_;
-        check(x_.raw(), hzsdr_rs_decode(r_, in, in_stride ? in_stride : cap * pitch, pitch, in_counts, cap, out.data(), cap * db_, db_, info.data()));
-        std::vector<std::vector<Frame>> rows(rows_);
-        for (size_t r = 0; r < rows_; r++) {
-            const size_t k = in_counts && in_counts[r] < cap ? in_counts[r] : cap;
-            for (size_t f = 0; f < k; f++) {
-                const uint8_t *p = out.data() + (r * cap + f) * db_;
-                const uint32_t w = info[r * cap + f];
-                rows[r].push_back({std::vector<uint8_t>(p, p + db_), w & 0xffffu, (w >> 16) & 0x7fffu, (w >> 31) != 0});
-            }
-        }
-        return rows;
+        return decoded(cap, in_counts, [&](uint8_t *out, uint32_t *info) {
+            return hzsdr_rs_decode(h_, in, in_stride ? in_stride : cap * pitch, pitch, in_counts, cap, out, cap * db_, db_, info);
+        });
     }
     // what Viterbi::Decode returned, frame for frame (a frame's bytes are the bank's frame bytes)
     std::vector<std::vector<Frame>> Decode(const std::vector<std::vector<Viterbi::Frame>> &frames) {
         if (frames.size() != rows_) throw std::invalid_argument("ReedSolomon: a list of frames per row");
-        size_t cap = 1;
-        for (const auto &row : frames) cap = row.size() > cap ? row.size() : cap;
-        std::vector<uint8_t> in(rows_ * cap * fb_, 0);
-        std::vector<uint32_t> counts(rows_);
-        for (size_t r = 0; r < rows_; r++) {
-            counts[r] = (uint32_t)frames[r].size();
-            for (size_t f = 0; f < frames[r].size(); f++) {
-                if (frames[r][f].bytes.size() != fb_) throw std::invalid_argument("ReedSolomon: a frame of another size");
-                std::copy(frames[r][f].bytes.begin(), frames[r][f].bytes.end(), in.begin() + (r * cap + f) * fb_);
-            }
-        }
-        return Decode(in.data(), cap, 0, 0, counts.data());
+        const Packed p = pack(frames);
+        return Decode(p.in.data(), p.cap, 0, 0, p.counts.data());
     }
     // -> (waves per workgroup, LDS bytes per workgroup, workgroups a compute unit holds, workgroups of a call at most)
     std::tuple<size_t, size_t, size_t, size_t> Plan() const {
         size_t w = 0, l = 0, c = 0, g = 0;
-        check(x_.raw(), hzsdr_rs_plan(r_, &w, &l, &c, &g));
+        check(x_.raw(), hzsdr_rs_plan(h_, &w, &l, &c, &g));
         return {w, l, c, g};
     }
-    size_t Rows() const { return rows_; }
     size_t DataSymbols() const { return k_; }
     size_t Correctable() const { return t_; }
-    size_t FrameBytes() const { return fb_; }
-    size_t DataBytes() const { return db_; }
 
 private:
-    const Context &x_;
-    size_t rows_;
-    size_t k_ = 0, t_ = 0, fb_ = 0, db_ = 0;
-    hzsdr_rs *r_ = nullptr;
+    size_t k_ = 0, t_ = 0;
 };
 
 // The tuner bank (include/hzsdr_tuner.h): one pass over a stream of src_format samples, a tuner per frequency word

@@ -25,8 +25,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import ErrInvalidArgument, _is_torch, lib
-from ._frames import block_ptr, dense_ptr, new_like
+from . import ErrInvalidArgument
+from ._frames import DecoderBank
 from ._capi import (LDPC_BITS, LDPC_FORM_TABLES_CACHE, LDPC_FORM_TABLES_LDS, LDPC_MAX_BITS, LDPC_MAX_CHECKS, LDPC_MAX_DEGREE, LDPC_MAX_EDGES,
                     LDPC_MAX_FRAMES, LDPC_MAX_ITERS, LDPC_MAX_ROWS, LDPC_MAX_VARIABLES, LDPC_SOFT_F32)
 
@@ -189,18 +189,19 @@ def ldpc_encode(code, data):
     return x
 
 
-class LdpcDecoder:
+class LdpcDecoder(DecoderBank):
     """hzsdr_ldpc: decode(frames, counts) -> (data, info).  `kind` is LDPC_SOFT_F32 (float32 frames of N values,
     positive meaning 1: SoftFrames.push's values) or LDPC_BITS (uint8 frames of FB = ceil(N / 8) bytes, most significant
     bit first: FrameSync.push's frames).  `code` is an LdpcCode; `received` defaults to every variable behind `head`,
     `data_bits` to the code's k (or n).  frames is (rows, cap, N or FB) -- (cap, ...) will do for one row -- with
     contiguous rows and any row pitch.  numpy in a HOST context; torch tensors on the context's device, written on the
     context's stream, in a DEVICE context (info and counts are int32 there: the same bits)."""
+    _c = _noun = "ldpc"
+    _bits = LDPC_BITS
 
     def __init__(self, ctx, kind, code, received=None, head=0, data_bits=None, scale=1.0, level=1, max_iters=50, norm=12, offset=0, rows=1):
-        self.ctx, self.kind, self.rows, self.code = ctx, int(kind), int(rows), code
-        if self.rows <= 0:
-            raise ErrInvalidArgument("ldpc: rows is at least 1")
+        self.kind, self.code = int(kind), code
+        self._open(ctx, rows)
         self.head = int(head)
         self.N = code.n - self.head if received is None else int(received)
         self.D = (code.n if code.k is None else code.k) if data_bits is None else int(data_bits)
@@ -211,23 +212,17 @@ class LdpcDecoder:
         rp, col = np.ascontiguousarray(code.row_ptr, np.uint32), np.ascontiguousarray(code.col, np.uint32)
         if len(rp) < 1:
             raise ErrInvalidArgument("ldpc: row_ptr has checks + 1 entries")
-        self._h = C.c_void_p()
-        ctx._ck(lib.hzsdr_ldpc_create(ctx._h, self.kind, len(rp) - 1, int(code.n), rp.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                      col.ctypes.data_as(C.POINTER(C.c_uint32)), len(col), self.head, self.N, self.D, self.scale, self.level,
-                                      self.max_iters, self.norm, self.offset, self.rows, C.byref(self._h)))
+        self._create(self.kind, len(rp) - 1, int(code.n), rp.ctypes.data_as(C.POINTER(C.c_uint32)), col.ctypes.data_as(C.POINTER(C.c_uint32)), len(col),
+                     self.head, self.N, self.D, self.scale, self.level, self.max_iters, self.norm, self.offset)
         _, self.frame_bytes, self.n, self.m, self.E, self.data_bytes = self.sizes()
 
     def sizes(self):
         """(N received positions, FB = ceil(N / 8), n, m, E, DB = ceil(D / 8))"""
-        v = [C.c_size_t(0) for _ in range(6)]
-        self.ctx._ck(lib.hzsdr_ldpc_sizes(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._sizes("sizes", 6)
 
     def plan(self):
         """(frames per workgroup, threads per frame, LDS bytes of a frame's state, LDPC_FORM_TABLES_LDS or _CACHE)"""
-        g, t, b, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_ldpc_plan(self._h, C.byref(g), C.byref(t), C.byref(b), C.byref(f)))
-        return g.value, t.value, b.value, f.value
+        return self._plan()
 
     def decode(self, frames, counts=None, cap=None, out=None):
         """Decode min(counts[r], cap) frames of every row -> (data uint8 (rows, cap, DB), info (rows, cap) =
@@ -235,50 +230,16 @@ class LdpcDecoder:
         above cap are clamped); without it every row decodes cap frames.  `cap` defaults to the frames' second-last
         extent.  Slots from a row's count up hold what the destination held (a new one is zero).  `out`, when given, is
         such a pair (data, info); data may be a view with a row pitch above cap * DB."""
-        R = self.rows
-        width = self.frame_bytes if self.kind == LDPC_BITS else self.N
-        dtype = np.uint8 if self.kind == LDPC_BITS else np.float32
-        if frames.ndim == 2 and R == 1:
-            frames = frames[None]
-        if frames.ndim != 3:
-            raise ValueError("ldpc: frames are (rows, cap, FB or N)")
-        cap = int(frames.shape[1]) if cap is None else int(cap)
-        fptr, fpitch = block_ptr(frames, (R, cap, width), dtype, "frames", "ldpc")
-        if out is None:
-            out = (new_like((R, cap, self.data_bytes), np.uint8, frames), new_like((R, cap), np.uint32, frames))
-        data, info = out
-        dptr, dpitch = block_ptr(data, (R, cap, self.data_bytes), np.uint8, "data", "ldpc")
-        iptr = dense_ptr(info, (R, cap), np.uint32, "info", "ldpc", "int32")
-        cptr = None if counts is None else dense_ptr(counts, (R,), np.uint32, "the frames' counts", "ldpc", "int32")
-        self.ctx._ck(lib.hzsdr_ldpc_decode(self._h, fptr, fpitch, cptr, cap, dptr, dpitch, iptr))
-        return data, info
+        return self._decode(frames, counts, cap, out)
 
     def ragged(self, data, info, counts=None):
         """A call's results -> a list of `rows` host tuples (data (k, DB), unsatisfied (k,) uint32, iters (k,) uint32,
         ok (k,) bool), k = min(counts[r], cap) (this waits for the device in a DEVICE context)."""
-        if _is_torch(data):
-            data, info = data.cpu().numpy(), info.cpu().numpy()
-            counts = None if counts is None else counts.cpu().numpy()
-        cap = data.shape[1]
-        info = np.asarray(info).view(np.uint32)
-        got = np.full(self.rows, cap, np.uint32) if counts is None else np.asarray(counts).reshape(-1).view(np.uint32)
-        out = []
-        for r, c in enumerate(got):
-            k = min(int(c), cap)
-            w = info[r, :k]
-            out.append((data[r, :k].copy(), w & np.uint32(0xFFFF), (w >> np.uint32(16)) & np.uint32(0xFF), (w >> np.uint32(31)).astype(bool)))
-        return out
+        return self._ragged(data, info, counts)
 
-    def close(self):
-        if self._h:
-            lib.hzsdr_ldpc_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    @staticmethod
+    def _fields(w):
+        return w & np.uint32(0xFFFF), (w >> np.uint32(16)) & np.uint32(0xFF), (w >> np.uint32(31)).astype(bool)
 
 
 __all__ = ["LdpcDecoder", "LdpcCode", "qc_code", "regular_code", "ldpc_systematic", "ldpc_encode", "LDPC_BITS", "LDPC_SOFT_F32",

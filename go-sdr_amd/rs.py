@@ -17,12 +17,10 @@ and the bytes behind I k in a slot, stay as they are.  Frames are independent an
 Not here: erasures, soft decisions, encoding on the device (rs_encode is numpy), other symbol sizes, interleavers
 across frames.
 """
-import ctypes as C
-
 import numpy as np
 
-from . import ErrInvalidArgument, _is_torch, lib
-from ._frames import dense_ptr, new_like, pitched_block_ptr
+from . import ErrInvalidArgument
+from ._frames import DecoderBank, pitched_block_ptr
 from ._capi import RS_MAX_FRAMES, RS_MAX_INTERLEAVE, RS_MAX_N, RS_MAX_ROOTS, RS_MAX_ROWS, RS_MAX_SCRAMBLE, RS_MIN_ROOTS
 
 CCSDS_RS_255_223 = (0x187, 112, 11, 32, 255)  # (gfpoly, fcr, prim, nroots, n)
@@ -110,17 +108,16 @@ def ccsds_dual_basis():
     return to_dual.astype(np.uint8), from_dual.astype(np.uint8)
 
 
-class ReedSolomon:
+class ReedSolomon(DecoderBank):
     """hzsdr_rs: decode(frames, counts) -> (data, info).  frames is uint8 (rows, cap, width) -- (cap, width) will do for
     one row -- with width at least the frame bytes I n, unit stride along a frame, any frame pitch and any row pitch: the
     Viterbi bank's data block as it is.  numpy in a HOST context; torch tensors on the context's device, written on the
     context's stream, in a DEVICE context (info and counts are int32 there: the same bits)."""
+    _c = _noun = "rs"
 
     def __init__(self, ctx, code, interleave=1, in_map=None, out_map=None, scramble=None, rows=1):
-        self.ctx, self.rows, self.interleave = ctx, int(rows), int(interleave)
-        self.code = tuple(int(v) for v in code)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("rs: rows is at least 1")
+        self.interleave, self.code = int(interleave), tuple(int(v) for v in code)
+        self._open(ctx, rows)
         if len(self.code) != 5 or min(self.code) < 0 or max(self.code) >= 1 << 32 or not 0 <= self.interleave < 1 << 32:
             raise ErrInvalidArgument("rs: a code is (gfpoly, fcr, prim, nroots, n), unsigned values")
         maps = []
@@ -134,22 +131,17 @@ class ReedSolomon:
         if scr is not None and scr.size == 0:
             scr = None
         ptr = [None if m is None else m.ctypes.data for m in (*maps, scr)]
-        self._h = C.c_void_p()
-        ctx._ck(lib.hzsdr_rs_create(ctx._h, *self.code, self.interleave, *ptr, 0 if scr is None else scr.size, self.rows, C.byref(self._h)))
+        self._create(*self.code, self.interleave, *ptr, 0 if scr is None else scr.size)
         self.k, self.t, self.frame_bytes, self.data_bytes = self.sizes()
         self.n, self.nroots = self.code[4], self.code[3]
 
     def sizes(self):
         """(k data symbols, t correctable symbols per codeword, frame bytes I n, data bytes I k)"""
-        v = [C.c_size_t(0) for _ in range(4)]
-        self.ctx._ck(lib.hzsdr_rs_sizes(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._sizes("sizes", 4)
 
     def plan(self):
         """(waves per workgroup, LDS bytes per workgroup, workgroups a compute unit holds, workgroups of a call at most)"""
-        v = [C.c_size_t(0) for _ in range(4)]
-        self.ctx._ck(lib.hzsdr_rs_plan(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._sizes("plan", 4)
 
     def decode(self, frames, counts=None, cap=None, out=None):
         """Decode min(counts[r], cap) frames of every row -> (data uint8 (rows, cap, I k), info (rows, cap) =
@@ -163,45 +155,23 @@ class ReedSolomon:
             raise ValueError("rs: frames are (rows, cap, width)")
         cap = int(frames.shape[1]) if cap is None else int(cap)
         fptr, fstride, fpitch = pitched_block_ptr(frames, self.rows, cap, self.frame_bytes, "frames", "rs")
-        if out is None:
-            out = (new_like((self.rows, cap, self.data_bytes), np.uint8, frames), new_like((self.rows, cap), np.uint32, frames))
+        out = self._out(frames, cap, out)
         data, info = out
         if data.ndim == 2 and self.rows == 1:
             data = data[None]
         dptr, dstride, dpitch = pitched_block_ptr(data, self.rows, cap, self.data_bytes, "data", "rs")
-        iptr = dense_ptr(info, (self.rows, cap), np.uint32, "info", "rs", "int32")
-        cptr = None if counts is None else dense_ptr(counts, (self.rows,), np.uint32, "the frames' counts", "rs", "int32")
-        self.ctx._ck(lib.hzsdr_rs_decode(self._h, fptr, fstride, fpitch, cptr, cap, dptr, dstride, dpitch, iptr))
+        iptr, cptr = self._tail_ptrs(info, counts, cap)
+        self._call("decode", fptr, fstride, fpitch, cptr, cap, dptr, dstride, dpitch, iptr)
         return out[0], info
 
     def ragged(self, data, info, counts=None):
         """A call's results -> a list of `rows` host tuples (data (k, I k), E (k,) uint32, nfail (k,) uint32, ok (k,)
         bool), k = min(counts[r], cap) (this waits for the device in a DEVICE context)."""
-        if _is_torch(data):
-            data, info = data.cpu().numpy(), info.cpu().numpy()
-            counts = None if counts is None else counts.cpu().numpy()
-        if data.ndim == 2:
-            data, info = data[None], np.asarray(info).reshape(1, -1)
-        cap = data.shape[1]
-        info = np.asarray(info).view(np.uint32)
-        got = np.full(self.rows, cap, np.uint32) if counts is None else np.asarray(counts).reshape(-1).view(np.uint32)
-        out = []
-        for r, c in enumerate(got):
-            k = min(int(c), cap)
-            w = info[r, :k]
-            out.append((data[r, :k, :self.data_bytes].copy(), w & np.uint32(0xFFFF), (w >> np.uint32(16)) & np.uint32(0x7FFF), (w >> np.uint32(31)).astype(bool)))
-        return out
+        return self._ragged(data, info, counts)
 
-    def close(self):
-        if self._h:
-            lib.hzsdr_rs_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    @staticmethod
+    def _fields(w):
+        return w & np.uint32(0xFFFF), (w >> np.uint32(16)) & np.uint32(0x7FFF), (w >> np.uint32(31)).astype(bool)
 
 
 __all__ = ["ReedSolomon", "rs_encode", "rs_generator", "interleave_codewords", "ccsds_randomizer", "ccsds_dual_basis", "CCSDS_RS_255_223",

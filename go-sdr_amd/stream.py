@@ -1040,20 +1040,12 @@ def equalized_rows(src, bank, block=READER_BLOCK):
             yield bank.push(symbols, counts), counts
 
 
-# ---- a Reader, or a symbol-timing bank's pushes, through the frame sync bank (include/hzsdr_framesync.h) ----
+# ---- the banks fed symbols with counts: what frame_rows, hdlc_frames, decoded_frames and ldpc_frames do alike ----
 
-def frame_rows(src, bank, cap=4, block=READER_BLOCK):
-    """Push `src` through `bank` (a framesync.FrameSync on a HOST context) and yield, per push, bank.ragged(...) of its
-    results: a list of `rows` triples (frames (k, FB) uint8, positions (k,), info (k,)).  `src` is a Reader of complex64
-    samples at ONE sample per symbol, read to its end in blocks of `block` symbols (a one-row complex bank), or any
-    iterable of (symbols, counts) pairs -- what symbol_rows(...) yields -- or of blocks of symbols alone.  `cap` frames
-    per row and push are kept; a row that accepted more raises ErrShortBuffer, since nothing here may be lost in silence.  The
-    state carries from block to block; a frame still open at the end is not emitted."""
-    def push(symbols, counts=None):
-        frames, positions, info, got = bank.push(symbols, counts, cap)
-        if int(got.max()) > cap:
-            raise ErrShortBuffer("sdr: a row accepted more frames in one push than frame_rows keeps")
-        return bank.ragged(frames, positions, info, got)
+def _pushed_frames(src, bank, block, push):
+    """push(symbols, counts) of every push of `src`: a Reader of complex64 samples read to its end in blocks of `block`
+    symbols into a complex `bank` (counts is None), or an iterable of (symbols, counts) pairs or of blocks of symbols
+    alone; empty reads and blocks are passed over."""
     if isinstance(src, Reader):
         if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
             raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
@@ -1070,6 +1062,31 @@ def frame_rows(src, bank, cap=4, block=READER_BLOCK):
         symbols, counts = b if isinstance(b, tuple) else (b, None)
         if symbols.shape[-1]:
             yield push(symbols, counts)
+
+
+def _soft_beside(bank, soft):
+    """the checks of a soft frame bank beside the frame sync bank `bank`"""
+    if soft.rows != bank.rows or soft.P != bank.P or soft.kind != bank.kind or soft.B != bank.B or list(soft.maps) != list(bank.maps):
+        raise ValueError("sdr: the soft frame bank's rows, kind, bits per symbol, payload bits and maps are the frame sync bank's")
+    if bank.diff != 0:
+        raise ValueError("sdr: a frame sync bank with a differential decoding has no soft counterpart")
+
+
+# ---- a Reader, or a symbol-timing bank's pushes, through the frame sync bank (include/hzsdr_framesync.h) ----
+
+def frame_rows(src, bank, cap=4, block=READER_BLOCK):
+    """Push `src` through `bank` (a framesync.FrameSync on a HOST context) and yield, per push, bank.ragged(...) of its
+    results: a list of `rows` triples (frames (k, FB) uint8, positions (k,), info (k,)).  `src` is a Reader of complex64
+    samples at ONE sample per symbol, read to its end in blocks of `block` symbols (a one-row complex bank), or any
+    iterable of (symbols, counts) pairs -- what symbol_rows(...) yields -- or of blocks of symbols alone.  `cap` frames
+    per row and push are kept; a row that accepted more raises ErrShortBuffer, since nothing here may be lost in silence.  The
+    state carries from block to block; a frame still open at the end is not emitted."""
+    def push(symbols, counts=None):
+        frames, positions, info, got = bank.push(symbols, counts, cap)
+        if int(got.max()) > cap:
+            raise ErrShortBuffer("sdr: a row accepted more frames in one push than frame_rows keeps")
+        return bank.ragged(frames, positions, info, got)
+    yield from _pushed_frames(src, bank, block, push)
 
 
 # ---- the HDLC deframer bank where the frame sync bank stands (include/hzsdr_hdlc.h) ----
@@ -1086,22 +1103,7 @@ def hdlc_frames(src, bank, cap=4, block=READER_BLOCK):
         if int(got.max()) > cap:
             raise ErrShortBuffer("sdr: a row emitted more frames in one push than hdlc_frames keeps")
         return bank.ragged(frames, positions, info, got)
-    if isinstance(src, Reader):
-        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
-            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
-        buf = make_samples(src.sample_format(), block)
-        while True:
-            try:
-                k = src.read(buf)
-            except EOF:
-                break
-            if k:
-                yield push(buf[:k])
-        return
-    for b in src:
-        symbols, counts = b if isinstance(b, tuple) else (b, None)
-        if symbols.shape[-1]:
-            yield push(symbols, counts)
+    yield from _pushed_frames(src, bank, block, push)
 
 
 # ---- frame_rows with the Viterbi decoder bank behind the frame sync bank (include/hzsdr_viterbi.h) ----
@@ -1119,10 +1121,7 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, 
     if decoder.rows != bank.rows or decoder.N != bank.P:
         raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
     if soft is not None:
-        if soft.rows != bank.rows or soft.P != bank.P or soft.kind != bank.kind or soft.B != bank.B or list(soft.maps) != list(bank.maps):
-            raise ValueError("sdr: the soft frame bank's rows, kind, bits per symbol, payload bits and maps are the frame sync bank's")
-        if bank.diff != 0:
-            raise ValueError("sdr: a frame sync bank with a differential decoding has no soft counterpart")
+        _soft_beside(bank, soft)
         if decoder.kind != VITERBI_SOFT_F32:
             raise ValueError("sdr: behind a soft frame bank the decoder takes VITERBI_SOFT_F32 input")
 
@@ -1139,22 +1138,7 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, 
         found = bank.ragged(frames, positions, info, got)
         rows = [(d, p, i, m, ok) for (_, p, i), (d, m, ok) in zip(found, decoder.ragged(data, verdict, got))]
         return rows if more is None else more(rows)
-    if isinstance(src, Reader):
-        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
-            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
-        buf = make_samples(src.sample_format(), block)
-        while True:
-            try:
-                k = src.read(buf)
-            except EOF:
-                break
-            if k:
-                yield push(buf[:k])
-        return
-    for b in src:
-        symbols, counts = b if isinstance(b, tuple) else (b, None)
-        if symbols.shape[-1]:
-            yield push(symbols, counts)
+    yield from _pushed_frames(src, bank, block, push)
 
 
 # ---- decoded_frames with the Reed-Solomon decoder bank behind the Viterbi bank (include/hzsdr_rs.h) ----
@@ -1189,10 +1173,7 @@ def ldpc_frames(src, bank, soft, decoder, cap=4, block=READER_BLOCK):
     in one push raises ErrShortBuffer."""
     if decoder.rows != bank.rows or decoder.N != bank.P:
         raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
-    if soft.rows != bank.rows or soft.P != bank.P or soft.kind != bank.kind or soft.B != bank.B or list(soft.maps) != list(bank.maps):
-        raise ValueError("sdr: the soft frame bank's rows, kind, bits per symbol, payload bits and maps are the frame sync bank's")
-    if bank.diff != 0:
-        raise ValueError("sdr: a frame sync bank with a differential decoding has no soft counterpart")
+    _soft_beside(bank, soft)
     if decoder.kind != LDPC_SOFT_F32:
         raise ValueError("sdr: behind a soft frame bank the decoder takes LDPC_SOFT_F32 input")
 
@@ -1204,22 +1185,7 @@ def ldpc_frames(src, bank, soft, decoder, cap=4, block=READER_BLOCK):
             raise ErrShortBuffer("sdr: a row accepted more frames in one push than ldpc_frames keeps")
         found = bank.ragged(frames, positions, info, got)
         return [(d, p, i, u, it, ok) for (_, p, i), (d, u, it, ok) in zip(found, decoder.ragged(data, verdict, got))]
-    if isinstance(src, Reader):
-        if src.sample_format() != FMT_C64 or bank.kind != FMT_C64:
-            raise ErrSampleFormatMismatch("sdr: iq sample formats do not match")
-        buf = make_samples(src.sample_format(), block)
-        while True:
-            try:
-                k = src.read(buf)
-            except EOF:
-                break
-            if k:
-                yield push(buf[:k])
-        return
-    for b in src:
-        symbols, counts = b if isinstance(b, tuple) else (b, None)
-        if symbols.shape[-1]:
-            yield push(symbols, counts)
+    yield from _pushed_frames(src, bank, block, push)
 
 
 # ---- a Reader through the tuner bank (include/hzsdr_tuner.h) -----------------------------------

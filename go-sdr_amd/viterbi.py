@@ -21,8 +21,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import ErrInvalidArgument, _is_torch, lib
-from ._frames import block_ptr, dense_ptr, new_like
+from . import ErrInvalidArgument
+from ._frames import DecoderBank
 from ._capi import (VITERBI_BITS, VITERBI_FORM_LDS, VITERBI_FORM_SCRATCH, VITERBI_MAX_BITS, VITERBI_MAX_FRAMES, VITERBI_MAX_K, VITERBI_MAX_PATTERN,
                     VITERBI_MAX_RATE, VITERBI_MAX_ROWS, VITERBI_MIN_K, VITERBI_SOFT_F32, VITERBI_TAIL, VITERBI_TRUNCATED)
 
@@ -79,17 +79,18 @@ def crc_register(bits, C, poly, init=0, xorout=0):
     return reg ^ int(xorout)
 
 
-class ViterbiDecoder:
+class ViterbiDecoder(DecoderBank):
     """hzsdr_viterbi: decode(frames, counts) -> (data, info).  `kind` is VITERBI_BITS (uint8 frames of FB = ceil(N / 8)
     bytes, most significant bit first: FrameSync.push's frames) or VITERBI_SOFT_F32 (float32 frames of N values, positive
     meaning 1).  frames is (rows, cap, FB or N) -- (cap, ...) will do for one row -- with contiguous rows and any row
     pitch.  `crc` is None or (bits, poly, init, xorout).  numpy in a HOST context; torch tensors on the context's device,
     written on the context's stream, in a DEVICE context (info and counts are int32 there: the same bits)."""
+    _c = _noun = "viterbi"
+    _bits = VITERBI_BITS
 
     def __init__(self, ctx, kind, K, gens, data_bits, inv=0, pattern=None, termination=VITERBI_TAIL, scale=1.0, crc=None, rows=1):
-        self.ctx, self.kind, self.rows = ctx, int(kind), int(rows)
-        if self.rows <= 0:
-            raise ErrInvalidArgument("viterbi: rows is at least 1")
+        self.kind = int(kind)
+        self._open(ctx, rows)
         gens = [int(g) for g in gens]
         self.K, self.gens, self.n, self.inv, self.D = int(K), gens, len(gens), int(inv), int(data_bits)
         self.pattern, self.pattern_bits = _pattern(pattern, self.n)
@@ -99,23 +100,17 @@ class ViterbiDecoder:
         if not 1 <= self.n <= 8 or len(self.crc) != 4 or min(values) < 0 or max(gens + [self.K, self.inv, self.pattern_bits, *self.crc]) >= 1 << 32 or \
                 self.pattern >= 1 << 64 or self.D >= 1 << 62:
             raise ErrInvalidArgument("viterbi: generators, sizes, the pattern and the CRC are unsigned values of their widths")
-        self._h = C.c_void_p()
         g = (C.c_uint * self.n)(*gens)
-        ctx._ck(lib.hzsdr_viterbi_create(ctx._h, self.kind, self.K, self.n, g, self.inv, self.pattern, self.pattern_bits, self.termination, self.D,
-                                         self.scale, *self.crc, self.rows, C.byref(self._h)))
+        self._create(self.kind, self.K, self.n, g, self.inv, self.pattern, self.pattern_bits, self.termination, self.D, self.scale, *self.crc)
         self.N, self.frame_bytes, self.T, self.data_bytes = self.sizes()
 
     def sizes(self):
         """(N received positions, FB = ceil(N / 8), T trellis steps, DB = ceil(D / 8)) of a frame"""
-        v = [C.c_size_t(0) for _ in range(4)]
-        self.ctx._ck(lib.hzsdr_viterbi_sizes(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._sizes("sizes", 4)
 
     def plan(self):
         """(frames per wave, states per lane, bytes of a frame's decisions, VITERBI_FORM_LDS or VITERBI_FORM_SCRATCH)"""
-        g, s, d, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0)
-        self.ctx._ck(lib.hzsdr_viterbi_plan(self._h, C.byref(g), C.byref(s), C.byref(d), C.byref(f)))
-        return g.value, s.value, d.value, f.value
+        return self._plan()
 
     def decode(self, frames, counts=None, cap=None, out=None):
         """Decode min(counts[r], cap) frames of every row -> (data uint8 (rows, cap, DB), info (rows, cap) =
@@ -123,49 +118,16 @@ class ViterbiDecoder:
         cap are clamped); without it every row decodes cap frames.  `cap` defaults to the frames' second-last extent.
         Slots from a row's count up hold what the destination held (a new one is zero).  `out`, when given, is such a
         pair (data, info); data may be a view with a row pitch above cap * DB."""
-        R = self.rows
-        width = self.frame_bytes if self.kind == VITERBI_BITS else self.N
-        dtype = np.uint8 if self.kind == VITERBI_BITS else np.float32
-        if frames.ndim == 2 and R == 1:
-            frames = frames[None]
-        if frames.ndim != 3:
-            raise ValueError("viterbi: frames are (rows, cap, FB or N)")
-        cap = int(frames.shape[1]) if cap is None else int(cap)
-        fptr, fpitch = block_ptr(frames, (R, cap, width), dtype, "frames", "viterbi")
-        if out is None:
-            out = (new_like((R, cap, self.data_bytes), np.uint8, frames), new_like((R, cap), np.uint32, frames))
-        data, info = out
-        dptr, dpitch = block_ptr(data, (R, cap, self.data_bytes), np.uint8, "data", "viterbi")
-        iptr = dense_ptr(info, (R, cap), np.uint32, "info", "viterbi", "int32")
-        cptr = None if counts is None else dense_ptr(counts, (R,), np.uint32, "the frames' counts", "viterbi", "int32")
-        self.ctx._ck(lib.hzsdr_viterbi_decode(self._h, fptr, fpitch, cptr, cap, dptr, dpitch, iptr))
-        return data, info
+        return self._decode(frames, counts, cap, out)
 
     def ragged(self, data, info, counts=None):
         """A call's results -> a list of `rows` host triples (data (k, DB), metric (k,) uint32, crc_ok (k,) bool),
         k = min(counts[r], cap) (this waits for the device in a DEVICE context)."""
-        if _is_torch(data):
-            data, info = data.cpu().numpy(), info.cpu().numpy()
-            counts = None if counts is None else counts.cpu().numpy()
-        cap = data.shape[1]
-        info = np.asarray(info).view(np.uint32)
-        got = np.full(self.rows, cap, np.uint32) if counts is None else np.asarray(counts).reshape(-1).view(np.uint32)
-        out = []
-        for r, c in enumerate(got):
-            k = min(int(c), cap)
-            out.append((data[r, :k].copy(), info[r, :k] & np.uint32(0x7FFFFFFF), (info[r, :k] >> np.uint32(31)).astype(bool)))
-        return out
+        return self._ragged(data, info, counts)
 
-    def close(self):
-        if self._h:
-            lib.hzsdr_viterbi_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    @staticmethod
+    def _fields(w):
+        return w & np.uint32(0x7FFFFFFF), (w >> np.uint32(31)).astype(bool)
 
 
 __all__ = ["ViterbiDecoder", "conv_encode", "puncture_pattern", "crc_register", "CCSDS_K7", "VITERBI_BITS", "VITERBI_SOFT_F32", "VITERBI_TAIL",
