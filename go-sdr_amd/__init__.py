@@ -515,6 +515,16 @@ class Context:
         from .ldpc import LdpcDecoder
         return LdpcDecoder(self, kind, code, received, head, data_bits, scale, level, max_iters, norm, offset, rows)
 
+    def demapper(self, kind, points, symbols, perm=None, flip=None, gain=1.0, rows=1):
+        """The demapper bank (include/hzsdr_demap.h, demap.Demapper): frames of `symbols` received symbols -- complex
+        (DEMAP_C64), real (DEMAP_REAL_F32) or per-bit values already (DEMAP_LLR_F32, `points` None): the soft frame
+        bank's values as they are -- to max-log soft values against the 2^m `points` (psk_points, qam_points,
+        pam_points), scaled by `gain` (one value or one per row: demap_gain), put into the decoder's order by `perm`
+        (block_interleaver; DEMAP_ERASED marks a hole) and sign by `flip` (pack_flip), over `rows` rows: what
+        ViterbiDecoder and LdpcDecoder read as soft input."""
+        from .demap import Demapper
+        return Demapper(self, kind, points, symbols, perm, flip, gain, rows)
+
     def reed_solomon(self, code, interleave=1, in_map=None, out_map=None, scramble=None, rows=1):
         """The Reed-Solomon decoder bank (include/hzsdr_rs.h, rs.ReedSolomon): frames of `interleave` symbol-interleaved
         codewords of `code` = (gfpoly, fcr, prim, nroots, n) -- CCSDS_RS_255_223, CCSDS_RS_255_239, DVB_RS_204_188 -- the
@@ -1001,6 +1011,9 @@ from .hdlc import Hdlc, hdlc_encode, hdlc_fcs16, hdlc_fcs32, hdlc_line  # noqa: 
 from ._capi import (LDPC_BITS, LDPC_FORM_TABLES_CACHE, LDPC_FORM_TABLES_LDS, LDPC_MAX_BITS, LDPC_MAX_CHECKS, LDPC_MAX_DEGREE,  # noqa: E402
                     LDPC_MAX_EDGES, LDPC_MAX_FRAMES, LDPC_MAX_ITERS, LDPC_MAX_ROWS, LDPC_MAX_VARIABLES, LDPC_SOFT_F32)
 from .ldpc import LdpcCode, LdpcDecoder, ldpc_encode, ldpc_systematic, qc_code, regular_code  # noqa: E402
+from ._capi import (DEMAP_C64, DEMAP_ERASED, DEMAP_FORM_GROUPED, DEMAP_FORM_PERM, DEMAP_FORM_TREE, DEMAP_LLR_F32, DEMAP_MAX_BITS,  # noqa: E402
+                    DEMAP_MAX_FRAMES, DEMAP_MAX_LLRS, DEMAP_MAX_OUT, DEMAP_MAX_ROWS, DEMAP_MAX_SYMBOLS, DEMAP_REAL_F32)
+from .demap import Demapper, block_interleaver, demap_gain, map_bits, pack_flip, pam_points, psk_points, qam_points  # noqa: E402
 from .spectrum import Spectrum  # noqa: E402
 
 ZERO_FIRST, NEGATIVE_FIRST = ORDER_ZERO_FIRST, ORDER_NEGATIVE_FIRST

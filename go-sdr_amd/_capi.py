@@ -427,6 +427,19 @@ LDPC_MAX_ROWS, LDPC_MAX_CHECKS, LDPC_MAX_VARIABLES, LDPC_MAX_EDGES, LDPC_MAX_DEG
 LDPC_BITS, LDPC_SOFT_F32 = 1, 32
 LDPC_FORM_TABLES_LDS, LDPC_FORM_TABLES_CACHE = 1, 2
 
+# name -> (restype, argtypes); every symbol include/hzsdr_demap.h declares
+DEMAP_SIGNATURES = {
+    "hzsdr_demap_create": (i32, [vp, i32, C.c_uint, C.POINTER(f32), sz, C.POINTER(C.c_uint32), sz, C.POINTER(C.c_uint8), C.POINTER(f32), sz, sz, pvp]),
+    "hzsdr_demap_run": (i32, [vp, vp, sz, vp, sz, vp, sz]),
+    "hzsdr_demap_sizes": (i32, [vp, psz, psz, psz, psz]),
+    "hzsdr_demap_plan": (i32, [vp, psz, psz, psz, C.POINTER(i32)]),
+    "hzsdr_demap_free": (i32, [vp]),
+}
+DEMAP_MAX_ROWS, DEMAP_MAX_BITS, DEMAP_MAX_SYMBOLS, DEMAP_MAX_LLRS, DEMAP_MAX_OUT, DEMAP_MAX_FRAMES = 8192, 8, 8192, 16384, 8192, 1 << 22
+DEMAP_ERASED = 0xFFFFFFFF
+DEMAP_C64, DEMAP_REAL_F32, DEMAP_LLR_F32 = 1, 32, 33
+DEMAP_FORM_GROUPED, DEMAP_FORM_PERM, DEMAP_FORM_TREE = 1, 2, 4
+
 # name -> (restype, argtypes); every symbol include/hzsdr_rs.h declares
 RS_SIGNATURES = {
     "hzsdr_rs_create": (i32, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, sz, sz, pvp]),
@@ -457,7 +470,7 @@ for _name, (_res, _args) in (*SIGNATURES.items(), *SPECTRUM_SIGNATURES.items(), 
                              *CHANBANK_SIGNATURES.items(), *COVAR_SIGNATURES.items(), *IIR_SIGNATURES.items(), *SYMSYNC_SIGNATURES.items(),
                              *CARRIER_SIGNATURES.items(), *AGC_SIGNATURES.items(), *FRAMESYNC_SIGNATURES.items(), *VITERBI_SIGNATURES.items(),
                              *RS_SIGNATURES.items(), *SOFTFRAME_SIGNATURES.items(), *EQUALIZER_SIGNATURES.items(), *HDLC_SIGNATURES.items(),
-                             *LDPC_SIGNATURES.items()):
+                             *LDPC_SIGNATURES.items(), *DEMAP_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header and library disagree
     _fn.restype = _res
     _fn.argtypes = _args

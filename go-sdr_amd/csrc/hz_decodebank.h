@@ -3,6 +3,7 @@
 // its geometry, its device tables and, as a static, the noun that starts its messages.  A bank decodes
 // min(counts[r], cap) frames of every row into a block of data bytes and an info word per slot, leaves every other slot
 // as it was and keeps no state; the arithmetic of a call is hz_decodebank_plan.h.  Nothing here knows which bank it serves.
+// The demapper bank (hz_demap.hip) in front of them is the same call with floats on both sides and no info word: run().
 #pragma once
 #include <initializer_list>
 #include <string>
@@ -49,11 +50,13 @@ inline int upload(hzsdr_ctx *ctx, const char *what, std::initializer_list<Table>
 
 // A call: the checks in their order, the rows staged (`isz`: the bytes of an input element), launch(FrameArgs, cap,
 // slots) -> status with the leading part of the kernel's arguments filled in, the rows brought back.
-template <class F, class Launch>
-int decode(F *f, const dbp::Slots &s, size_t isz, const dbp::Call &c, const uint32_t *in_counts, uint32_t *info, Launch launch) {
+// `osz`: the bytes of an output element (the decoders write bytes; hz_demap.hip writes floats and has no info word:
+// a null `info` is not staged); `check(&why)` is the call's validation.
+template <class F, class Check, class Launch>
+int run(F *f, const dbp::Slots &s, size_t isz, size_t osz, const dbp::Call &c, const uint32_t *in_counts, uint32_t *info, Check check, Launch launch) {
     hzsdr_ctx *ctx = f->ctx;
     const char *why = nullptr;
-    const int bad = dbp::check_call(s, c, &why);
+    const int bad = check(&why);
     if (bad) return fail(ctx, bad == dbp::kDstTooSmall ? HZSDR_ERR_DST_TOO_SMALL : HZSDR_ERR_INVALID_ARGUMENT, who<F>(why));
     HZ_TRY(enter(ctx));
     Stage st(ctx);
@@ -65,11 +68,15 @@ int decode(F *f, const dbp::Slots &s, size_t isz, const dbp::Call &c, const uint
     HZ_TRY(st.in_rows(0, (const void *)c.in, R, iw, istride, isz, &din, &istride));
     if (in_counts) HZ_TRY(st.in(1, in_counts, R * sizeof(uint32_t), &dic));
     // the slots behind a row's count, and what lies between a slot's data and the next slot, stay as they are
-    HZ_TRY(stage_out_rows_preserved(st, 2, (void *)c.out, R, ow, c.out_stride, 1, &dout, &ostride));
-    HZ_TRY(st.out_preserve(3, info, R * cap * sizeof(uint32_t), &dinfo));
+    HZ_TRY(stage_out_rows_preserved(st, 2, (void *)c.out, R, ow, c.out_stride, osz, &dout, &ostride));
+    if (info) HZ_TRY(st.out_preserve(3, info, R * cap * sizeof(uint32_t), &dinfo));
     HZ_TRY(launch(dbp::FrameArgs{din, istride, (const uint32_t *)dic, (uint8_t *)dout, ostride, (uint32_t *)dinfo}, (uint32_t)cap, (uint32_t)(R * cap)));
     HZ_HIP(ctx, hipGetLastError());
     return st.finish();
+}
+template <class F, class Launch>
+int decode(F *f, const dbp::Slots &s, size_t isz, const dbp::Call &c, const uint32_t *in_counts, uint32_t *info, Launch launch) {
+    return run(f, s, isz, 1, c, in_counts, info, [&](const char **why) { return dbp::check_call(s, c, why); }, launch);
 }
 
 }  // namespace db

@@ -40,6 +40,7 @@
 #include "../../include/hzsdr_hdlc.h"
 #include "../../include/hzsdr_viterbi.h"
 #include "../../include/hzsdr_ldpc.h"
+#include "../../include/hzsdr_demap.h"
 #include "../../include/hzsdr_rs.h"
 #include "../../include/hzsdr_softframe.h"
 #include "../../include/hzsdr_spectrum.h"
@@ -1807,6 +1808,63 @@ public:
 private:
     int kind_;
     size_t n_ = 0, vars_ = 0, checks_ = 0, edges_ = 0;
+};
+
+// The demapper bank (include/hzsdr_demap.h): frames of received symbols -- complex (HZSDR_DEMAP_C64: the soft frame bank's
+// floats re, im ...), real (HZSDR_DEMAP_REAL_F32) or per-bit values already (HZSDR_DEMAP_LLR_F32) -- to max-log soft values
+// against 2^m points listed by label, scaled by a gain (one, or one per row), put into the decoder's order by perm
+// (HZSDR_DEMAP_ERASED marks a hole) and sign by flip, over `rows` rows of `cap` frame slots: what Viterbi and Ldpc read as
+// soft input.  Run handles min(in_counts[r], cap) frames of every row (row r starts r * in_stride floats into `in`; dense
+// rows when in_stride is 0; every row has cap frames when in_counts is null).  The bank keeps no state.
+class Demapper {
+public:
+    struct Config {
+        unsigned bits_per_symbol = 1;
+        std::vector<float> points;  // 2 M floats re, im (C64), M floats (REAL_F32), none (LLR_F32)
+        size_t symbols = 0;
+        std::vector<uint32_t> perm;  // empty: the order is kept, N = symbols * bits_per_symbol
+        std::vector<uint8_t> flip;   // empty: no sign is flipped; else ceil(N / 8) packed bytes
+        std::vector<float> gains = {1.0f};
+    };
+    Demapper(const Context &x, int kind, const Config &c, size_t rows = 1) : x_(x), rows_(rows) {
+        const size_t n = c.perm.empty() ? c.symbols * c.bits_per_symbol : c.perm.size();
+        if (!c.flip.empty() && c.flip.size() != (n + 7) / 8) throw std::invalid_argument("Demapper: flip has ceil(N / 8) bytes");
+        check(x_.raw(), hzsdr_demap_create(x_.raw(), kind, c.bits_per_symbol, c.points.empty() ? nullptr : c.points.data(), c.symbols,
+                                           c.perm.empty() ? nullptr : c.perm.data(), n, c.flip.empty() ? nullptr : c.flip.data(),
+                                           c.gains.empty() ? nullptr : c.gains.data(), c.gains.size(), rows, &h_));
+        check(x_.raw(), hzsdr_demap_sizes(h_, &s_, &w_, &m_, &n_));
+    }
+    Demapper(const Demapper &) = delete;
+    Demapper &operator=(const Demapper &) = delete;
+    ~Demapper() { if (h_) hzsdr_demap_free(h_); }
+    // into `out`, rows of out_stride floats (dense rows of cap * N when 0)
+    void Run(const float *in, size_t cap, float *out, size_t in_stride = 0, const uint32_t *in_counts = nullptr, size_t out_stride = 0) {
+        check(x_.raw(), hzsdr_demap_run(h_, in, in_stride ? in_stride : cap * w_, in_counts, cap, out, out_stride ? out_stride : cap * n_));
+    }
+    // -> a dense block (rows, cap, N); slots behind a row's count are zero
+    std::vector<float> Run(const float *in, size_t cap, size_t in_stride = 0, const uint32_t *in_counts = nullptr) {
+        std::vector<float> out(rows_ * cap * n_, 0.0f);
+        Run(in, cap, out.data(), in_stride, in_counts);
+        return out;
+    }
+    // -> (frames per workgroup, threads per frame, LDS bytes of a frame's values, a sum of HZSDR_DEMAP_FORM_*)
+    std::tuple<size_t, size_t, size_t, int> Plan() const {
+        size_t g = 0, t = 0, b = 0;
+        int f = 0;
+        check(x_.raw(), hzsdr_demap_plan(h_, &g, &t, &b, &f));
+        return {g, t, b, f};
+    }
+    size_t Rows() const { return rows_; }
+    size_t Symbols() const { return s_; }
+    size_t FrameFloats() const { return w_; }
+    size_t BitsPerSymbol() const { return m_; }
+    size_t Values() const { return n_; }
+
+private:
+    const Context &x_;
+    size_t rows_;
+    size_t s_ = 0, w_ = 0, m_ = 0, n_ = 0;
+    hzsdr_demap *h_ = nullptr;
 };
 
 // The Reed-Solomon decoder bank (include/hzsdr_rs.h): frames of `interleave` symbol-interleaved codewords over GF(2^8) --

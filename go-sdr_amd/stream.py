@@ -1072,6 +1072,19 @@ def _soft_beside(bank, soft):
         raise ValueError("sdr: a frame sync bank with a differential decoding has no soft counterpart")
 
 
+def _decoder_behind(bank, decoder, demap, soft):
+    """the checks of a decoder behind the frame sync bank `bank`, with a demap.Demapper between the soft frame bank and
+    the decoder when `demap` is given"""
+    if demap is None:
+        if decoder.rows != bank.rows or decoder.N != bank.P:
+            raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
+        return
+    if soft is None:
+        raise ValueError("sdr: a demapper stands behind a soft frame bank")
+    if demap.rows != bank.rows or decoder.rows != bank.rows or decoder.N != demap.N or demap.W != bank.P:
+        raise ValueError("sdr: the demapper takes the frame sync bank's rows and payload floats and gives the decoder's received values")
+
+
 # ---- a Reader, or a symbol-timing bank's pushes, through the frame sync bank (include/hzsdr_framesync.h) ----
 
 def frame_rows(src, bank, cap=4, block=READER_BLOCK):
@@ -1108,7 +1121,7 @@ def hdlc_frames(src, bank, cap=4, block=READER_BLOCK):
 
 # ---- frame_rows with the Viterbi decoder bank behind the frame sync bank (include/hzsdr_viterbi.h) ----
 
-def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, soft=None):
+def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, soft=None, demap=None):
     """Push `src` through `bank` (a framesync.FrameSync) as frame_rows does and decode every push's frames with
     `decoder` (a viterbi.ViterbiDecoder of VITERBI_BITS input over the same rows, whose received positions N are the
     bank's payload bits).  The frame block and its counts go from the one bank to the other as they are, in the
@@ -1117,9 +1130,10 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, 
     frames in one push raises ErrShortBuffer.
     `soft`, when given, is a softframe.SoftFrames beside `bank` (Context.soft_frames(bank)) and `decoder` takes
     VITERBI_SOFT_F32 input: every push runs frame sync -> soft frame bank -> decoder, and the decoder reads the frames'
-    payload floats (include/hzsdr_softframe.h) where it read their decided bits; the tuples are the same."""
-    if decoder.rows != bank.rows or decoder.N != bank.P:
-        raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
+    payload floats (include/hzsdr_softframe.h) where it read their decided bits; the tuples are the same.
+    `demap`, when given with `soft`, is a demap.Demapper over the same rows whose W is the bank's P and whose N is the
+    decoder's N: it stands behind `soft` and in front of the decoder, and its block goes on as the others do."""
+    _decoder_behind(bank, decoder, demap, soft)
     if soft is not None:
         _soft_beside(bank, soft)
         if decoder.kind != VITERBI_SOFT_F32:
@@ -1131,7 +1145,7 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, 
             data, verdict = decoder.decode(frames, got, cap)
         else:
             values, _ = soft.push(symbols, counts, positions, info, got, cap)
-            data, verdict = decoder.decode(values, got, cap)
+            data, verdict = decoder.decode(values if demap is None else demap.run(values, got, cap), got, cap)
         more = None if _behind is None else _behind(data, got, cap)  # (corrected_frames: launched before anything is read)
         if int(got.max()) > cap:
             raise ErrShortBuffer("sdr: a row accepted more frames in one push than decoded_frames keeps")
@@ -1143,12 +1157,12 @@ def decoded_frames(src, bank, decoder, cap=4, block=READER_BLOCK, _behind=None, 
 
 # ---- decoded_frames with the Reed-Solomon decoder bank behind the Viterbi bank (include/hzsdr_rs.h) ----
 
-def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK, soft=None):
+def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK, soft=None, demap=None):
     """decoded_frames with `rs` (an rs.ReedSolomon over the same rows whose frame bytes are the decoder's data bytes)
     behind the Viterbi decoder: the decoded block and the counts go on to it as they are, in the context's memory space,
     with nothing read in between.  Yields, per push, a list of `rows` tuples (data (k, I k) uint8 -- the corrected data
-    bytes --, positions (k,), sync info (k,), metric (k,), crc_ok (k,), E (k,), nfail (k,), ok (k,)).  `soft`: as in
-    decoded_frames."""
+    bytes --, positions (k,), sync info (k,), metric (k,), crc_ok (k,), E (k,), nfail (k,), ok (k,)).  `soft` and
+    `demap`: as in decoded_frames."""
     if rs.rows != decoder.rows or rs.frame_bytes != decoder.data_bytes or decoder.D != 8 * rs.frame_bytes:
         raise ValueError("sdr: the Reed-Solomon bank's rows and frame bytes are the decoder's rows and data bytes")
 
@@ -1158,21 +1172,22 @@ def corrected_frames(src, bank, decoder, rs, cap=4, block=READER_BLOCK, soft=Non
         def read(rows):
             return [(c, p, i, m, ok, e, nf, good) for (_, p, i, m, ok), (c, e, nf, good) in zip(rows, rs.ragged(clean, verdict, got))]
         return read
-    return decoded_frames(src, bank, decoder, cap, block, _behind=behind, soft=soft)
+    return decoded_frames(src, bank, decoder, cap, block, _behind=behind, soft=soft, demap=demap)
 
 
 # ---- frame sync -> soft frame bank -> the LDPC decoder bank (include/hzsdr_ldpc.h) ----
 
-def ldpc_frames(src, bank, soft, decoder, cap=4, block=READER_BLOCK):
+def ldpc_frames(src, bank, soft, decoder, cap=4, block=READER_BLOCK, demap=None):
     """Push `src` through `bank` (a framesync.FrameSync) as frame_rows does, gather every push's payload floats with
     `soft` (a softframe.SoftFrames beside `bank`: Context.soft_frames(bank)) and decode them with `decoder` (an
     ldpc.LdpcDecoder of LDPC_SOFT_F32 input over the same rows, whose received positions N are the bank's payload
     bits).  The blocks and their counts go from bank to bank as they are, in the context's memory space, with nothing
     read in between.  Yields, per push, a list of `rows` tuples (data (k, DB) uint8, positions (k,), sync info (k,),
     unsatisfied (k,), iters (k,), ok (k,)).  The checks are decoded_frames': a row that accepted more than `cap` frames
-    in one push raises ErrShortBuffer."""
-    if decoder.rows != bank.rows or decoder.N != bank.P:
-        raise ValueError("sdr: the decoder's rows and received bits are the frame sync bank's rows and payload bits")
+    in one push raises ErrShortBuffer.  `demap`, when given, is a demap.Demapper over the same rows whose W is the bank's
+    P and whose N is the decoder's N: it stands behind `soft` and in front of the decoder (symbols of more than two bits,
+    a deinterleaver, a derandomiser), and its block goes on as the others do."""
+    _decoder_behind(bank, decoder, demap, soft)
     _soft_beside(bank, soft)
     if decoder.kind != LDPC_SOFT_F32:
         raise ValueError("sdr: behind a soft frame bank the decoder takes LDPC_SOFT_F32 input")
@@ -1180,7 +1195,7 @@ def ldpc_frames(src, bank, soft, decoder, cap=4, block=READER_BLOCK):
     def push(symbols, counts=None):
         frames, positions, info, got = bank.push(symbols, counts, cap)
         values, _ = soft.push(symbols, counts, positions, info, got, cap)
-        data, verdict = decoder.decode(values, got, cap)
+        data, verdict = decoder.decode(values if demap is None else demap.run(values, got, cap), got, cap)
         if int(got.max()) > cap:
             raise ErrShortBuffer("sdr: a row accepted more frames in one push than ldpc_frames keeps")
         found = bank.ragged(frames, positions, info, got)

@@ -4,7 +4,9 @@
  * once.  It is a sibling of hzsdr_viterbi.h and stands where that bank stands: it takes the soft frame bank's float32
  * block (hzsdr_softframe.h) or the frame sync bank's `out` block (hzsdr_framesync.h) and their device-side counts as they
  * are, with no host read in between.  What it leaves to others: layered schedules; non-binary codes; shortening by known
- * bits; rate matching; the outer BCH code of DVB-S2; soft outputs of the decoder.  It ships no standard's tables: the
+ * bits; rate matching; the outer BCH code of DVB-S2; soft outputs of the decoder.  Symbols of more than two bits, bit
+ * interleaving, punctured positions inside a frame and a randomiser on the codeword (CCSDS 131.0-B) are undone in front of
+ * this bank by the demapper bank (hzsdr_demap.h), whose output block is this bank's input.  It ships no standard's tables: the
  * Python layer expands a quasi-cyclic base table (the form in which CCSDS 131.0-B, DVB-S2, 802.11n and 5G publish their
  * codes) into the compressed form below.
  *

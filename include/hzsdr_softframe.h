@@ -8,7 +8,8 @@
  * at float r * out_stride + f * P, sign bit clear meaning 1.  Nothing is read by the host in between.  What it leaves to
  * others: a soft form of the frame sync bank's differential decodings (diff != 0 there has NO soft counterpart here:
  * pair this bank with diff = 0 banks only); level normalisation (hzsdr_agc.h in front, the decoder's `scale` behind);
- * int8 soft values; demappers for more than two bits per symbol.
+ * int8 soft values.  Symbols of more than two bits, bit deinterleaving, depuncturing and derandomising of the soft values
+ * are the demapper bank's (hzsdr_demap.h), which takes this bank's block as it is.
  *
  * The entries live beside hzsdr.h and the other headers (same conventions, same status codes, same context).  The
  * reference has no such stage: the definition below is the contract, restated under tests/ (tests/host/softframe_ref.cpp
