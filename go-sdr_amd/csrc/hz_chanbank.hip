@@ -3,8 +3,9 @@
 // time modulo M, then y = W u as a float32 matrix product on v_mfma_f32_16x16x4_f32 -- A (2M x 2Mp, the DFT table as a
 // real matrix in MFMA operand order, made at create) times B (2Mp x T, the tile's folded frames) -- and stored as
 // complex rows (frame-major) or as one stream per channel (channel-major).  The term of the fold is hz_chanbank_math.h
-// (shared with tests/host/chanbank_ref.cpp), the host arithmetic (counts, tile, both layouts, position map, table) is
-// hz_chanbank_plan.h.
+// (shared with tests/host/chanbank_ref.cpp), the host arithmetic (tile, both layouts, table) is hz_chanbank_plan.h, the
+// stream's (counts, rotation, position map) hz_polyphase_plan.h; the object's host side (create, the push around the
+// launch, frames_for, pending, reset, free) is hz_polyphase.h.
 //
 // One kernel.  A workgroup of four waves takes T consecutive frames of a push, tile after tile.  The fold gives
 // 2^fold_shift lanes to a frame (a wave folds 64 >> fold_shift frames at once; consecutive lanes read consecutive
@@ -28,20 +29,16 @@
 #include "hz_chanbank_plan.h"
 #include "hz_polyphase.h"
 
-struct hzsdr_chanbank {
-    hzsdr_ctx *ctx;
-    int fmt;
-    uint32_t M, L, D;
-    int order, layout;
+struct hzsdr_chanbank : hz::pp::Bank {
+    static constexpr const char *noun = "chanbank", *create_name = "chanbank_create";
+    static constexpr const char *format_why = "unknown source format", *channels_why = "the channel count is 2 ... 255 (hzsdr_channelizer.h from 256 on)";
+    static constexpr hz::ppp::ChannelRule rule = hz::ppp::kMatrixRule;
+    static constexpr auto destroy = hzsdr_chanbank_free;
     hz::cp::Geom g{};
     uint64_t magic = 0;
     std::vector<float> taps_host;
-    std::vector<hz::cb::c32> W;            // M rows of Mp
-    float *taps = nullptr;                 // the prototype, L values
-    float *a_dev = nullptr;                // A in operand order
-    float2 *tail[2] = {nullptr, nullptr};  // the samples held for the next frame, converted: read one, write the other
-    int tcur = 0;
-    hz::cp::State st{};
+    std::vector<hz::cb::c32> W;  // M rows of Mp
+    float *a_dev = nullptr;      // A in operand order
 };
 
 namespace hz {
@@ -172,10 +169,9 @@ static int cb_launch_form(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
     // (tile after tile in a workgroup once the chip is full many times over: A is staged once per workgroup)
     const uint64_t cap = (uint64_t)c->ctx->num_cus * 16;
     const dim3 grid((unsigned)(a.tiles < cap ? a.tiles : cap)), block(cp::kThreads);
-    if (c->layout == HZSDR_CHANNELIZER_FRAME_MAJOR)
-        HZ_TRY(launch_fv(chanbank_tile_kernel<FMT, NC, A_LDS, HZSDR_CHANNELIZER_FRAME_MAJOR>, grid, block, c->g.lds_bytes, c->ctx->stream, a, out));
-    else
-        HZ_TRY(launch_fv(chanbank_tile_kernel<FMT, NC, A_LDS, HZSDR_CHANNELIZER_CHANNEL_MAJOR>, grid, block, c->g.lds_bytes, c->ctx->stream, a, out));
+    HZ_TRY(pp::with_layout(c->layout, [&](auto l) {
+        return launch_fv(chanbank_tile_kernel<FMT, NC, A_LDS, decltype(l)::value>, grid, block, c->g.lds_bytes, c->ctx->stream, a, out);
+    }));
     HZ_HIP(c->ctx, hipGetLastError());
     return HZSDR_OK;
 }
@@ -191,94 +187,48 @@ static int cb_launch(hzsdr_chanbank *c, const CbArgs &a, float2 *out) {
     return with_format(c->fmt, [&](auto f) { return cb_launch_fmt<decltype(f)::value>(c, a, out); });
 }
 
+// what create makes on the host: the tile, the table and A in operand order
+static void cb_host_tables(hzsdr_chanbank *c, const float *taps, std::vector<float> &A) {
+    c->g = cp::chanbank_geom(c->M);
+    c->magic = div_magic(c->M);
+    c->taps_host.assign(taps, taps + c->L);
+    c->W = cp::chanbank_tables(c->M);
+    A = cp::chanbank_fill_a(c->g, c->W);
+}
+
 }  // namespace hz
+
+// (the table's move into the object stays in the library's symbol table whatever was inlined above)
+template std::vector<hz::cb::c32> &std::vector<hz::cb::c32>::operator=(std::vector<hz::cb::c32> &&);
 
 extern "C" {
 
 int hzsdr_chanbank_create(hzsdr_ctx *ctx, int src_format, size_t channels, const float *taps, size_t n_taps, size_t hop, int order,
                           int layout, hzsdr_chanbank **out) {
     using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    const size_t m = channels;
-    if (format_size(src_format) == 0) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "chanbank: unknown source format");
-    if (m < cp::kMinChannels || m > cp::kMaxChannels)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the channel count is 2 ... 255 (hzsdr_channelizer.h from 256 on)");
-    if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: null taps");
-    static_assert(cp::kMaxTapsPerChannel == 32, "check_polyphase_args allows 32 taps per channel");
-    HZ_TRY(check_polyphase_args(ctx, "chanbank", m, n_taps, hop, order, layout));
-    HZ_TRY(enter(ctx));
-    hzsdr_chanbank *c = new hzsdr_chanbank{ctx, src_format, (uint32_t)m, (uint32_t)n_taps, (uint32_t)hop, order, layout};
-    c->g = cp::chanbank_geom(c->M);
-    c->magic = div_magic(c->M);
-    c->taps_host.assign(taps, taps + n_taps);
-    c->W = cp::chanbank_tables(c->M);
-    const std::vector<float> A = cp::chanbank_fill_a(c->g, c->W);
-    auto undo = [&](int rc) {
-        hzsdr_chanbank_free(c);
-        return rc;
-    };
-    hipError_t e = hipMalloc((void **)&c->taps, n_taps * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->a_dev, A.size() * sizeof(float));
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&c->tail[i], n_taps * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpyAsync(c->taps, taps, n_taps * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->a_dev, A.data(), A.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (taps is the caller's and A is local: free to go when create returns)
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "chanbank_create", __FILE__, __LINE__));
-    *out = c;
-    return HZSDR_OK;
+    std::vector<float> A;  // (local: free to go when create returns)
+    return pp::create(ctx, src_format, channels, taps, n_taps, hop, order, layout, out, [&](hzsdr_chanbank *c, std::vector<Table> &tables) {
+        cb_host_tables(c, taps, A);
+        tables.push_back({(void **)&c->a_dev, A.data(), A.size() * sizeof(float)});
+        return HZSDR_OK;
+    });
 }
 
-int hzsdr_chanbank_frames_for(const hzsdr_chanbank *c, size_t n_in, size_t *frames) {
-    if (!c || !frames) return HZSDR_ERR_INVALID_ARGUMENT;
-    const hz::cp::Step p = hz::cp::chanbank_step(c->st, c->M, c->L, c->D, n_in);
-    if (!p.ok) return hz::fail(c->ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the push is too long");
-    *frames = (size_t)p.F;
-    return HZSDR_OK;
-}
+int hzsdr_chanbank_frames_for(const hzsdr_chanbank *c, size_t n_in, size_t *frames) { return hz::pp::frames_for(c, n_in, frames); }
 
 int hzsdr_chanbank_push(hzsdr_chanbank *c, const void *in, size_t n_in, void *out, size_t out_frames_cap, size_t out_stride,
                         size_t *frames_written) {
     using namespace hz;
-    if (frames_written) *frames_written = 0;
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    hzsdr_ctx *ctx = c->ctx;
-    if (n_in && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: null input");
-    const cp::Step p = cp::chanbank_step(c->st, c->M, c->L, c->D, n_in);
-    if (!p.ok) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "chanbank: the push is too long");
-    const bool chmajor = c->layout == HZSDR_CHANNELIZER_CHANNEL_MAJOR;
-    const size_t F = (size_t)p.F, M = c->M;
-    // (the rows of a push: M channels of F frames, out_stride apart, or -- frame-major -- one run of F * M values)
-    HZ_TRY(check_rows_out(ctx, "chanbank", chmajor ? M : 1, out, out_frames_cap, out_stride, F, 0));
-    HZ_TRY(enter(ctx));
-    if (n_in == 0) return HZSDR_OK;
-    Stage st(ctx);
-    const void *din;
-    void *dout;
-    size_t dstride;
-    HZ_TRY(st.in(0, in, n_in * (size_t)format_size(c->fmt), &din));
-    HZ_TRY(st.out_rows(1, out, chmajor ? M : 1, chmajor ? F : F * M, out_stride, sizeof(float2), &dout, &dstride, true));
-    const cp::Geom &g = c->g;
-    const CbArgs a{din, c->tail[c->tcur], c->taps, c->a_dev, c->st.held, p.F, (p.F + g.T - 1) / g.T, dstride, c->magic,
-                   c->M, g.Mp, c->L / c->M, c->D, c->st.rot, g.steps, g.pitch, g.groups, g.fold_shift, g.b_floats, (uint32_t)g.a_floats,
-                   (uint32_t)(c->order == HZSDR_ORDER_NEGATIVE_FIRST)};
-    if (F) HZ_TRY(cb_launch(c, a, (float2 *)dout));
-    if (p.next.held) {
-        HZ_TRY(hold_samples(ctx, c->fmt, din, a.tail, a.held, p.V - p.next.held, p.next.held, c->tail[c->tcur ^ 1]));
-        c->tcur ^= 1;
-    }
-    c->st = p.next;
-    HZ_TRY(st.finish());
-    if (frames_written) *frames_written = F;
-    return HZSDR_OK;
+    return pp::push_frames(c, in, n_in, out, out_frames_cap, out_stride, frames_written, [&](const void *din, float2 *dout, size_t dstride, const ppp::Step &p) {
+        const cp::Geom &g = c->g;
+        const CbArgs a{din, c->held.now(), c->taps, c->a_dev, c->st.held, p.F, (p.F + g.T - 1) / g.T, dstride, c->magic,
+                       c->M, g.Mp, c->L / c->M, c->D, c->st.rot, g.steps, g.pitch, g.groups, g.fold_shift, g.b_floats, (uint32_t)g.a_floats,
+                       (uint32_t)c->negative_first()};
+        return cb_launch(c, a, dout);
+    });
 }
 
-int hzsdr_chanbank_pending(const hzsdr_chanbank *c, size_t *samples_held, uint64_t *frame_index) {
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (samples_held) *samples_held = (size_t)c->st.held;
-    if (frame_index) *frame_index = c->st.frame;
-    return HZSDR_OK;
-}
+int hzsdr_chanbank_pending(const hzsdr_chanbank *c, size_t *samples_held, uint64_t *frame_index) { return hz::pp::pending(c, samples_held, frame_index); }
 
 int hzsdr_chanbank_plan(const hzsdr_chanbank *c, size_t *tile_frames, size_t *tile_rows, int *form) {
     if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
@@ -306,19 +256,9 @@ int hzsdr_chanbank_readout(const hzsdr_chanbank *c, int what, size_t index, void
     return HZSDR_OK;
 }
 
-int hzsdr_chanbank_reset(hzsdr_chanbank *c) {
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    // (the held samples are only read behind a later push's own writes: nothing to clear, nothing to wait for)
-    c->st = hz::cp::State{};
-    return HZSDR_OK;
-}
+int hzsdr_chanbank_reset(hzsdr_chanbank *c) { return hz::pp::reset(c); }
 
-int hzsdr_chanbank_free(hzsdr_chanbank *c) {
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(c->ctx, {c->taps, c->a_dev, c->tail[0], c->tail[1]});
-    delete c;
-    return HZSDR_OK;
-}
+int hzsdr_chanbank_free(hzsdr_chanbank *c) { return hz::pp::release(c, {c ? c->a_dev : nullptr}); }
 
 }  // extern "C"
 

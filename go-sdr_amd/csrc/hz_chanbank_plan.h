@@ -2,9 +2,8 @@
 // tests/host/chanbank_plan.cpp can run it under the sanitizers and tests/host/chanbank_ref.cpp can transcribe the
 // kernel's indexing from the same functions.  Everything that can overflow lives here.
 //
-// The stream position is the channelizer's: the samples held (converted, below L), the rotation (position of the next
-// frame's first sample) mod M and the index of the next frame, all running values; no product with the stream length
-// is ever formed.
+// The stream position, what a push does to it, the rotation and the position map are the polyphase banks' own
+// (hz_polyphase_plan.h), taken by `using` and by their old names below.
 //
 // The product is A (2M x 2Mp, the DFT table as a real matrix, MFMA operand order, device memory and -- where it fits
 // beside B -- LDS) times B (2Mp x T, the folded frames of one tile, LDS) on v_mfma_f32_16x16x4_f32.  A workgroup of four
@@ -23,53 +22,24 @@
 #include <vector>
 
 #include "hz_chanbank_math.h"
+#include "hz_polyphase_plan.h"
 
 namespace hz {
 namespace cp {
 
-constexpr uint32_t kMinChannels = 2, kMaxChannels = 255, kMaxTapsPerChannel = 32;
+constexpr uint32_t kMinChannels = (uint32_t)ppp::kMatrixRule.lo, kMaxChannels = (uint32_t)ppp::kMatrixRule.hi, kMaxTapsPerChannel = ppp::kMaxTapsPerChannel;
 constexpr int kThreads = 256, kWaves = 4;
 constexpr uint32_t kGroupTiles = 2;  // 16-row tiles of A a wave works on at once
 constexpr uint32_t kLdsFloats = 16896;  // 66 KiB
-constexpr uint64_t kPushMax = (uint64_t)1 << 62;  // samples of one push: held + n and every index below 2^63
 
-// ---- the counts (the channelizer's chan_step) -------------------------------------------------------------
-struct State {
-    uint64_t held = 0;   // samples held for the next frame (below L)
-    uint32_t rot = 0;    // (stream position of the next frame's first sample) mod M
-    uint64_t frame = 0;  // index of the next frame
-};
-
-struct Step {
-    bool ok;        // false: the push is too long for the counts
-    uint64_t V, F;  // samples of the virtual buffer held ++ in; frames that complete in the push
-    State next;
-};
-
-// (rot + f D) mod M without a product of the stream length: f is reduced first
-HZ_HD uint32_t chanbank_rot(uint32_t rot, uint64_t f, uint32_t D, uint32_t M) {
-    return (uint32_t)((rot + (f % M) * D) % M);  // below 255 + 254 * 255
-}
-
-inline Step chanbank_step(const State &s, uint32_t M, uint32_t L, uint32_t D, uint64_t n) {
-    Step p{};
-    if (n > kPushMax) return p;
-    p.ok = true;
-    p.V = s.held + n;
-    p.F = p.V >= L ? (p.V - L) / D + 1 : 0;
-    p.next.held = p.V - p.F * D;  // (D <= M <= L: never a gap; below L)
-    p.next.rot = chanbank_rot(s.rot, p.F, D, M);
-    p.next.frame = s.frame + p.F;
-    return p;
-}
-
-// ---- the position map ----------------------------------------------------------------------------------
-// ascending signed frequency for NegativeFirst: position 0 is channel ceil(M / 2), i.e. -floor(M / 2) fs / M
-HZ_HD uint32_t chanbank_pos(uint32_t k, uint32_t M, bool negative_first) {
-    if (!negative_first) return k;
-    const uint32_t p = k + M / 2;
-    return p >= M ? p - M : p;
-}
+// ---- the counts, the rotation and the position map: the polyphase banks' own (hz_polyphase_plan.h) ------------
+using ppp::kPushMax;
+using ppp::State;
+using ppp::Step;
+// (under the names the kernel, tests/host/chanbank_plan.cpp and tests/host/chanbank_ref.cpp call them by)
+HZ_HD uint32_t chanbank_rot(uint32_t rot, uint64_t f, uint32_t D, uint32_t M) { return ppp::rot(rot, f, D, M); }
+inline Step chanbank_step(const State &s, uint32_t M, uint32_t L, uint32_t D, uint64_t n) { return ppp::step(s, M, L, D, n); }
+HZ_HD uint32_t chanbank_pos(uint32_t k, uint32_t M, bool negative_first) { return ppp::pos(k, M, negative_first); }
 
 // ---- the tile --------------------------------------------------------------------------------------------
 struct Geom {
@@ -87,7 +57,8 @@ struct Geom {
 
 inline uint32_t chanbank_b_floats(uint32_t Mp, uint32_t T) { return 2 * Mp * (T + 1); }
 
-inline Geom chanbank_geom(uint32_t M) {
+// (out of line, as chanbank_fill_a is: both stay in the library's symbol table)
+__attribute__((noinline)) inline Geom chanbank_geom(uint32_t M) {
     Geom g{};
     g.M = M;
     g.Mp = (M + 1) & ~1u;
@@ -174,7 +145,7 @@ inline std::vector<cb::c32> chanbank_tables(uint32_t M) {
 
 // A in operand order from the table: row 2k is (w.re, -w.im) interleaved over r, row 2k + 1 is (w.im, w.re); the rows
 // behind 2M are +0
-inline std::vector<float> chanbank_fill_a(const Geom &g, const std::vector<cb::c32> &W) {
+__attribute__((noinline)) inline std::vector<float> chanbank_fill_a(const Geom &g, const std::vector<cb::c32> &W) {
     std::vector<float> A(g.a_floats, 0.0f);
     for (uint32_t k = 0; k < g.M; k++)
         for (uint32_t r = 0; r < g.Mp; r++) {

@@ -9,40 +9,22 @@
 // frame offsets i_p = ((r - jD) mod M) + pM, for the samples and for the taps alike, so the transform's input is
 // u_j in natural order and nothing follows the transform but the store.  A sample is read by L/D frames: consecutive
 // frames are dealt to workgroups that share an XCD (and so an L2), which keeps the re-reads and the taps in that L2.
+//
+// This file: the kernel, its arguments, its dispatch and the ABI functions.  The object's host side (create, the push
+// around the launch, frames_for, pending, reset, free) is hz_polyphase.h, the stream arithmetic hz_polyphase_plan.h.
 #include "hz_chain_host.h"
 #include "../../include/hzsdr_channelizer.h"
 #include "hz_polyphase.h"
 
-struct hzsdr_channelizer {
-    hzsdr_ctx *ctx;
-    int fmt;
-    size_t m, ntaps, hop;
-    int order, layout;
+struct hzsdr_channelizer : hz::pp::Bank {
+    static constexpr const char *noun = "channelizer", *create_name = "channelizer_create";
+    static constexpr const char *format_why = "unknown source format", *channels_why = "the channel count is a power of two, 256 ... 8192";
+    static constexpr hz::ppp::ChannelRule rule = hz::ppp::kTransformRule;
+    static constexpr auto destroy = hzsdr_channelizer_free;
     hz::fv::FvTabs tabs{};
-    float *taps = nullptr;                 // the prototype, L values
-    float2 *tail[2] = {nullptr, nullptr};  // the samples held for the next frame, converted: read one, write the other
-    int tcur = 0;
-    size_t held = 0;     // samples held (below L)
-    size_t rot = 0;      // (stream position of the next frame's first sample) mod M
-    uint64_t frame = 0;  // index of the next frame
 };
 
 namespace hz {
-
-// what a push of n samples does, computed on the host before anything is launched
-struct ChanStep {
-    size_t V;  // samples of the virtual buffer: held ++ in
-    size_t F;  // frames that complete in the push
-    size_t new_held;
-};
-
-static ChanStep chan_step(const hzsdr_channelizer *c, size_t n) {
-    ChanStep p{};
-    p.V = c->held + n;
-    p.F = p.V >= c->ntaps ? (p.V - c->ntaps) / c->hop + 1 : 0;
-    p.new_held = p.V - p.F * c->hop;  // (hop <= M <= L: never a gap; below L)
-    return p;
-}
 
 // The frames of one launch.  Frame f (0-based within the push) starts at virtual index f*hop of
 // V = tail[0 .. held) ++ convert(in[0 ..)); its rotation is (rot + f*hop) mod M.
@@ -158,26 +140,11 @@ static int chan_launch_m(hzsdr_channelizer *c, const ChanArgs &a, float2 *out, s
     constexpr int XPB = fv::xpb(M);
     const dim3 grid((unsigned)((a.F + XPB - 1) / XPB)), block(fv::block(M));
     const size_t lds = (size_t)XPB * fv::lds_elems(M) * sizeof(cf);
-    const int neg = c->order == HZSDR_ORDER_NEGATIVE_FIRST;
-    if (c->layout == HZSDR_CHANNELIZER_FRAME_MAJOR)
-        HZ_TRY(launch_fv(channelizer_frames_kernel<M, FMT, HZSDR_CHANNELIZER_FRAME_MAJOR>, grid, block, lds, c->ctx->stream, a, out, stride, neg));
-    else
-        HZ_TRY(launch_fv(channelizer_frames_kernel<M, FMT, HZSDR_CHANNELIZER_CHANNEL_MAJOR>, grid, block, lds, c->ctx->stream, a, out, stride, neg));
+    HZ_TRY(pp::with_layout(c->layout, [&](auto l) {
+        return launch_fv(channelizer_frames_kernel<M, FMT, decltype(l)::value>, grid, block, lds, c->ctx->stream, a, out, stride, (int)c->negative_first());
+    }));
     HZ_HIP(c->ctx, hipGetLastError());
     return HZSDR_OK;
-}
-
-template <int FMT>
-static int chan_launch_fmt(hzsdr_channelizer *c, const ChanArgs &a, float2 *out, size_t stride) {
-    switch (c->m) {
-    case 256: return chan_launch_m<256, FMT>(c, a, out, stride);
-    case 512: return chan_launch_m<512, FMT>(c, a, out, stride);
-    case 1024: return chan_launch_m<1024, FMT>(c, a, out, stride);
-    case 2048: return chan_launch_m<2048, FMT>(c, a, out, stride);
-    case 4096: return chan_launch_m<4096, FMT>(c, a, out, stride);
-    case 8192: return chan_launch_m<8192, FMT>(c, a, out, stride);
-    default: return HZSDR_ERR_INVALID_ARGUMENT;
-    }
 }
 
 }  // namespace hz
@@ -187,91 +154,28 @@ extern "C" {
 int hzsdr_channelizer_create(hzsdr_ctx *ctx, int src_format, size_t channels, const float *taps, size_t n_taps, size_t hop,
                              int order, int layout, hzsdr_channelizer **out) {
     using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    const size_t m = channels;
-    if (format_size(src_format) == 0) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "channelizer: unknown source format");
-    if (m < 256 || m > 8192 || (m & (m - 1)) != 0)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: the channel count is a power of two, 256 ... 8192");
-    if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: null taps");
-    HZ_TRY(check_polyphase_args(ctx, "channelizer", m, n_taps, hop, order, layout));
-    HZ_TRY(enter(ctx));
-    hzsdr_channelizer *c = new hzsdr_channelizer{ctx, src_format, m, n_taps, hop, order, layout};
-    auto undo = [&](int rc) {
-        hzsdr_channelizer_free(c);
-        return rc;
-    };
-    int rc = get_fv_tables(ctx, m, &c->tabs);  // (plan-time: the transform's tables, not inside the first push)
-    if (rc != HZSDR_OK) return undo(rc);
-    hipError_t e = hipMalloc((void **)&c->taps, n_taps * sizeof(float));
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&c->tail[i], n_taps * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpyAsync(c->taps, taps, n_taps * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (taps is the caller's: free to go when create returns)
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "channelizer_create", __FILE__, __LINE__));
-    *out = c;
-    return HZSDR_OK;
+    // (plan-time: the transform's tables, not inside the first push)
+    return pp::create(ctx, src_format, channels, taps, n_taps, hop, order, layout, out,
+                      [&](hzsdr_channelizer *c, std::vector<Table> &) { return get_fv_tables(ctx, c->M, &c->tabs); });
 }
 
-int hzsdr_channelizer_frames_for(const hzsdr_channelizer *c, size_t n_in, size_t *frames) {
-    if (!c || !frames) return HZSDR_ERR_INVALID_ARGUMENT;
-    *frames = hz::chan_step(c, n_in).F;
-    return HZSDR_OK;
-}
+int hzsdr_channelizer_frames_for(const hzsdr_channelizer *c, size_t n_in, size_t *frames) { return hz::pp::frames_for(c, n_in, frames); }
 
 int hzsdr_channelizer_push(hzsdr_channelizer *c, const void *in, size_t n_in, void *out, size_t out_frames_cap, size_t out_stride,
                            size_t *frames_written) {
     using namespace hz;
-    if (frames_written) *frames_written = 0;
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    hzsdr_ctx *ctx = c->ctx;
-    if (n_in && !in) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "channelizer: null input");
-    const ChanStep p = chan_step(c, n_in);
-    const bool chmajor = c->layout == HZSDR_CHANNELIZER_CHANNEL_MAJOR;
-    const size_t M = c->m;
-    // (the rows of a push: M channels of F frames, out_stride apart, or -- frame-major -- one run of F * M values)
-    HZ_TRY(check_rows_out(ctx, "channelizer", chmajor ? M : 1, out, out_frames_cap, out_stride, p.F, 0));
-    HZ_TRY(enter(ctx));
-    if (n_in == 0) return HZSDR_OK;
-    Stage st(ctx);
-    const void *din;
-    void *dout;
-    size_t dstride;
-    HZ_TRY(st.in(0, in, n_in * (size_t)format_size(c->fmt), &din));
-    HZ_TRY(st.out_rows(1, out, chmajor ? M : 1, chmajor ? p.F : p.F * M, out_stride, sizeof(float2), &dout, &dstride, true));
-    const ChanArgs a{din, c->tail[c->tcur], c->held, c->hop, p.F, c->taps, c->tabs.fwd, (unsigned)c->rot, (unsigned)(c->ntaps / M)};
-    if (p.F) HZ_TRY(with_format(c->fmt, [&](auto f) { return chan_launch_fmt<decltype(f)::value>(c, a, (float2 *)dout, dstride); }));
-    if (p.new_held) {
-        HZ_TRY(hold_samples(ctx, c->fmt, din, a.tail, a.held, p.V - p.new_held, p.new_held, c->tail[c->tcur ^ 1]));
-        c->tcur ^= 1;
-    }
-    c->held = p.new_held;
-    c->rot = (c->rot + (p.F & (M - 1)) * c->hop) & (M - 1);  // (running value mod M: no product of stream length)
-    c->frame += p.F;
-    HZ_TRY(st.finish());
-    if (frames_written) *frames_written = p.F;
-    return HZSDR_OK;
+    return pp::push_frames(c, in, n_in, out, out_frames_cap, out_stride, frames_written, [&](const void *din, float2 *dout, size_t dstride, const ppp::Step &p) {
+        const ChanArgs a{din, c->held.now(), (size_t)c->st.held, c->D, (size_t)p.F, c->taps, c->tabs.fwd, c->st.rot, c->L / c->M};
+        return with_format(c->fmt, [&](auto f) {
+            return pp::with_fv_size(c->M, [&](auto m) { return chan_launch_m<decltype(m)::value, decltype(f)::value>(c, a, dout, dstride); });
+        });
+    });
 }
 
-int hzsdr_channelizer_pending(const hzsdr_channelizer *c, size_t *samples_held, uint64_t *frame_index) {
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (samples_held) *samples_held = c->held;
-    if (frame_index) *frame_index = c->frame;
-    return HZSDR_OK;
-}
+int hzsdr_channelizer_pending(const hzsdr_channelizer *c, size_t *samples_held, uint64_t *frame_index) { return hz::pp::pending(c, samples_held, frame_index); }
 
-int hzsdr_channelizer_reset(hzsdr_channelizer *c) {
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    // (the held samples are only read behind a later push's own writes: nothing to clear, nothing to wait for)
-    c->held = c->rot = 0;
-    c->frame = 0;
-    return HZSDR_OK;
-}
+int hzsdr_channelizer_reset(hzsdr_channelizer *c) { return hz::pp::reset(c); }
 
-int hzsdr_channelizer_free(hzsdr_channelizer *c) {
-    if (!c) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(c->ctx, {c->taps, c->tail[0], c->tail[1]});
-    delete c;
-    return HZSDR_OK;
-}
+int hzsdr_channelizer_free(hzsdr_channelizer *c) { return hz::pp::release(c); }
 
 }  // extern "C"

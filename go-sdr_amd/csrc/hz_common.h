@@ -229,6 +229,24 @@ inline int bank_upload(hzsdr_ctx *ctx, void *dst_dev, const void *src, size_t by
     return HZSDR_OK;
 }
 
+// a device table of `bytes` bytes (none: skipped) behind *dev, filled from `host` (null: left as it comes)
+// (hidden, as upload below: neither they nor a container of them are among the library's dynamic symbols)
+struct __attribute__((visibility("hidden"))) Table {
+    void **dev;
+    const void *host;
+    size_t bytes;
+};
+// a create's device memory: every table's memory first, then the contents; `what` names the create in a HIP error
+__attribute__((visibility("hidden"))) inline int upload(hzsdr_ctx *ctx, const char *what, const std::vector<Table> &tables) {
+    for (const Table &t : tables) {
+        const hipError_t e = t.bytes ? hipMalloc(t.dev, t.bytes) : hipSuccess;
+        if (e != hipSuccess) return hip_fail(ctx, e, what, __FILE__, __LINE__);
+    }
+    for (const Table &t : tables)
+        if (t.bytes && t.host) HZ_TRY(bank_upload(ctx, *t.dev, t.host, t.bytes));
+    return HZSDR_OK;
+}
+
 // (what the four row-wave banks -- IIR, symbol timing, carrier recovery, AGC -- share on top, a state array that the
 // caller may read and replace and parameter sets with a row per row, is hz_loopbank.h)
 // (what the two bit-ring banks -- frame sync, HDLC -- share on top is hz_framebank.h; what the three decoder banks --

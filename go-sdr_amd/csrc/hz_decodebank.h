@@ -5,7 +5,6 @@
 // as it was and keeps no state; the arithmetic of a call is hz_decodebank_plan.h.  Nothing here knows which bank it serves.
 // The demapper bank (hz_demap.hip) in front of them is the same call with floats on both sides and no info word: run().
 #pragma once
-#include <initializer_list>
 #include <string>
 
 #include "hz_common.h"
@@ -31,22 +30,9 @@ template <class F> int check_create(hzsdr_ctx *ctx, int kind, size_t rows, F **o
     return HZSDR_OK;
 }
 
-// a device table of `bytes` bytes (none: skipped) behind *dev, filled from `host` (null: left as it comes)
-struct Table {
-    void **dev;
-    const void *host;
-    size_t bytes;
-};
-// every table's memory first, then the contents; `what` names the create in a HIP error
-inline int upload(hzsdr_ctx *ctx, const char *what, std::initializer_list<Table> tables) {
-    for (const Table &t : tables) {
-        const hipError_t e = t.bytes ? hipMalloc(t.dev, t.bytes) : hipSuccess;
-        if (e != hipSuccess) return hip_fail(ctx, e, what, __FILE__, __LINE__);
-    }
-    for (const Table &t : tables)
-        if (t.bytes && t.host) HZ_TRY(bank_upload(ctx, *t.dev, t.host, t.bytes));
-    return HZSDR_OK;
-}
+// (a create's device tables: Table and upload of hz_common.h)
+using hz::Table;
+using hz::upload;
 
 // A call: the checks in their order, the rows staged (`isz`: the bytes of an input element), launch(FrameArgs, cap,
 // slots) -> status with the leading part of the kernel's arguments filled in, the rows brought back.

@@ -23,9 +23,9 @@ struct hzsdr_spectrum {
     int form = HZSDR_SPECTRUM_FORM_AUTO, last_form = 0;
     hz::fv::FvTabs tabs{};
     float *win = nullptr;                 // n window values (ones for a rectangular window)
-    float2 *tail[2] = {nullptr, nullptr}; // the samples held for the next frame, converted: read one, write the other
+    hz::pp::Held tail;                    // the samples held for the next frame, converted: read one, write the other
     float *acc[2] = {nullptr, nullptr};   // the partial row's float32 sums per bin (ZeroFirst), likewise
-    int tcur = 0, acur = 0;
+    int acur = 0;
     size_t held = 0, skip = 0, frames = 0;  // samples held, samples still to skip, frames summed into the open row
     float *scratch = nullptr;             // frame-parallel p_j, grow-only
     size_t scratch_cap = 0;
@@ -261,19 +261,6 @@ static int spec_launch_n(hzsdr_spectrum *s, const SpecArgs &a, float *out, int f
     return HZSDR_OK;
 }
 
-template <int FMT>
-static int spec_launch_fmt(hzsdr_spectrum *s, const SpecArgs &a, float *out, int form) {
-    switch (s->n) {
-    case 256: return spec_launch_n<256, FMT>(s, a, out, form);
-    case 512: return spec_launch_n<512, FMT>(s, a, out, form);
-    case 1024: return spec_launch_n<1024, FMT>(s, a, out, form);
-    case 2048: return spec_launch_n<2048, FMT>(s, a, out, form);
-    case 4096: return spec_launch_n<4096, FMT>(s, a, out, form);
-    case 8192: return spec_launch_n<8192, FMT>(s, a, out, form);
-    default: return HZSDR_ERR_INVALID_ARGUMENT;
-    }
-}
-
 // Auto: the row walk as long as the rows give every SIMD of the chip a wave of their own (a row is TPT lanes), the
 // frames dealt across the grid otherwise (few rows of many frames: the row walk would leave the chip idle).
 static int spec_pick_form(const hzsdr_spectrum *s, size_t F) {
@@ -311,7 +298,7 @@ int hzsdr_spectrum_create(hzsdr_ctx *ctx, int src_format, size_t n, size_t hop, 
     std::vector<float> w(n, 1.f);
     if (window) std::copy(window, window + n, w.begin());
     hipError_t e = hipMalloc((void **)&s->win, n * sizeof(float));
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&s->tail[i], n * sizeof(float2));
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&s->tail.buf[i], n * sizeof(float2));
     for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&s->acc[i], n * sizeof(float));
     if (e == hipSuccess) e = hipMemcpyAsync(s->win, w.data(), n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (w is a host vector of this frame)
@@ -346,16 +333,15 @@ int hzsdr_spectrum_push(hzsdr_spectrum *s, const void *in, size_t n_in, float *o
     void *dout = nullptr;
     HZ_TRY(st.in(0, (const char *)in + p.s0 * fs, mp * fs, &din));
     if (p.rows) HZ_TRY(st.out(1, out, p.rows * s->n * sizeof(float), &dout));
-    const SpecArgs a{din, s->tail[s->tcur], s->held, s->hop, p.F, s->win, s->tabs.fwd};
+    const SpecArgs a{din, s->tail.now(), s->held, s->hop, p.F, s->win, s->tabs.fwd};
     if (p.F) {
         const int form = spec_pick_form(s, p.F);
-        HZ_TRY(with_format(s->fmt, [&](auto f) { return spec_launch_fmt<decltype(f)::value>(s, a, (float *)dout, form); }));
+        HZ_TRY(with_format(s->fmt, [&](auto f) {
+            return pp::with_fv_size(s->n, [&](auto n) { return spec_launch_n<decltype(n)::value, decltype(f)::value>(s, a, (float *)dout, form); });
+        }));
         s->last_form = form;
     }
-    if (p.new_held) {
-        HZ_TRY(hold_samples(ctx, s->fmt, din, a.tail, a.held, p.L - p.new_held, p.new_held, s->tail[s->tcur ^ 1]));
-        s->tcur ^= 1;
-    }
+    HZ_TRY(pp::keep(ctx, s->fmt, s->tail, din, a.held, p.L - p.new_held, p.new_held));
     s->held = p.new_held;
     s->skip = p.new_skip;
     s->frames = p.new_frames;
@@ -394,7 +380,7 @@ int hzsdr_spectrum_reset(hzsdr_spectrum *s) {
 
 int hzsdr_spectrum_free(hzsdr_spectrum *s) {
     if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(s->ctx, {s->win, s->tail[0], s->tail[1], s->acc[0], s->acc[1], s->scratch});
+    hz::bank_release(s->ctx, {s->win, s->tail.buf[0], s->tail.buf[1], s->acc[0], s->acc[1], s->scratch});
     delete s;
     return HZSDR_OK;
 }

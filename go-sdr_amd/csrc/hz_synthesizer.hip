@@ -9,34 +9,26 @@
 // natural order to a device scratch.  synthesizer_ola_kernel: a lane per output position, the terms of the frames that
 // cover it in ascending order.  A position is covered by ceil(L / D) frames: consecutive frames are dealt to workgroups
 // that share an XCD, so that the second kernel's re-reads of w meet in one L2.  The held state makes a cut between two
-// frames free, so a push of any length is processed in groups whose scratch stays within kSynthScratchBytes.
+// frames free, so a push of any length is processed in groups whose scratch stays within ppp::kSynthScratchBytes.
+//
+// This file: the kernels, their arguments, their dispatch, the push over the groups and the flush.  What the object
+// shares with the channelizer and the channel bank on the host is hz_polyphase.h; the counts of a group and the position
+// behind it are hz_polyphase_plan.h.
 #include "hz_chain_host.h"
 #include "../../include/hzsdr_synthesizer.h"
 #include "hz_polyphase.h"
 
-struct hzsdr_synthesizer {
-    hzsdr_ctx *ctx;
-    int fmt;
-    size_t m, ntaps, hop;
-    int order, layout;
+struct hzsdr_synthesizer : hz::pp::Bank {
+    static constexpr const char *noun = "synthesizer", *create_name = "synthesizer_create";
+    static constexpr const char *format_why = "unknown destination format", *channels_why = "the channel count is a power of two, 256 ... 8192";
+    static constexpr hz::ppp::ChannelRule rule = hz::ppp::kTransformRule;
+    static constexpr auto destroy = hzsdr_synthesizer_free;
     hz::fv::FvTabs tabs{};
-    float *taps = nullptr;                 // the prototype, L values
-    float2 *hold[2] = {nullptr, nullptr};  // the L - D partial sums behind the samples written: read one, write the other
-    int hcur = 0;
     float2 *w = nullptr;  // the transforms' outputs of one group of frames
     size_t wcap = 0;      // ... frames it has room for
-    size_t held = 0;      // partial sums held: 0 before the first frame, L - D after it
-    size_t rot = 0;       // (stream position of the next frame's first sample) mod M
-    uint64_t frame = 0;   // index of the next frame
 };
 
 namespace hz {
-
-// The scratch one group of frames may take (group_frames * M * 8 bytes): small enough to stay in the memory-side cache
-// between the two kernels, large enough that the launches of a group do not show.
-constexpr size_t kSynthScratchBytes = (size_t)16 << 20;
-
-static size_t synth_group_frames(const hzsdr_synthesizer *s) { return kSynthScratchBytes / (s->m * sizeof(float2)); }
 
 // one term of the overlap-add: THE expression every path evaluates (one fused multiply-add per component)
 __device__ __forceinline__ float2 synth_term(float2 acc, float g, float2 w) { return make_float2(__fmaf_rn(g, w.x, acc.x), __fmaf_rn(g, w.y, acc.y)); }
@@ -154,28 +146,22 @@ static int synth_frames_m(hzsdr_synthesizer *s, const float2 *in, size_t stride,
     constexpr int XPB = fv::xpb(M);
     const dim3 grid((unsigned)((F + XPB - 1) / XPB)), block(fv::block(M));
     const size_t lds = (size_t)XPB * fv::lds_elems(M) * sizeof(cf);
-    const int neg = s->order == HZSDR_ORDER_NEGATIVE_FIRST;
-    if (s->layout == HZSDR_CHANNELIZER_FRAME_MAJOR)
-        HZ_TRY(launch_fv(synthesizer_frames_kernel<M, HZSDR_CHANNELIZER_FRAME_MAJOR>, grid, block, lds, s->ctx->stream, in, stride, F, s->tabs.bwd, s->w, neg));
-    else
-        HZ_TRY(launch_fv(synthesizer_frames_kernel<M, HZSDR_CHANNELIZER_CHANNEL_MAJOR>, grid, block, lds, s->ctx->stream, in, stride, F, s->tabs.bwd, s->w, neg));
+    HZ_TRY(pp::with_layout(s->layout, [&](auto l) {
+        return launch_fv(synthesizer_frames_kernel<M, decltype(l)::value>, grid, block, lds, s->ctx->stream, in, stride, F, s->tabs.bwd, s->w, (int)s->negative_first());
+    }));
     HZ_HIP(s->ctx, hipGetLastError());
     return HZSDR_OK;
 }
 
 static int synth_frames(hzsdr_synthesizer *s, const float2 *in, size_t stride, size_t F) {
-    switch (s->m) {
-    case 256: return synth_frames_m<256>(s, in, stride, F);
-    case 512: return synth_frames_m<512>(s, in, stride, F);
-    case 1024: return synth_frames_m<1024>(s, in, stride, F);
-    case 2048: return synth_frames_m<2048>(s, in, stride, F);
-    case 4096: return synth_frames_m<4096>(s, in, stride, F);
-    case 8192: return synth_frames_m<8192>(s, in, stride, F);
-    default: return HZSDR_ERR_INVALID_ARGUMENT;
-    }
+    return pp::with_fv_size(s->M, [&](auto m) { return synth_frames_m<decltype(m)::value>(s, in, stride, F); });
 }
 
-static int synth_ola(hzsdr_synthesizer *s, const SynthOla &a, void *out) {
+// one group's overlap-add (the flush: no frames): the counts of hz_polyphase_plan.h in the kernel's arguments
+static int synth_ola(hzsdr_synthesizer *s, const ppp::Group &g, void *out) {
+    const bool flush = g.F == 0;
+    const SynthOla a{flush ? nullptr : s->w, s->taps, s->held.now(), flush ? nullptr : s->held.next(), g.F, s->D, s->L, s->M - 1,
+                     flush ? 0u : s->st.rot, g.held, g.n_out, g.total};
     const dim3 grid((a.total + kThreads - 1) / kThreads), block(kThreads);
     with_format(s->fmt, [&](auto f) {
         constexpr int FMT = decltype(f)::value;
@@ -187,7 +173,7 @@ static int synth_ola(hzsdr_synthesizer *s, const SynthOla &a, void *out) {
 
 // room in the scratch for the largest group of a push of n frames (grow-only, before anything is launched)
 static int synth_scratch(hzsdr_synthesizer *s, size_t n) {
-    const size_t want = std::min(n, synth_group_frames(s));
+    const size_t want = ppp::scratch_frames(n, s->M);
     if (want <= s->wcap) return HZSDR_OK;
     if (s->w) {
         HZ_HIP(s->ctx, hipStreamSynchronize(s->ctx->stream));  // (enqueued work may still read the old one)
@@ -195,7 +181,7 @@ static int synth_scratch(hzsdr_synthesizer *s, size_t n) {
         s->w = nullptr;
         s->wcap = 0;
     }
-    HZ_HIP(s->ctx, hipMalloc((void **)&s->w, want * s->m * sizeof(float2)));
+    HZ_HIP(s->ctx, hipMalloc((void **)&s->w, want * s->M * sizeof(float2)));
     s->wcap = want;
     return HZSDR_OK;
 }
@@ -207,29 +193,9 @@ extern "C" {
 int hzsdr_synthesizer_create(hzsdr_ctx *ctx, int dst_format, size_t channels, const float *taps, size_t n_taps, size_t hop,
                              int order, int layout, hzsdr_synthesizer **out) {
     using namespace hz;
-    if (!ctx || !out) return HZSDR_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    const size_t m = channels;
-    if (format_size(dst_format) == 0) return fail(ctx, HZSDR_ERR_FORMAT_UNKNOWN, "synthesizer: unknown destination format");
-    if (m < 256 || m > 8192 || (m & (m - 1)) != 0)
-        return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: the channel count is a power of two, 256 ... 8192");
-    if (!taps) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null taps");
-    HZ_TRY(check_polyphase_args(ctx, "synthesizer", m, n_taps, hop, order, layout));
-    HZ_TRY(enter(ctx));
-    hzsdr_synthesizer *s = new hzsdr_synthesizer{ctx, dst_format, m, n_taps, hop, order, layout};
-    auto undo = [&](int rc) {
-        hzsdr_synthesizer_free(s);
-        return rc;
-    };
-    int rc = get_fv_tables(ctx, m, &s->tabs);  // (plan-time: the transform's tables, not inside the first push)
-    if (rc != HZSDR_OK) return undo(rc);
-    hipError_t e = hipMalloc((void **)&s->taps, n_taps * sizeof(float));
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&s->hold[i], n_taps * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpyAsync(s->taps, taps, n_taps * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (taps is the caller's: free to go when create returns)
-    if (e != hipSuccess) return undo(hip_fail(ctx, e, "synthesizer_create", __FILE__, __LINE__));
-    *out = s;
-    return HZSDR_OK;
+    // (plan-time: the transform's tables, not inside the first push)
+    return pp::create(ctx, dst_format, channels, taps, n_taps, hop, order, layout, out,
+                      [&](hzsdr_synthesizer *s, std::vector<Table> &) { return get_fv_tables(ctx, s->M, &s->tabs); });
 }
 
 int hzsdr_synthesizer_push(hzsdr_synthesizer *s, const void *frames, size_t n_frames, size_t in_stride, void *out, size_t out_cap,
@@ -238,8 +204,8 @@ int hzsdr_synthesizer_push(hzsdr_synthesizer *s, const void *frames, size_t n_fr
     if (samples_written) *samples_written = 0;
     if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
     hzsdr_ctx *ctx = s->ctx;
-    const bool chmajor = s->layout == HZSDR_CHANNELIZER_CHANNEL_MAJOR;
-    const size_t M = s->m, D = s->hop, L = s->ntaps, n_out = n_frames * D;
+    const bool chmajor = s->channel_major();
+    const size_t M = s->M, D = s->D, n_out = n_frames * D;
     if (n_frames && !frames) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: null input");
     if (chmajor && in_stride < n_frames) return fail(ctx, HZSDR_ERR_INVALID_ARGUMENT, "synthesizer: in_stride is below the frames of the push");
     HZ_TRY(check_rows_out(ctx, "synthesizer", 1, out, out_cap, 0, n_out, 0));
@@ -254,17 +220,13 @@ int hzsdr_synthesizer_push(hzsdr_synthesizer *s, const void *frames, size_t n_fr
     // (M channels of n_frames frames, in_stride apart, or -- frame-major -- one run of n_frames * M values)
     HZ_TRY(st.in_rows(0, frames, chmajor ? M : 1, chmajor ? n_frames : n_frames * M, in_stride, sizeof(float2), &din, &dstride));
     HZ_TRY(st.out(1, out, n_out * fs, &dout));
-    const size_t group = synth_group_frames(s);
+    const size_t group = ppp::group_frames(M);
     for (size_t f0 = 0; f0 < n_frames; f0 += group) {
         const size_t F = std::min(group, n_frames - f0);
         HZ_TRY(synth_frames(s, (const float2 *)din + (chmajor ? f0 : f0 * M), dstride, F));
-        const SynthOla a{s->w, s->taps, s->hold[s->hcur], s->hold[s->hcur ^ 1], (unsigned)F, (unsigned)D, (unsigned)L, (unsigned)(M - 1),
-                         (unsigned)s->rot, (unsigned)s->held, (unsigned)(F * D), (unsigned)(F * D + (L - D))};
-        HZ_TRY(synth_ola(s, a, (char *)dout + f0 * D * fs));
-        s->hcur ^= 1;
-        s->held = L - D;
-        s->rot = (s->rot + (F & (M - 1)) * D) & (M - 1);  // (running value mod M: no product of stream length)
-        s->frame += F;
+        HZ_TRY(synth_ola(s, ppp::group(s->st, s->L, s->D, F), (char *)dout + f0 * D * fs));
+        s->held.flip();
+        s->st = ppp::after_group(s->st, s->M, s->L, s->D, F);
     }
     HZ_TRY(st.finish());
     if (samples_written) *samples_written = n_out;
@@ -276,50 +238,31 @@ int hzsdr_synthesizer_flush(hzsdr_synthesizer *s, void *out, size_t out_cap, siz
     if (samples_written) *samples_written = 0;
     if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
     hzsdr_ctx *ctx = s->ctx;
-    const size_t n = s->held;
+    const size_t n = (size_t)s->st.held;
     HZ_TRY(check_rows_out(ctx, "synthesizer", 1, out, out_cap, 0, n, 0));
     HZ_TRY(enter(ctx));
     if (n) {
         Stage st(ctx);
         void *dout;
         HZ_TRY(st.out(1, out, n * (size_t)format_size(s->fmt), &dout));
-        const SynthOla a{nullptr, s->taps, s->hold[s->hcur], nullptr, 0u, (unsigned)s->hop, (unsigned)s->ntaps, (unsigned)(s->m - 1),
-                         0u, (unsigned)n, (unsigned)n, (unsigned)n};
-        HZ_TRY(synth_ola(s, a, dout));
+        HZ_TRY(synth_ola(s, ppp::flush_group(s->st), dout));
         HZ_TRY(st.finish());
     }
-    s->held = s->rot = 0;
-    s->frame = 0;
+    s->st = ppp::State{};
     if (samples_written) *samples_written = n;
     return HZSDR_OK;
 }
 
-int hzsdr_synthesizer_pending(const hzsdr_synthesizer *s, size_t *samples_held, uint64_t *frame_index) {
-    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
-    if (samples_held) *samples_held = s->held;
-    if (frame_index) *frame_index = s->frame;
-    return HZSDR_OK;
-}
+int hzsdr_synthesizer_pending(const hzsdr_synthesizer *s, size_t *samples_held, uint64_t *frame_index) { return hz::pp::pending(s, samples_held, frame_index); }
 
 int hzsdr_synthesizer_group_frames(const hzsdr_synthesizer *s, size_t *frames) {
     if (!s || !frames) return HZSDR_ERR_INVALID_ARGUMENT;
-    *frames = hz::synth_group_frames(s);
+    *frames = hz::ppp::group_frames(s->M);
     return HZSDR_OK;
 }
 
-int hzsdr_synthesizer_reset(hzsdr_synthesizer *s) {
-    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
-    // (the held sums are only read behind a later push's own writes: nothing to clear, nothing to wait for)
-    s->held = s->rot = 0;
-    s->frame = 0;
-    return HZSDR_OK;
-}
+int hzsdr_synthesizer_reset(hzsdr_synthesizer *s) { return hz::pp::reset(s); }
 
-int hzsdr_synthesizer_free(hzsdr_synthesizer *s) {
-    if (!s) return HZSDR_ERR_INVALID_ARGUMENT;
-    hz::bank_release(s->ctx, {s->taps, s->hold[0], s->hold[1], s->w});
-    delete s;
-    return HZSDR_OK;
-}
+int hzsdr_synthesizer_free(hzsdr_synthesizer *s) { return hz::pp::release(s, {s ? s->w : nullptr}); }
 
 }  // extern "C"

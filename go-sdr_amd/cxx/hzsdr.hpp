@@ -942,161 +942,137 @@ private:
     hzsdr_spectrum *s_ = nullptr;
 };
 
-// The polyphase channelizer (include/hzsdr_channelizer.h): Push consumes every sample it is given and returns the
-// frames that complete as complex64, frames x channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames
-// (HZSDR_CHANNELIZER_CHANNEL_MAJOR, the pitch being the frames of the push), in the channelizer's fft.Order
-// (fft/result.go:34-47).
-class Channelizer {
+// What the three polyphase bank classes below share: the handle and its life, Pending, Reset and Channels.  H is the
+// handle, the rest hzsdr_<bank>_pending, _reset and _free.
+template <class H, auto PendingFn, auto ResetFn, auto FreeFn>
+class PolyphaseBank {
 public:
-    Channelizer(const Context &x, int src_format, size_t channels, const std::vector<float> &taps, size_t hop,
-                int order = HZSDR_ORDER_NEGATIVE_FIRST, int layout = HZSDR_CHANNELIZER_FRAME_MAJOR)
-        : x_(x), m_(channels) {
-        check(x_.raw(), hzsdr_channelizer_create(x_.raw(), src_format, channels, taps.empty() ? nullptr : taps.data(), taps.size(), hop,
-                                                 order, layout, &c_));
+    PolyphaseBank(const PolyphaseBank &) = delete;
+    PolyphaseBank &operator=(const PolyphaseBank &) = delete;
+    // -> (samples held for the next frame -- the synthesis bank: partial sums held behind the samples written --, index
+    // of the next frame)
+    std::pair<size_t, uint64_t> Pending() const {
+        size_t h = 0;
+        uint64_t j = 0;
+        check(x_.raw(), PendingFn(h_, &h, &j));
+        return {h, j};
     }
-    ~Channelizer() { if (c_) hzsdr_channelizer_free(c_); }
-    Channelizer(const Channelizer &) = delete;
-    Channelizer &operator=(const Channelizer &) = delete;
+    void Reset() { check(x_.raw(), ResetFn(h_)); }
+    size_t Channels() const { return m_; }
+
+protected:
+    PolyphaseBank(const Context &x, size_t channels) : x_(x), m_(channels) {}
+    ~PolyphaseBank() { if (h_) FreeFn(h_); }
+    const Context &x_;
+    size_t m_;
+    H *h_ = nullptr;
+};
+// ... and the two analysis banks on top of it: the create, FramesFor and Push, over hzsdr_<bank>_create, _frames_for and
+// _push.
+template <class H, auto CreateFn, auto FramesForFn, auto PushFn, auto PendingFn, auto ResetFn, auto FreeFn>
+class AnalysisBank : public PolyphaseBank<H, PendingFn, ResetFn, FreeFn> {
+public:
     size_t FramesFor(size_t n_in) const {
         size_t f = 0;
-        check(x_.raw(), hzsdr_channelizer_frames_for(c_, n_in, &f));
+        check(this->x_.raw(), FramesForFn(this->h_, n_in, &f));
         return f;
     }
     // (a HOST context's buffers: the frames come back in a vector)
     std::vector<std::complex<float>> Push(Samples in) {
         const size_t want = FramesFor(in.length);
-        std::vector<std::complex<float>> out(want * m_);
+        std::vector<std::complex<float>> out(want * this->m_);
         size_t frames = 0;
-        check(x_.raw(), hzsdr_channelizer_push(c_, in.data, in.length, out.empty() ? nullptr : out.data(), want, want, &frames));
+        check(this->x_.raw(), PushFn(this->h_, in.data, in.length, out.empty() ? nullptr : out.data(), want, want, &frames));
         return out;
     }
-    // -> (samples held for the next frame, index of the next frame)
-    std::pair<size_t, uint64_t> Pending() const {
-        size_t h = 0;
-        uint64_t j = 0;
-        check(x_.raw(), hzsdr_channelizer_pending(c_, &h, &j));
-        return {h, j};
-    }
-    void Reset() { check(x_.raw(), hzsdr_channelizer_reset(c_)); }
-    size_t Channels() const { return m_; }
 
-private:
-    const Context &x_;
-    size_t m_;
-    hzsdr_channelizer *c_ = nullptr;
+protected:
+    AnalysisBank(const Context &x, int src_format, size_t channels, const std::vector<float> &taps, size_t hop, int order, int layout)
+        : PolyphaseBank<H, PendingFn, ResetFn, FreeFn>(x, channels) {
+        check(x.raw(), CreateFn(x.raw(), src_format, channels, taps.empty() ? nullptr : taps.data(), taps.size(), hop, order, layout, &this->h_));
+    }
+};
+
+// The polyphase channelizer (include/hzsdr_channelizer.h): Push consumes every sample it is given and returns the
+// frames that complete as complex64, frames x channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames
+// (HZSDR_CHANNELIZER_CHANNEL_MAJOR, the pitch being the frames of the push), in the channelizer's fft.Order
+// (fft/result.go:34-47).
+class Channelizer : public AnalysisBank<hzsdr_channelizer, hzsdr_channelizer_create, hzsdr_channelizer_frames_for, hzsdr_channelizer_push,
+                                        hzsdr_channelizer_pending, hzsdr_channelizer_reset, hzsdr_channelizer_free> {
+public:
+    Channelizer(const Context &x, int src_format, size_t channels, const std::vector<float> &taps, size_t hop,
+                int order = HZSDR_ORDER_NEGATIVE_FIRST, int layout = HZSDR_CHANNELIZER_FRAME_MAJOR)
+        : AnalysisBank(x, src_format, channels, taps, hop, order, layout) {}
 };
 // The channel bank (include/hzsdr_chanbank.h): the polyphase channelizer for the small channel counts, any `channels`
 // from 2 to 255.  Push consumes every sample it is given and returns the frames that complete as complex64, frames x
 // channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames (HZSDR_CHANNELIZER_CHANNEL_MAJOR, the pitch being the
 // frames of the push); HZSDR_ORDER_NEGATIVE_FIRST is ascending signed frequency, position 0 at -floor(channels / 2).
-class ChannelBank {
+class ChannelBank : public AnalysisBank<hzsdr_chanbank, hzsdr_chanbank_create, hzsdr_chanbank_frames_for, hzsdr_chanbank_push, hzsdr_chanbank_pending,
+                                        hzsdr_chanbank_reset, hzsdr_chanbank_free> {
 public:
     ChannelBank(const Context &x, int src_format, size_t channels, const std::vector<float> &taps, size_t hop,
                 int order = HZSDR_ORDER_NEGATIVE_FIRST, int layout = HZSDR_CHANNELIZER_FRAME_MAJOR)
-        : x_(x), m_(channels), l_(taps.size()) {
-        check(x_.raw(), hzsdr_chanbank_create(x_.raw(), src_format, channels, taps.empty() ? nullptr : taps.data(), taps.size(), hop, order,
-                                              layout, &c_));
-    }
-    ~ChannelBank() { if (c_) hzsdr_chanbank_free(c_); }
-    ChannelBank(const ChannelBank &) = delete;
-    ChannelBank &operator=(const ChannelBank &) = delete;
-    size_t FramesFor(size_t n_in) const {
-        size_t f = 0;
-        check(x_.raw(), hzsdr_chanbank_frames_for(c_, n_in, &f));
-        return f;
-    }
-    // (a HOST context's buffers: the frames come back in a vector)
-    std::vector<std::complex<float>> Push(Samples in) {
-        const size_t want = FramesFor(in.length);
-        std::vector<std::complex<float>> out(want * m_);
-        size_t frames = 0;
-        check(x_.raw(), hzsdr_chanbank_push(c_, in.data, in.length, out.empty() ? nullptr : out.data(), want, want, &frames));
-        return out;
-    }
-    // -> (samples held for the next frame, index of the next frame)
-    std::pair<size_t, uint64_t> Pending() const {
-        size_t h = 0;
-        uint64_t j = 0;
-        check(x_.raw(), hzsdr_chanbank_pending(c_, &h, &j));
-        return {h, j};
-    }
+        : AnalysisBank(x, src_format, channels, taps, hop, order, layout), l_(taps.size()) {}
     // -> (frames per workgroup, rows of the real matrix per workgroup, HZSDR_CHANBANK_FORM_*)
     std::tuple<size_t, size_t, int> Plan() const {
         size_t t = 0, r = 0;
         int f = 0;
-        check(x_.raw(), hzsdr_chanbank_plan(c_, &t, &r, &f));
+        check(x_.raw(), hzsdr_chanbank_plan(h_, &t, &r, &f));
         return {t, r, f};
     }
     // row k of the DFT table: the channels rounded up to an even count of complex64 values
     std::vector<std::complex<float>> Table(size_t k) const {
         std::vector<std::complex<float>> out((m_ + 1) & ~(size_t)1);
-        check(x_.raw(), hzsdr_chanbank_readout(c_, HZSDR_CHANBANK_READ_DFT, k, out.data(), out.size()));
+        check(x_.raw(), hzsdr_chanbank_readout(h_, HZSDR_CHANBANK_READ_DFT, k, out.data(), out.size()));
         return out;
     }
     std::vector<float> Taps() const {
         std::vector<float> out(l_);
-        check(x_.raw(), hzsdr_chanbank_readout(c_, HZSDR_CHANBANK_READ_TAPS, 0, out.data(), out.size()));
+        check(x_.raw(), hzsdr_chanbank_readout(h_, HZSDR_CHANBANK_READ_TAPS, 0, out.data(), out.size()));
         return out;
     }
-    void Reset() { check(x_.raw(), hzsdr_chanbank_reset(c_)); }
-    size_t Channels() const { return m_; }
 
 private:
-    const Context &x_;
-    size_t m_, l_;
-    hzsdr_chanbank *c_ = nullptr;
+    size_t l_;
 };
 // The polyphase synthesis bank (include/hzsdr_synthesizer.h), the channelizer's adjoint: Push consumes frames of
 // `channels` complex64 values, frames x channels (HZSDR_CHANNELIZER_FRAME_MAJOR) or channels x frames
 // (HZSDR_CHANNELIZER_CHANNEL_MAJOR, the pitch being the frames of the push), in the synthesizer's fft.Order
 // (fft/result.go:34-47), and returns the frames * hop samples they complete in the destination format; Flush returns
 // the stream's tail and starts over.
-class Synthesizer {
+class Synthesizer : public PolyphaseBank<hzsdr_synthesizer, hzsdr_synthesizer_pending, hzsdr_synthesizer_reset, hzsdr_synthesizer_free> {
 public:
     Synthesizer(const Context &x, int dst_format, size_t channels, const std::vector<float> &taps, size_t hop,
                 int order = HZSDR_ORDER_NEGATIVE_FIRST, int layout = HZSDR_CHANNELIZER_FRAME_MAJOR)
-        : x_(x), fmt_(dst_format), m_(channels), hop_(hop) {
+        : PolyphaseBank(x, channels), fmt_(dst_format), hop_(hop) {
         check(x_.raw(), hzsdr_synthesizer_create(x_.raw(), dst_format, channels, taps.empty() ? nullptr : taps.data(), taps.size(), hop,
-                                                 order, layout, &s_));
+                                                 order, layout, &h_));
     }
-    ~Synthesizer() { if (s_) hzsdr_synthesizer_free(s_); }
-    Synthesizer(const Synthesizer &) = delete;
-    Synthesizer &operator=(const Synthesizer &) = delete;
     // (a HOST context's buffers: the samples come back in a Buffer of the destination format)
     Buffer Push(const std::vector<std::complex<float>> &frames) {
         const size_t f = frames.size() / m_;
         Buffer out(fmt_, f * hop_);
         size_t n = 0;
-        check(x_.raw(), hzsdr_synthesizer_push(s_, frames.empty() ? nullptr : frames.data(), f, f, out.view.length ? out.view.data : nullptr,
+        check(x_.raw(), hzsdr_synthesizer_push(h_, frames.empty() ? nullptr : frames.data(), f, f, out.view.length ? out.view.data : nullptr,
                                                out.view.length, &n));
         return out;
     }
     Buffer Flush() {
         Buffer out(fmt_, Pending().first);
         size_t n = 0;
-        check(x_.raw(), hzsdr_synthesizer_flush(s_, out.view.length ? out.view.data : nullptr, out.view.length, &n));
+        check(x_.raw(), hzsdr_synthesizer_flush(h_, out.view.length ? out.view.data : nullptr, out.view.length, &n));
         return out;
-    }
-    // -> (partial sums held behind the samples written, index of the next frame)
-    std::pair<size_t, uint64_t> Pending() const {
-        size_t h = 0;
-        uint64_t j = 0;
-        check(x_.raw(), hzsdr_synthesizer_pending(s_, &h, &j));
-        return {h, j};
     }
     size_t GroupFrames() const {
         size_t f = 0;
-        check(x_.raw(), hzsdr_synthesizer_group_frames(s_, &f));
+        check(x_.raw(), hzsdr_synthesizer_group_frames(h_, &f));
         return f;
     }
-    void Reset() { check(x_.raw(), hzsdr_synthesizer_reset(s_)); }
-    size_t Channels() const { return m_; }
 
 private:
-    const Context &x_;
     int fmt_;
-    size_t m_, hop_;
-    hzsdr_synthesizer *s_ = nullptr;
+    size_t hop_;
 };
 }  // namespace fft
 

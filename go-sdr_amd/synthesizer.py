@@ -17,11 +17,11 @@ import ctypes as C
 
 import numpy as np
 
-from . import _is_torch, _ptr, ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, lib, MEM_HOST  # noqa: F401
+from . import _is_torch, _ptr, ErrDstTooSmall, ErrInvalidArgument, FMT_C64, FMT_I8, FMT_I16, FMT_U8, MEM_HOST  # noqa: F401
 from ._capi import CHANNELIZER_CHANNEL_MAJOR, CHANNELIZER_FRAME_MAJOR
+from ._polyphase import _PolyphaseBank
 from ._rows import device_like, torch_dtype
-from .channelizer import _LAYOUTS
-from .spectrum import NegativeFirst, ZeroFirst, _order
+from .spectrum import NegativeFirst, ZeroFirst
 
 _NP_OUT = {FMT_C64: (np.complex64, ()), FMT_U8: (np.uint8, (2,)), FMT_I8: (np.int8, (2,)), FMT_I16: (np.int16, (2,))}
 
@@ -37,34 +37,21 @@ def wola_taps(channels):
     return np.sin(np.pi * np.arange(m, dtype=np.float64) / m).astype(np.float32)
 
 
-class Synthesizer:
+class Synthesizer(_PolyphaseBank):
     """hzsdr_synthesizer: push(frames) -> the frames * hop samples they complete, in the destination format (numpy for
     a HOST context, a torch tensor on the frames' device, written on the context's stream, for a DEVICE context);
-    flush() -> the stream's tail."""
+    flush() -> the stream's tail.  The object's life, channel_major, reset and close are _polyphase._PolyphaseBank's."""
+    _c, _noun = "synthesizer", "synthesizer"
 
     def __init__(self, ctx, dst_fmt, channels, taps, hop=None, order=NegativeFirst, layout="frames"):
-        self.ctx, self.dst_fmt, self.channels = ctx, dst_fmt, int(channels)
-        self.hop = self.channels if hop is None else int(hop)
-        self.order = _order(order)
-        if layout not in _LAYOUTS:
-            raise ValueError(f"synthesizer: unknown layout {layout!r}")
-        self.layout = _LAYOUTS[layout]
-        self.taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        if self.channels <= 0 or self.hop <= 0:
-            raise ErrInvalidArgument("synthesizer: channels and hop are at least 1")
-        self._h = C.c_void_p()
-        ctx._ck(lib.hzsdr_synthesizer_create(ctx._h, dst_fmt, self.channels, self.taps.ctypes.data_as(C.POINTER(C.c_float)),
-                                             self.taps.shape[0], self.hop, self.order, self.layout, C.byref(self._h)))
-
-    @property
-    def channel_major(self):
-        return self.layout == CHANNELIZER_CHANNEL_MAJOR
+        self.dst_fmt = dst_fmt
+        self._open(ctx, dst_fmt, channels, taps, hop, order, layout)
 
     @property
     def group_frames(self):
         """Frames per internal launch group: a longer push is processed in groups of this many."""
         f = C.c_size_t(0)
-        self.ctx._ck(lib.hzsdr_synthesizer_group_frames(self._h, C.byref(f)))
+        self._call("group_frames", C.byref(f))
         return f.value
 
     def _empty(self, n, like):
@@ -112,7 +99,7 @@ class Synthesizer:
             out = self._empty(f * self.hop, frames)
         cap = int(out.shape[0])
         got = C.c_size_t(0)
-        self.ctx._ck(lib.hzsdr_synthesizer_push(self._h, ptr, f, pitch, _ptr(out) if cap else None, cap, C.byref(got)))
+        self._call("push", ptr, f, pitch, _ptr(out) if cap else None, cap, C.byref(got))
         return out[:got.value]
 
     def flush(self, out=None):
@@ -123,32 +110,16 @@ class Synthesizer:
             out = self._empty(held, device_like(self.ctx))
         cap = int(out.shape[0])
         got = C.c_size_t(0)
-        self.ctx._ck(lib.hzsdr_synthesizer_flush(self._h, _ptr(out) if cap else None, cap, C.byref(got)))
+        self._call("flush", _ptr(out) if cap else None, cap, C.byref(got))
         return out[:got.value]
 
     def pending(self):
         """(partial sums held behind the samples written, index of the next frame)."""
-        h, j = C.c_size_t(0), C.c_uint64(0)
-        self.ctx._ck(lib.hzsdr_synthesizer_pending(self._h, C.byref(h), C.byref(j)))
-        return h.value, j.value
-
-    def reset(self):
-        self.ctx._ck(lib.hzsdr_synthesizer_reset(self._h))
+        return self._pending()
 
     def sample_rate(self, channel_rate):
         """The sample rate of the output stream: channel_rate * hop."""
         return float(channel_rate) * self.hop
-
-    def close(self):
-        if self._h:
-            lib.hzsdr_synthesizer_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 __all__ = ["Synthesizer", "wola_taps", "ZeroFirst", "NegativeFirst", "CHANNELIZER_FRAME_MAJOR", "CHANNELIZER_CHANNEL_MAJOR"]

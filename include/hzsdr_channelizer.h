@@ -70,7 +70,8 @@ int hzsdr_channelizer_create(hzsdr_ctx *ctx, int src_format, size_t channels, co
  * device.  HZSDR_ERR_DST_TOO_SMALL when out_frames_cap, or the channel-major
  * out_stride, is below the frames the push completes: checked before anything
  * is launched; the state is unchanged.  Stream-ordered on the context's
- * stream; HOST contexts stage `in` and `out`. */
+ * stream; HOST contexts stage `in` and `out`.
+ * HZSDR_ERR_INVALID_ARGUMENT ("the push is too long") for n_in above 2^62, here and in frames_for. */
 int hzsdr_channelizer_push(hzsdr_channelizer *c, const void *in, size_t n_in, void *out, size_t out_frames_cap,
                            size_t out_stride, size_t *frames_written);
 /* The frames a push of n_in samples would write now. */

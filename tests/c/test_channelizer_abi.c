@@ -63,6 +63,9 @@ int main(void) {
     CHECK(hzsdr_channelizer_push(z, x, LEN, a, FRAMES - 1, 0, &got) == HZSDR_ERR_DST_TOO_SMALL && got == 0);
     OK(hzsdr_channelizer_pending(z, &held, &next));
     CHECK(held == 0 && next == 0);
+    /* a push above 2^62 samples: refused before a count is formed, by push and by frames_for alike */
+    CHECK(hzsdr_channelizer_push(z, x, ((size_t)1 << 62) + 1, a, FRAMES, 0, &got) == HZSDR_ERR_INVALID_ARGUMENT && got == 0);
+    CHECK(hzsdr_channelizer_frames_for(z, ((size_t)1 << 62) + 1, &frames) == HZSDR_ERR_INVALID_ARGUMENT);
     OK(hzsdr_channelizer_push(z, x, LEN, a, FRAMES, 0, &got));
     CHECK(got == FRAMES);
     OK(hzsdr_channelizer_pending(z, &held, &next));
